@@ -8,8 +8,15 @@ int16 PCM (processSSB_opt, src/ssb/ssb_demod_opt.cpp:221-296; the reference's 25
 Inputs are synthetic CW tones + noise, resident in HBM before the timed region; every step does the full
 work (the per-stream filter state advances from step to step like a live receiver).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one process per GPU)
+
+A plain run does what the headline needs and no more: set up, pre-roll and warm up, time the K steps, write the
+last timed step's outputs (--dump-outputs) and print the line (value, ms_per_step, and what the timed region's own
+HIP events give: kernel_ms, roofline, roofline_step).  --full adds every leg that takes runs of its own after the
+timed region: the stages alone (roofline_isolated, ssb_latency_floor, roofline_ssb), the HBM copy rates
+(hbm_measured), the labelled configs[1] / configs[2] / configs[4] lines, the CPU baseline and, at N > 1, the
+full-spectra gather and the gather check.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N rank processes itself
 (torch.distributed.run as a child process, before anything touches a GPU) and exits with their status.
@@ -18,7 +25,7 @@ spectra) of each step are gathered to rank 0 by libsdrg.so's own RCCL ncclGather
 sdrg_engine_gather, the C ABI a C/C++ host behind JNI calls; torch.distributed only carries the control plane:
 the communicator id, barriers and the max-over-ranks time, over gloo); value = all ranks' samples /
 max-over-ranks time.  The full-spectra gather (the fftCallback payload) is timed after the timed region and
-reported separately.
+reported separately (--full).
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -52,6 +59,8 @@ PROFILED_STEPS = 20  # labelled lines: steps of the separate profiled pass behin
 LABELLED_MIN_STEPS = 100
 LAB_HOST_TIMES = os.environ.get("SDRG_BENCH_HOST_TIMES") == "1"
 LAB_NO_STEP_GATHER = os.environ.get("SDRG_BENCH_NO_STEP_GATHER") == "1"  # lab: the N > 1 path without its per-step gathers
+DUMP_SPECTRA_BYTES = 32 << 20  # --dump-outputs: spectra of a seeded sample of streams up to this size ...
+DUMP_PCM_BYTES = 16 << 20  # ... and every stream's PCM up to this one as float32: under 64 MB with the records
 N_OUTPUTS = 3  # spectra / records buffers rotated per step (asynchronous statistics read a call's spectra late)
 # SSB floor: the sample-serial low-pass wave's own instruction issue.  Per sample it issues 6 VALU instructions
 # (the packed product of the previous output, 4 dependent adds, the packed product of the output before it) and
@@ -164,6 +173,45 @@ def cpu_baseline(threads: int, target_cpu_s: float = 15.0) -> dict:
                       f"{per_frame * 1e3:.3f} ms/frame single-thread"}
 
 
+def fields_f64(a: np.ndarray) -> np.ndarray:
+    """A structured array as float64 [len, fields], fields in dtype order (float32 and int32 exactly; the int64
+    fields, a frequency in Hz, far below 2^53)."""
+    return np.stack([a[k].astype(np.float64) for k in a.dtype.names], axis=1)
+
+
+def dump_outputs(torch, eng, out_dir: str, prefix: str, stages: int, spec, rec, pcm) -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last step, as out_dir/<prefix><name>.npy.
+    spectra: float32 [k, n], the streams listed in sample_streams (a fixed seeded sample, DUMP_SPECTRA_BYTES at
+    the most); records: float64 [streams, fields of RECORD_DTYPE]; pcm: float32 [streams, pcm_len] (the sampled
+    streams only where every stream's would pass DUMP_PCM_BYTES); pulse_spectral / pulse_audio: float64 [streams,
+    fields of PULSE_OUTPUT_DTYPE].  Only what the stages that ran produced."""
+    import sdrg
+    os.makedirs(out_dir, exist_ok=True)
+    eng.synchronize()
+    torch.cuda.synchronize()
+    streams, n = spec.shape
+    k = min(streams, max(1, DUMP_SPECTRA_BYTES // (4 * n)))
+    rows = np.sort(np.random.default_rng(0xD0).choice(streams, size=k, replace=False))
+    rows_dev = torch.as_tensor(rows, device=spec.device)
+    out = {"sample_streams": rows.astype(np.float64)}
+    if stages & sdrg.STAGE_SPECTRUM:
+        out["spectra"] = spec[rows_dev].cpu().numpy()
+    if stages & sdrg.STAGE_STATS:
+        out["records"] = fields_f64(rec.cpu().numpy().view(sdrg.RECORD_DTYPE).reshape(-1))
+    if stages & sdrg.STAGE_SSB:
+        every = pcm.numel() * 4 <= DUMP_PCM_BYTES
+        out["pcm"] = (pcm if every else pcm[rows_dev]).cpu().numpy().astype(np.float32)
+    sp, au = eng.pulse_outputs(spectral=bool(stages & sdrg.STAGE_SPECTRAL_PULSE),
+                               audio=bool(stages & sdrg.STAGE_AUDIO_PULSE))
+    if sp is not None:
+        out["pulse_spectral"] = fields_f64(sp)
+    if au is not None:
+        out["pulse_audio"] = fields_f64(au)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+    log(f"bench: wrote {', '.join(out)} ({sum(a.nbytes for a in out.values()) / 2**20:.1f} MiB) to {out_dir}")
+
+
 def rehearsal_verify(torch, dist, world, rank, streams, rec, f_stage, pcm, gather_pcm, gathered, f_out, p_out):
     """--rehearse-gloo: after the timed steps, every rank hashes what it contributed to the last step's gathers
     (records, focus slices, PCM bytes) and rank 0 checks that each rank's block of its gathered buffers hashes
@@ -238,7 +286,15 @@ def main() -> int:
     # 25-step blocks at 0.36, 0.345, then 0.34 ms/step), so the default warmup covers that ramp
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--streams", type=int, default=B)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs that take runs of their own: the stages alone, the "
+                         "HBM copy rates, the labelled configs lines, the CPU baseline, and at N > 1 the full-spectra "
+                         "gather and the gather check (off by default: a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / "
+                         "float64): the spectra of a fixed seeded sample of streams, every stream's records, PCM and "
+                         "pulse-detector outputs; the same arguments give the same inputs and stream states every run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 (default): every core granted (host_cores)")
     ap.add_argument("--no-labelled", action="store_true", help="skip the labelled configs[1]/configs[2] legs")
     ap.add_argument("--pipelined", type=int, default=2, choices=[0, 1, 2],
@@ -469,6 +525,12 @@ def main() -> int:
         prewarm_steps += 25
         eng.synchronize()
     prewarm_ms = (time.perf_counter() - t_pre) * 1e3
+    # the pre-roll runs for a time, not a count: every stream starts over behind it (filter, AGC, statistics and
+    # detector state, input rotation, clock), so the timed steps see the same inputs and states in every run
+    eng.reset_state()
+    calls[0], now[0] = 0, 1000
+    for _ in range(N_INPUTS):  # the first call after a reset designs the filters on the host: never a timed step
+        step()
     for _ in range(args.warmup):
         step()
     eng.synchronize()
@@ -489,8 +551,10 @@ def main() -> int:
     if LAB_HOST_TIMES and host_t[2]:
         log(f"bench: host us per step: process_device {host_t[0] / host_t[2] * 1e6:.1f}, gather "
             f"{host_t[1] / host_t[2] * 1e6:.1f} over {host_t[2]} timed calls")
+    if args.dump_outputs:  # before any later leg writes into the same buffers
+        dump_outputs(torch, eng, args.dump_outputs, f"rank{rank}_" if world > 1 else "", stages, spec, rec, pcm)
     spectra_gather = None
-    if dist_on and args.spectra_gather_steps > 0:
+    if args.full and dist_on and args.spectra_gather_steps > 0:
         # the full spectra of every frame (fftCallback payload) to rank 0, timed on its own: outside the metric
         eng.synchronize()
         s_out = torch.empty((world * streams, n), dtype=torch.float32, device=gdev) if rank == 0 else None
@@ -523,7 +587,7 @@ def main() -> int:
                                   "payload, SURVEY 8e), after the timed region; not part of value"}
         del s_out
     # every rank hashes what it contributed to the last step's gathers; rank 0 checks its gathered blocks (any backend)
-    if dist_on:
+    if args.full and dist_on:
         eng.synchronize()
         f_mine = (f_stage if rehearse else spec[:, f_lo:f_lo + f_n].contiguous()) if focus else None
         rehearsal_check = rehearsal_verify(torch, dist, world, rank, streams, rec, f_mine, pcm, gather_pcm, gathered,
@@ -531,27 +595,28 @@ def main() -> int:
     else:
         rehearsal_check = None
     ts = eng.timing_stats()
-    # the spectrum kernel alone (no SSB sharing the chip), a few launches after the timed region: its
-    # isolated HBM rate, reported beside the timed-region one
-    eng.set_pipelining(False)
-    for k in range(5 + ISO_LAUNCHES):  # 5 untimed launches, then ISO_LAUNCHES timed ones
-        if k == 5:
-            eng.synchronize()
-            eng.reset_timing_stats()
-        eng.process_device(iqs[k % N_INPUTS].data_ptr(), fmt, sdrg.STAGE_SPECTRUM, spec.data_ptr(), None, None, now[0])
-    eng.synchronize()
-    spec_iso_ms = eng.timing_stats()["spectrum_ms"]
-    ssb_iso_ms = None
-    if args.stages == "all":  # the SSB stage alone (nothing else on the chip), for its latency-floor fraction
-        for k in range(5 + SSB_ISO_CALLS):  # 5 untimed calls, then SSB_ISO_CALLS timed ones
+    spec_iso_ms = ssb_iso_ms = d2d = stream_gbs = None
+    if args.full:
+        # the spectrum kernel alone (no SSB sharing the chip), a few launches after the timed region: its
+        # isolated HBM rate, reported beside the timed-region one
+        eng.set_pipelining(False)
+        for k in range(5 + ISO_LAUNCHES):  # 5 untimed launches, then ISO_LAUNCHES timed ones
             if k == 5:
                 eng.synchronize()
                 eng.reset_timing_stats()
-            eng.process_device(iqs[k % N_INPUTS].data_ptr(), fmt, sdrg.STAGE_SSB, None, None, pcm.data_ptr(), now[0])
+            eng.process_device(iqs[k % N_INPUTS].data_ptr(), fmt, sdrg.STAGE_SPECTRUM, spec.data_ptr(), None, None, now[0])
         eng.synchronize()
-        ssb_iso_ms = eng.timing_stats()["ssb_ms"]
-    d2d = d2d_copy_gbs(torch, dev)
-    stream_gbs = sdrg.measure_hbm_copy(local, 1 << 30, 10)  # the library's float4 streaming copy (roofline basis)
+        spec_iso_ms = eng.timing_stats()["spectrum_ms"]
+        if args.stages == "all":  # the SSB stage alone (nothing else on the chip), for its latency-floor fraction
+            for k in range(5 + SSB_ISO_CALLS):  # 5 untimed calls, then SSB_ISO_CALLS timed ones
+                if k == 5:
+                    eng.synchronize()
+                    eng.reset_timing_stats()
+                eng.process_device(iqs[k % N_INPUTS].data_ptr(), fmt, sdrg.STAGE_SSB, None, None, pcm.data_ptr(), now[0])
+            eng.synchronize()
+            ssb_iso_ms = eng.timing_stats()["ssb_ms"]
+        d2d = d2d_copy_gbs(torch, dev)
+        stream_gbs = sdrg.measure_hbm_copy(local, 1 << 30, 10)  # the library's float4 streaming copy (roofline basis)
 
     def labelled_rate(st, k_steps, variant_on=False, mode=None):
         """A separately labelled line measured in this same run: k_steps pipelined steps of stages st with profiling
@@ -633,7 +698,8 @@ def main() -> int:
 
     labelled = {}
     k_lab = max(args.steps, LABELLED_MIN_STEPS)
-    if not dist_on and args.config == "c3" and args.stages == "all" and not variant and not args.no_labelled:
+    if (args.full and not dist_on and args.config == "c3" and args.stages == "all" and not variant
+            and not args.no_labelled):
         eng.set_profiling(False)
         # FFT + statistics alone: the statistics after the spectrum on one stream (--stats-async auto) unless forced
         c1_mode = pipelined | (sdrg.PIPELINE_STATS_ASYNC if async_ok and args.stats_async == "1" else 0)
@@ -676,7 +742,6 @@ def main() -> int:
         "c5": (f"C5 (BASELINE configs[4]): {streams} streams x {n}-pt CS16 frames @2 Msps per GPU; four-step FFT + "
                f"|X|^2 + fftshift + signal-strength stats over a {focus_khz} kHz focus; no SSB"),
     }[args.config]
-    achieved_iso = alg_bytes / (spec_iso_ms * 1e-3) / 1e9 if spec_iso_ms > 0 else 0.0
     # whole-step algorithmic bytes: IQ in + spectra out + 72-B records + PCM out (~6.05 B/sample CS8)
     in_bps = 4.0 if c5 else 2.0
     step_bytes = streams * n * (in_bps + 4.0) + streams * (sdrg.RECORD_DTYPE.itemsize + 2 * plen * (args.stages == "all"))
@@ -714,17 +779,6 @@ def main() -> int:
                      "measured": ("HIP events on the kernel's stream over the timed region"
                                   + (", where each step's SSB pipeline shares the chip with the next step's spectrum"
                                      if pipelined else ""))},
-        "roofline_isolated": {"kernel": kname, "bound": "hbm", "achieved": round(achieved_iso, 1),
-                              "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved_iso / HBM_PEAK_GBS, 4),
-                              "measured": f"{ISO_LAUNCHES} launches of the spectrum stage alone after the timed region"},
-        "hbm_measured": {"stream_copy_GBs": round(stream_gbs, 1),
-                         "d2d_copy_GBs": round(d2d, 1),
-                         "note": "stream_copy: the library's float4 streaming copy of 1 GiB (sdrg_measure_hbm_copy: "
-                                 "nontemporal loads/stores, 16 workgroups per CU), read + write bytes per second, the "
-                                 "achievable rate the fractions below are priced against (MI355X_MICROARCH.md: 6.29 TB/s); "
-                                 "d2d_copy: a hipMemcpy D2D of 1 GiB, for comparison (the copy path is slower)",
-                         "frac_timed": round(achieved / stream_gbs, 4) if stream_gbs else None,
-                         "frac_isolated": round(achieved_iso / stream_gbs, 4) if stream_gbs else None},
         "roofline_step": {"bound": "hbm", "achieved": round(step_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": round(step_gbs / HBM_PEAK_GBS, 4),
                           "bytes_per_sample": round(step_bytes / (streams * n), 4),
@@ -737,6 +791,19 @@ def main() -> int:
         "inputs": f"{N_INPUTS} distinct {streams}x{n} {fmt_name} batches ({N_INPUTS * streams * n * in_bps / 2**20:.0f} "
                   "MiB) rotated per step in every leg, so inputs are not served from the 256 MiB Infinity Cache",
     }
+    if args.full:  # the legs that ran on their own after the timed region
+        achieved_iso = alg_bytes / (spec_iso_ms * 1e-3) / 1e9 if spec_iso_ms > 0 else 0.0
+        out["roofline_isolated"] = {"kernel": kname, "bound": "hbm", "achieved": round(achieved_iso, 1),
+                                   "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved_iso / HBM_PEAK_GBS, 4),
+                                   "measured": f"{ISO_LAUNCHES} launches of the spectrum stage alone after the timed region"}
+        out["hbm_measured"] = {"stream_copy_GBs": round(stream_gbs, 1),
+                              "d2d_copy_GBs": round(d2d, 1),
+                              "note": "stream_copy: the library's float4 streaming copy of 1 GiB (sdrg_measure_hbm_copy: "
+                                      "nontemporal loads/stores, 16 workgroups per CU), read + write bytes per second, the "
+                                      "achievable rate the fractions below are priced against (6.29 TB/s is published for this chip); "
+                                      "d2d_copy: a hipMemcpy D2D of 1 GiB, for comparison (the copy path is slower)",
+                              "frac_timed": round(achieved / stream_gbs, 4) if stream_gbs else None,
+                              "frac_isolated": round(achieved_iso / stream_gbs, 4) if stream_gbs else None}
     if args.stages == "all":
         # the step cannot beat its slowest bound: the SSB chain's serial floor (one frame's recurrences) or the HBM
         # time of its algorithmic bytes; as a fraction of HBM peak that ceiling is what ">= 60 % of HBM" can reach
@@ -810,7 +877,7 @@ def main() -> int:
         out["labelled"] = labelled
     if rehearse:
         out["rehearsal"] = "gloo, every rank on cuda:0: a functional check of the N > 1 path, not a measurement"
-    if dist_on:
+    if args.full and dist_on:
         out["rehearsal_check" if rehearse else "gather_check"] = rehearsal_check
     if variant:
         out["ssb_variant"] = {"nco_hz": NCO_HZ, "fir_taps": 127, "note": "not the reference's chain; no CPU baseline"}
@@ -818,7 +885,7 @@ def main() -> int:
         out["labelled_config"] = args.config
     elif args.stages != "all":
         out["ablation_stages"] = args.stages
-    if (rank == 0 and not dist_on and not args.no_cpu_baseline and args.stages == "all" and not variant
+    if (args.full and rank == 0 and not dist_on and not args.no_cpu_baseline and args.stages == "all" and not variant
             and args.config == "c3"):
         try:
             out["cpu_baseline"] = cpu_baseline(args.cpu_threads or host_cores()[0])

@@ -29,6 +29,14 @@ def test_launch_command_for_rehearsal():
     assert cmd[i + 1:] == ["--gpus", "2", "--rehearse-gloo", "--steps", "3", "--launch-dry-run"]
 
 
+def test_full_and_dump_outputs_reach_every_rank():
+    extra = ["--gpus", "2", "--rehearse-gloo", "--full", "--dump-outputs", "some/dir", "--launch-dry-run"]
+    r = run(extra)
+    assert r.returncode == 0, r.stderr
+    cmd = json.loads(r.stdout.strip().splitlines()[-1])["launch"]
+    assert cmd[cmd.index(BENCH) + 1:] == extra
+
+
 def test_too_few_devices_fails_before_launch():
     r = run(["--gpus", "2", "--launch-dry-run"], {"HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": ""})
     assert r.returncode == 3 and "GPU(s) visible" in r.stderr, (r.returncode, r.stderr)

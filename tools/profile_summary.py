@@ -1,6 +1,6 @@
 """Summarise tools/profile_round.sh output into profiles/ (committed evidence for the bench line).
 
-    python tools/profile_summary.py TAG
+    [PROFILE_OUT=DIR] python tools/profile_summary.py TAG     (DIR: where profile_round.sh wrote, default profile_out)
 
 Writes profiles/TAG_kernel_stats.csv (rocprofv3 --stats, as produced), profiles/TAG_bench.json (the bench
 line), profiles/TAG_hbm_pmc.json (FETCH_SIZE / WRITE_SIZE per launch of each engine kernel, with the
@@ -17,6 +17,7 @@ from collections import defaultdict
 
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r1"
 OUT = "profiles"
+RAW = os.environ.get("PROFILE_OUT", "profile_out")
 os.makedirs(OUT, exist_ok=True)
 ENGINE = ("spectrum16k_kernel", "spectrum_kernel", "stats_narrow_kernel", "stats_wide_multi_kernel", "stats_wide_kernel", "stats_kernel", "ssb_pipe_kernel", "four_step_a", "four_step_b", "ssb_chain_kernel",
           "ssb_fir_kernel", "ssb_eq_kernel", "spectral_pulse_kernel", "audio_pulse_kernel", "audio_front_kernel",
@@ -39,11 +40,11 @@ def counters(path: str, counter: str):
     return per
 
 
-stats_csv = glob.glob(f"gpurun_out/prof_{TAG}/**/*kernel_stats.csv", recursive=True)
+stats_csv = glob.glob(f"{RAW}/prof_{TAG}/**/*kernel_stats.csv", recursive=True)
 lines = [f"# Round profile {TAG}", ""]
 if stats_csv:
     shutil.copy(stats_csv[0], f"{OUT}/{TAG}_kernel_stats.csv")
-    lines += ["## rocprofv3 --kernel-trace --stats (bench.py --steps 40 --warmup 50 --no-cpu-baseline, defaults)", "",
+    lines += ["## rocprofv3 --kernel-trace --stats (bench.py --steps 40 --warmup 50 --full --no-cpu-baseline, defaults)", "",
               "| kernel | calls | avg us | min us | max us | % |", "|---|---|---|---|---|---|"]
     for r in csv.DictReader(open(stats_csv[0])):
         lines.append(f"| {short(r['Name'])} | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | "
@@ -51,7 +52,7 @@ if stats_csv:
 # per-launch durations of the roofline kernel from the trace, split by whether the launch overlapped an SSB
 # pipeline launch (the pipelined schedule: co-resident) or ran with no SSB work on the chip (the isolated leg
 # and the FFT + statistics labelled leg)
-trace_csv = glob.glob(f"gpurun_out/prof_{TAG}/**/*kernel_trace.csv", recursive=True)
+trace_csv = glob.glob(f"{RAW}/prof_{TAG}/**/*kernel_trace.csv", recursive=True)
 if trace_csv:
     allr = list(csv.DictReader(open(trace_csv[0])))
     iv = lambda r: (int(r["Start_Timestamp"]), int(r["End_Timestamp"]))
@@ -79,7 +80,7 @@ if trace_csv:
             cad.append((b0 - a0) / 1e6)
     dur = [(e - s) / 1e6 for s, e in ssb_s]
     prof_line = None
-    plog = f"gpurun_out/prof_bench_{TAG}.log"
+    plog = f"{RAW}/prof_bench_{TAG}.log"
     if os.path.exists(plog):
         for ln in open(plog):
             if ln.startswith("{"):
@@ -95,7 +96,7 @@ if trace_csv:
             lines.append(f"* the profiled run's own bench line: ssb_ms_coresident {b:.4f} ms, ms_per_step "
                          f"{prof_line['ms_per_step']:.4f} ({100 * (b / med - 1):+.1f} % against the trace)")
 bench = None
-blog = f"gpurun_out/bench_{TAG}.log"
+blog = f"{RAW}/bench_{TAG}.log"
 if os.path.exists(blog):
     for ln in open(blog):
         if ln.startswith("{"):
@@ -103,8 +104,8 @@ if os.path.exists(blog):
     if bench:
         json.dump(bench, open(f"{OUT}/{TAG}_bench.json", "w"), indent=1)
         lines += ["", "## bench.py line", "", "```", json.dumps(bench), "```"]
-fetch = counters(f"gpurun_out/pmcf_{TAG}", "FETCH_SIZE")
-write = counters(f"gpurun_out/pmcw_{TAG}", "WRITE_SIZE")
+fetch = counters(f"{RAW}/pmcf_{TAG}", "FETCH_SIZE")
+write = counters(f"{RAW}/pmcw_{TAG}", "WRITE_SIZE")
 pmc = {}
 for k in sorted(set(fetch) | set(write)):
     if k not in ENGINE:
@@ -117,7 +118,7 @@ for k in sorted(set(fetch) | set(write)):
               "fetch_bytes_corrected": 2 * f_med if f_med is not None else None,
               "traffic_bytes": (2 * f_med + w_med) if (f_med is not None and w_med is not None) else None}
 if pmc:
-    json.dump({"tag": TAG, "command": "bench.py --steps 5 --warmup 1 --no-cpu-baseline (all stages)",
+    json.dump({"tag": TAG, "command": "bench.py --steps 5 --warmup 1 --full --no-cpu-baseline (all stages)",
                "correction": "FETCH_SIZE x2 (gfx950 wide coalesced reads), KiB -> bytes", "kernels": pmc},
               open(f"{OUT}/{TAG}_hbm_pmc.json", "w"), indent=1)
     lines += ["", "## HBM traffic per launch (median; FETCH_SIZE doubled per MI355X_MICROARCH.md)", "",
