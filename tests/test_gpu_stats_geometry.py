@@ -1,8 +1,12 @@
-"""evaluateSignalStrength (fft_process.cpp:122-379) on the GPU across window geometries: every statistics kernel
-variant the host picks from the geometry (csrc/stats.hip: the narrow one-wave-per-frame kernel with its pooled
-bins in 8 or 24 registers per lane or visited in LDS, and the wide 256-thread kernel once the windows exceed the
-narrow kernel's staging budget; a rocprofv3 trace of this file shows all four launched) against the oracle restatement on the SAME GPU spectrum: every field bit-exact (dB through the
-glibc log10f restatement, csrc/glibc_logf.h), as in tests/test_gpu_parity.py.  The grid spans
+"""evaluateSignalStrength (fft_process.cpp:122-379) on the GPU across window geometries, end to end from raw samples:
+the narrow one-wave-per-frame kernel with its pooled bins in 8 or 24 registers per lane or visited in LDS, the wide
+256-thread kernel with several bottom windows and the multi-frame wide kernel with dB sums (csrc/stats.hip) against
+the oracle restatement on the SAME GPU spectrum: every field bit-exact (dB through the glibc log10f restatement,
+csrc/glibc_logf.h), as in tests/test_gpu_parity.py.  This grid was chosen by hand and does NOT reach every variant
+the launcher picks: stats_wide_multi_kernel<false> and the single-frame wide kernel with one bottom window never run
+here.  tests/stats_cases.py classifies geometries by the launcher's arithmetic, tests/test_gpu_stats_variants.py runs
+a case for every variant, and tests/test_stats_cases.py names the geometries of this grid it counts on
+(COVERED_ELSEWHERE).  The grid spans
 frame sizes, sample rates and focus widths from 1 kHz to 200 kHz, including geometries where fewer than two
 reference windows fit (the stale-output branch, :218-225)."""
 import numpy as np

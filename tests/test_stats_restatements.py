@@ -10,6 +10,7 @@ and multi-frame sequences through the tracking latch and the detection ring."""
 import numpy as np
 import pytest
 
+import stats_cases
 import stats_np
 
 INTS = ["detection_flag", "peak_bin", "valid", "n_ref_windows", "tracking_frequency"]
@@ -43,6 +44,9 @@ def spectrum(rng, n, kind):
 CASES = [(4096, 2_000_000, 5), (16384, 2_000_000, 5), (2048, 2_500_000, 5), (1536, 2_000_000, 5),
          (4099, 2_048_000, 3), (65536, 2_000_000, 200), (65536, 2_000_000, 5), (1000, 2_000_000, 50),
          (16384, 2_000_000, 400), (8192, 2_400_000, 10), (12288, 3_200_000, 7), (256, 2_000_000, 5)]
+# the geometries of the GPU variant test (tests/stats_cases.py) up to 65536 bins: thresholds of the launcher, odd
+# window counts, an empty focus; tests/test_stats_cases.py runs the larger ones on that test's own spectra
+CASES += [row[:3] for row in stats_cases.CASES if row[0] <= 65536 and row[:3] not in CASES]
 KINDS = ["noise", "tone", "const", "steps", "quantised", "tiny"]
 
 
