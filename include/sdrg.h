@@ -468,6 +468,57 @@ int32_t sdrg_engine_process_host(sdrg_engine *eng, const void *iq, int32_t forma
 /* Host copies of the last call's pulse outputs ([n_streams] each; either may be NULL); synchronises. */
 int32_t sdrg_engine_get_pulse_outputs(sdrg_engine *eng, sdrg_pulse_output *spectral, sdrg_pulse_output *audio);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the display stage.  Per stream and frame, a span [lo, lo + nb) of the
+ * fftshifted power spectrum (one row of N floats per stream, as sdrg_engine_process_device writes it) is reduced
+ * to `width` columns, converted to dB and written as float dB or as 8-bit codes: the spectrum or waterfall row a
+ * screen shows (16384 bins -> 1024 U8 columns: 1 KiB per frame instead of 64 KiB).
+ *   span     FULL: lo = 0, nb = N.  FOCUS: sdrg_focus_window of the statistics' configuration in force (what
+ *            sdrg_engine_gather_focus packs; clamped to the band when the focus is wider than it).  BINS: first_bin,
+ *            n_bins.  Resolved at each display call (N and the focus may change between calls): an empty focus
+ *            window (a 0 kHz focus), or lo + nb > N, fails that call with SDRG_E_INVALID and enqueues nothing.
+ *   columns  column c of [0, width) covers the bins lo + j0 .. lo + j1 - 1, j0 = floor(c nb / width),
+ *            j1 = floor((c + 1) nb / width) in 64-bit integers, and the one bin lo + j0 when that range is empty
+ *            (width > nb: nearest-bin repetition).  width in [1, 2^20]; width = nb is the whole log-magnitude spectrum.
+ *   value    MAX: the largest power of the column.  MEAN: (float)(S / (double)count), S the column's powers summed
+ *            in double (in any order).  Defined for finite powers >= 0 and +inf.
+ *   dB       d = 10.0f * log10f(v + 1e-20f) (fft_process.h:74-75 with refPower 1; glibc's log10f bit for bit).
+ *   format   DB_F32: d, [n_streams][width] float.  U8: [n_streams][width] bytes, rows dense (stride width bytes):
+ *            scale = 255.0f / (db_max - db_min); t = (d - db_min) * scale (two float operations); 255 if t >= 255,
+ *            0 if t <= 0 or NaN, else (int)(t + 0.5f).
+ * ---------------------------------------------------------------------------------------------- */
+enum { SDRG_DISPLAY_SPAN_FULL = 0, SDRG_DISPLAY_SPAN_FOCUS = 1, SDRG_DISPLAY_SPAN_BINS = 2 };
+enum { SDRG_DISPLAY_MAX = 0, SDRG_DISPLAY_MEAN = 1 };
+enum { SDRG_DISPLAY_DB_F32 = 0, SDRG_DISPLAY_U8 = 1 };
+typedef struct sdrg_display_config {
+    int32_t span, first_bin, n_bins;   /* first_bin / n_bins: SPAN_BINS only */
+    int32_t width, reduce, format;
+    float db_min, db_max;              /* U8 only: finite, db_max > db_min */
+} sdrg_display_config;
+
+/* Host-only, no device: the bins [*first, *first + *count) of the span (span-relative) that column `column` of
+ * `width` covers for a span of n_bins bins (n_bins and width in [1, 2^20], column in [0, width)). */
+int32_t sdrg_display_column_range(int32_t n_bins, int32_t width, int32_t column, int32_t *first, int32_t *count);
+/* Host-only: the U8 code of a dB value (db_min, db_max finite, db_max > db_min). */
+int32_t sdrg_display_code(float db, float db_min, float db_max, uint8_t *code);
+
+/* Set the configuration every later display call uses.  Checks what does not depend on N (known enum values, width
+ * in [1, 2^20], BINS: first_bin >= 0 and n_bins >= 1, U8: the dB range); a rejected call leaves the previous
+ * configuration in force.  A display call before any set_display returns SDRG_E_INVALID. */
+int32_t sdrg_engine_set_display(sdrg_engine *eng, const sdrg_display_config *cfg);
+int32_t sdrg_engine_get_display(const sdrg_engine *eng, sdrg_display_config *out);
+/* The span and the bytes per output row the next display call would use (host-only; any pointer may be NULL). */
+int32_t sdrg_engine_display_geometry(const sdrg_engine *eng, int32_t *first_bin, int32_t *n_bins, int32_t *row_bytes);
+/* spectra [n_streams][samples_per_reading] float and out [n_streams][row_bytes] in device memory.  Runs on the main
+ * stream (the caller's after sdrg_engine_set_stream): issued right after sdrg_engine_process_device it reads that
+ * call's spectra without a host synchronisation, in every pipelining mode.  Complete after sdrg_engine_synchronize,
+ * or on a stream after sdrg_engine_wait_outputs. */
+int32_t sdrg_engine_display_device(sdrg_engine *eng, const float *spectra, void *out);
+/* Host buffers, synchronous.  spectra == NULL: the spectra the last sdrg_engine_process_host call with
+ * SDRG_STAGE_SPECTRUM left on the device (SDRG_E_INVALID without such a call, or when samples_per_reading has changed
+ * since), so process_host(spectra = NULL, ...) + display_host(NULL, rows) copies back only the display rows. */
+int32_t sdrg_engine_display_host(sdrg_engine *eng, const float *spectra, void *out);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

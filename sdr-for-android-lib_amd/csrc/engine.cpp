@@ -269,6 +269,16 @@ struct sdrg_engine {
     int upper = 1;
     bool has_cbs = false;
     sdrg_callbacks cbs{};
+    // display stage (sdrg_engine_set_display / display_device / display_host; display.hip)
+    sdrg_display_config disp{};
+    bool disp_set = false;
+    float *d_disp_in = nullptr;   // display_host's copy of the caller's spectra (d_spec_stage keeps the odd-N bin N-1)
+    size_t disp_in_elems = 0;
+    unsigned char *d_disp_out = nullptr;  // display_host's rows
+    size_t disp_out_bytes = 0;
+    int host_spec_n = 0;          // N of the spectra the last process_host call with SPECTRUM left in d_spec_stage
+    hipEvent_t ev_display = nullptr;  // recorded by wait_outputs after a display call the waiting stream must follow
+    bool display_unmarked = false;    // a display kernel was enqueued on s_main after the last marker
 };
 
 namespace {
@@ -1018,7 +1028,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     e->spec_bank.detect_stream = e->audio_bank.detect_stream = nullptr;
     void *bufs[] = {e->d_stats, e->d_ssb, e->d_twiddles, e->d_taps, e->d_nco_tab, e->d_chunk_table, e->d_ssb_scratch,
                     e->d_spec_scratch, e->d_fft_scratch, e->d_pool, e->d_rec_scratch, e->d_iq_stage, e->d_spec_stage,
-                    e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage};
+                    e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->d_disp_in, e->d_disp_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
@@ -1026,7 +1036,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
         if (ev) (void)hipEventDestroy(ev);
     if (e->s_gather) (void)hipStreamSynchronize(e->s_gather);
     hipEvent_t evs[] = {e->ev_fork, e->ev_join, e->ev_in_main, e->ev_in_ssb, e->ev_fork_spec, e->ev_join_spec,
-                        e->ev_spec_done, e->ev_ap_end[0], e->ev_ap_end[1], e->ev_ap_end[2]};
+                        e->ev_spec_done, e->ev_ap_end[0], e->ev_ap_end[1], e->ev_ap_end[2], e->ev_display};
     for (hipEvent_t ev : evs)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ev_g)  // ev_gather is one of these
@@ -1117,6 +1127,15 @@ int32_t sdrg_engine_wait_outputs(sdrg_engine *e, void *hip_stream) {
     if (e->last_ap_end) HIP_TRY(hipStreamWaitEvent(s, e->last_ap_end, 0));                    // audio pulse
     if (e->stats_async && e->last_stats_end) HIP_TRY(hipStreamWaitEvent(s, e->last_stats_end, 0));  // records
     if (e->ev_gather) HIP_TRY(hipStreamWaitEvent(s, e->ev_gather, 0));  // the gathered outputs on the root
+    if (s != e->s_main) {  // display rows: enqueued on the main stream after the call's own end marker
+        if (e->display_unmarked) {
+            if (!e->ev_display)
+                HIP_TRY(hipEventCreateWithFlags(&e->ev_display, hipEventDisableTiming | hipEventDisableSystemFence));
+            HIP_TRY(hipEventRecord(e->ev_display, e->s_main));
+            e->display_unmarked = false;
+        }
+        if (e->ev_display) HIP_TRY(hipStreamWaitEvent(s, e->ev_display, 0));
+    }
     return SDRG_OK;
 }
 
@@ -1375,6 +1394,7 @@ int32_t sdrg_engine_process_host(sdrg_engine *e, const void *iq, int32_t format,
     const bool do_spec = stages & SDRG_STAGE_SPECTRUM, do_stats = stages & SDRG_STAGE_STATS,
                do_ssb = stages & SDRG_STAGE_SSB;
     if (do_spec) {
+        e->host_spec_n = 0;  // until this call's spectra are enqueued
         int32_t rc = ensure_device(&e->d_spec_stage, &e->spec_stage_elems, (size_t)B * n, true);  // see enqueue
         if (rc) return rc;
     }
@@ -1391,6 +1411,7 @@ int32_t sdrg_engine_process_host(sdrg_engine *e, const void *iq, int32_t format,
     int32_t rc = enqueue(e, e->d_iq_stage, format, stages, do_spec ? e->d_spec_stage : nullptr,
                          do_stats ? e->d_rec_stage : nullptr, do_ssb ? e->d_pcm_stage : nullptr, now_ms, true);
     if (rc) return rc;
+    if (do_spec) e->host_spec_n = n;  // sdrg_engine_display_host(spectra = NULL) reads these spectra
     float *h_spec = spectra;
     sdrg_frame_record *h_rec = records;
     int16_t *h_pcm = pcm;
@@ -1428,6 +1449,144 @@ int32_t sdrg_engine_process_host(sdrg_engine *e, const void *iq, int32_t format,
         if (do_ssb && h_pcm != e->h_pcm.data() && pcm_len > 0) e->h_pcm.assign(h_pcm, h_pcm + (size_t)B * pcm_len);
         dispatch_callbacks(e, stages, pcm_len);
     }
+    return SDRG_OK;
+}
+
+// ---- display stage (display.hip) ----------------------------------------------------------------------------------
+
+int32_t sdrg_display_column_range(int32_t n_bins, int32_t width, int32_t column, int32_t *first, int32_t *count) {
+    if (!first || !count) return fail(SDRG_E_INVALID, "null output");
+    if (n_bins < 1 || n_bins > (1 << 20) || width < 1 || width > (1 << 20) || column < 0 || column >= width)
+        return fail(SDRG_E_INVALID, "n_bins %d / width %d outside [1, 2^20] or column %d outside [0, width)", n_bins,
+                    width, column);
+    const int64_t j0 = (int64_t)column * n_bins / width, j1 = ((int64_t)column + 1) * n_bins / width;
+    *first = (int32_t)j0;
+    *count = j1 > j0 ? (int32_t)(j1 - j0) : 1;  // width > n_bins: the nearest bin, repeated
+    return SDRG_OK;
+}
+
+static bool display_db_range_ok(float db_min, float db_max) {
+    return std::isfinite(db_min) && std::isfinite(db_max) && db_max > db_min;
+}
+
+int32_t sdrg_display_code(float db, float db_min, float db_max, uint8_t *code) {
+    if (!code) return fail(SDRG_E_INVALID, "null output");
+    if (!display_db_range_ok(db_min, db_max)) return fail(SDRG_E_INVALID, "db_min / db_max must be finite, db_max > db_min");
+    const float scale = 255.0f / (db_max - db_min);
+    const float t = (db - db_min) * scale;  // two float operations (this file is built without contraction)
+    *code = t >= 255.0f ? 255 : !(t > 0.0f) ? 0 : (uint8_t)(int)(t + 0.5f);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_display(sdrg_engine *e, const sdrg_display_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!cfg) return fail(SDRG_E_INVALID, "null display config");
+    if (cfg->span != SDRG_DISPLAY_SPAN_FULL && cfg->span != SDRG_DISPLAY_SPAN_FOCUS && cfg->span != SDRG_DISPLAY_SPAN_BINS)
+        return fail(SDRG_E_INVALID, "unknown display span %d", cfg->span);
+    if (cfg->reduce != SDRG_DISPLAY_MAX && cfg->reduce != SDRG_DISPLAY_MEAN)
+        return fail(SDRG_E_INVALID, "unknown display reduction %d", cfg->reduce);
+    if (cfg->format != SDRG_DISPLAY_DB_F32 && cfg->format != SDRG_DISPLAY_U8)
+        return fail(SDRG_E_INVALID, "unknown display format %d", cfg->format);
+    if (cfg->width < 1 || cfg->width > (1 << 20)) return fail(SDRG_E_INVALID, "display width %d outside [1, 2^20]", cfg->width);
+    if (cfg->span == SDRG_DISPLAY_SPAN_BINS && (cfg->first_bin < 0 || cfg->n_bins < 1))
+        return fail(SDRG_E_INVALID, "display span: first_bin %d must be >= 0 and n_bins %d >= 1", cfg->first_bin, cfg->n_bins);
+    if (cfg->format == SDRG_DISPLAY_U8 && !display_db_range_ok(cfg->db_min, cfg->db_max))
+        return fail(SDRG_E_INVALID, "display db_min / db_max must be finite, db_max > db_min");
+    e->disp = *cfg;
+    e->disp_set = true;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_display(const sdrg_engine *e, sdrg_display_config *out) {
+    if (!e || !out) return fail(SDRG_E_INVALID, "null argument");
+    if (!e->disp_set) return fail(SDRG_E_INVALID, "no display configuration set");
+    *out = e->disp;
+    return SDRG_OK;
+}
+
+// the configuration in force resolved against the current N and focus window
+static int32_t display_params(const sdrg_engine *e, DisplayParams *p) {
+    if (!e->disp_set) return fail(SDRG_E_INVALID, "no display configuration set (sdrg_engine_set_display)");
+    const sdrg_display_config &c = e->disp;
+    const int n = e->cfg.samples_per_reading;
+    int64_t lo = 0, nb = n;
+    if (c.span == SDRG_DISPLAY_SPAN_FOCUS) {
+        if (e->fft_fs == 0) return fail(SDRG_E_INVALID, "the statistics' sample rate is 0");
+        const StatsGeometry geo = stats_geometry(e->fft_fs, e->fft_fc, n, e->fft_focus);
+        if (geo.focus_len <= 0) return fail(SDRG_E_INVALID, "the focus window is empty (focus range %d kHz)", e->fft_focus);
+        lo = geo.focus_lo;
+        nb = geo.focus_len;
+    } else if (c.span == SDRG_DISPLAY_SPAN_BINS) {
+        lo = c.first_bin;
+        nb = c.n_bins;
+    }
+    if (lo < 0 || nb < 1 || lo + nb > n)
+        return fail(SDRG_E_INVALID, "display span [%lld, %lld) outside the %d bins of a frame", (long long)lo,
+                    (long long)(lo + nb), n);
+    *p = DisplayParams{n, (int)lo, (int)nb, c.width, c.reduce, c.format, 0.0f, 0.0f};
+    if (c.format == SDRG_DISPLAY_U8) {
+        p->db_min = c.db_min;
+        p->scale = 255.0f / (c.db_max - c.db_min);
+    }
+    return SDRG_OK;
+}
+
+static size_t display_row_bytes(const DisplayParams &p) {
+    return (size_t)p.width * (p.format == SDRG_DISPLAY_U8 ? 1 : sizeof(float));
+}
+
+int32_t sdrg_engine_display_geometry(const sdrg_engine *e, int32_t *first_bin, int32_t *n_bins, int32_t *row_bytes) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    DisplayParams p;
+    int32_t rc = display_params(e, &p);
+    if (rc) return rc;
+    if (first_bin) *first_bin = p.lo;
+    if (n_bins) *n_bins = p.nb;
+    if (row_bytes) *row_bytes = (int32_t)display_row_bytes(p);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_display_device(sdrg_engine *e, const float *spectra, void *out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!spectra || !out) return fail(SDRG_E_INVALID, "null spectra or out");
+    DisplayParams p;
+    int32_t rc = display_params(e, &p);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    HIP_TRY(launch_display(spectra, e->n_streams, p, out, e->s_main));
+    e->display_unmarked = true;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_display_host(sdrg_engine *e, const float *spectra, void *out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!out) return fail(SDRG_E_INVALID, "null out");
+    DisplayParams p;
+    int32_t rc = display_params(e, &p);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const size_t B = (size_t)e->n_streams, out_bytes = B * display_row_bytes(p);
+    const float *src = e->d_spec_stage;
+    if (spectra) {
+        // a staging buffer of its own, as sdrg_engine_signal_strength_host: d_spec_stage carries the odd-N bin N-1
+        rc = ensure_device(&e->d_disp_in, &e->disp_in_elems, B * (size_t)p.n);
+        if (rc) return rc;
+        src = e->d_disp_in;
+    } else if (!e->d_spec_stage || e->host_spec_n == 0) {
+        return fail(SDRG_E_INVALID, "no spectra on the device: no sdrg_engine_process_host call with SDRG_STAGE_SPECTRUM yet");
+    } else if (e->host_spec_n != p.n) {
+        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the spectra on the device were computed",
+                    e->host_spec_n, p.n);
+    }
+    rc = ensure_device(&e->d_disp_out, &e->disp_out_bytes, out_bytes);
+    if (rc) return rc;
+    if (spectra)
+        HIP_TRY(hipMemcpyAsync(e->d_disp_in, spectra, sizeof(float) * B * (size_t)p.n, hipMemcpyHostToDevice, e->s_main));
+    HIP_TRY(launch_display(src, e->n_streams, p, e->d_disp_out, e->s_main));
+    HIP_TRY(hipMemcpyAsync(out, e->d_disp_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
     return SDRG_OK;
 }
 

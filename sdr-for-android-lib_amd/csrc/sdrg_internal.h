@@ -135,4 +135,13 @@ int dist_rank(const sdrg_dist *d);
 hipError_t measure_stream_copy(size_t bytes, int reps, double *gbs);
 hipError_t launch_focus_pack(const float *spectra, int n_streams, int n, int lo, int nb, float *out, hipStream_t stream);
 
+// Display stage (display.hip): rows of n floats, the span [lo, lo + nb) of each reduced to `width` columns
+// (reduce: SDRG_DISPLAY_MAX / _MEAN), 10 log10f(v + 1e-20f), written as float dB or 8-bit codes (format:
+// SDRG_DISPLAY_DB_F32 / _U8, code = (d - db_min) * scale clamped and rounded).  out: [n_streams][width], rows dense.
+struct DisplayParams {
+    int n, lo, nb, width, reduce, format;
+    float db_min, scale;  // U8 only; scale = 255.0f / (db_max - db_min)
+};
+hipError_t launch_display(const float *spectra, int n_streams, const DisplayParams &p, void *out, hipStream_t stream);
+
 }  // namespace sdrg

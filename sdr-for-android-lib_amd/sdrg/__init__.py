@@ -32,6 +32,9 @@ STAGE_SPECTRAL_PULSE, STAGE_AUDIO_PULSE, STAGE_ALL = 8, 16, 31
 PIPELINE_OFF, PIPELINE_ON, PIPELINE_INPUTS_READY = 0, 1, 2  # sdrg_engine_set_pipelining modes
 PIPELINE_STATS_ASYNC = 4  # OR'ed with ON / INPUTS_READY: statistics on a stream of their own
 PULSE_SPECTRAL, PULSE_AUDIO = 0, 1
+DISPLAY_SPAN_FULL, DISPLAY_SPAN_FOCUS, DISPLAY_SPAN_BINS = 0, 1, 2  # sdrg_display_config.span
+DISPLAY_MAX, DISPLAY_MEAN = 0, 1                                    # .reduce
+DISPLAY_DB_F32, DISPLAY_U8 = 0, 1                                   # .format
 STATUS = {0: "SDRG_OK", -1: "SDRG_E_INVALID", -2: "SDRG_E_UNSUPPORTED", -3: "SDRG_E_NOMEM", -4: "SDRG_E_HIP",
           -5: "SDRG_E_NODEVICE"}
 BYTES_PER_SAMPLE = {CF32: 8, CS8: 2, CU8: 2, CS16: 4}
@@ -103,6 +106,8 @@ EXPORTS = [
     "sdrg_engine_gather",
     "sdrg_engine_gather_records", "sdrg_engine_gather_focus", "sdrg_engine_gather_spectra", "sdrg_engine_gather_pcm",
     "sdrg_device_alloc", "sdrg_device_free", "sdrg_memcpy", "sdrg_measure_hbm_copy",
+    "sdrg_display_column_range", "sdrg_display_code", "sdrg_engine_set_display", "sdrg_engine_get_display",
+    "sdrg_engine_display_geometry", "sdrg_engine_display_device", "sdrg_engine_display_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -140,6 +145,13 @@ class PulseConfig(ctypes.Structure):
         for k, v in overrides.items():
             setattr(c, k, v)
         return c
+
+
+class DisplayConfig(ctypes.Structure):
+    """sdrg_display_config: the display stage's span, width, reduction and output format (include/sdrg.h)."""
+    _fields_ = [("span", ctypes.c_int32), ("first_bin", ctypes.c_int32), ("n_bins", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("reduce", ctypes.c_int32), ("format", ctypes.c_int32),
+                ("db_min", ctypes.c_float), ("db_max", ctypes.c_float)]
 
 
 class _Timings(ctypes.Structure):
@@ -296,6 +308,13 @@ def load() -> ctypes.CDLL:
         "sdrg_device_free": (_I32, [_I32, P]),
         "sdrg_memcpy": (_I32, [_I32, P, P, ctypes.c_size_t]),
         "sdrg_measure_hbm_copy": (_I32, [_I32, ctypes.c_size_t, _I32, ctypes.POINTER(ctypes.c_double)]),
+        "sdrg_display_column_range": (_I32, [_I32, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+        "sdrg_display_code": (_I32, [_F, _F, _F, ctypes.POINTER(ctypes.c_uint8)]),
+        "sdrg_engine_set_display": (_I32, [P, ctypes.POINTER(DisplayConfig)]),
+        "sdrg_engine_get_display": (_I32, [P, ctypes.POINTER(DisplayConfig)]),
+        "sdrg_engine_display_geometry": (_I32, [P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+        "sdrg_engine_display_device": (_I32, [P, P, P]),
+        "sdrg_engine_display_host": (_I32, [P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -434,6 +453,21 @@ def focus_window(sample_rate: int, n: int, focus_khz: int) -> tuple[int, int]:
     lo, nb = ctypes.c_int32(), ctypes.c_int32()
     _check(load().sdrg_focus_window(sample_rate, n, focus_khz, ctypes.byref(lo), ctypes.byref(nb)), "focus_window")
     return lo.value, nb.value
+
+
+def display_column_range(n_bins: int, width: int, column: int) -> tuple[int, int]:
+    """(first, count): the span-relative bins column `column` of `width` covers in a span of n_bins (host-side)."""
+    first, count = ctypes.c_int32(), ctypes.c_int32()
+    _check(load().sdrg_display_column_range(n_bins, width, column, ctypes.byref(first), ctypes.byref(count)),
+           "display_column_range")
+    return first.value, count.value
+
+
+def display_code(db: float, db_min: float, db_max: float) -> int:
+    """The display stage's 8-bit code of a dB value (host-side)."""
+    code = ctypes.c_uint8()
+    _check(load().sdrg_display_code(db, db_min, db_max, ctypes.byref(code)), "display_code")
+    return code.value
 
 
 def ssb_design(samp_count: int, sample_rate: int, sound_mode: int = 1) -> dict:
@@ -625,6 +659,50 @@ class Engine:
                                                        recs.ctypes.data_as(ctypes.c_void_p), now_ms),
                "signal_strength_host")
         return recs
+
+    # ---- display stage ----------------------------------------------------------------------------
+    def set_display(self, **fields) -> None:
+        """sdrg_engine_set_display: span, first_bin, n_bins, width, reduce, format, db_min, db_max (fields left out
+        are 0: the full span, MAX, float dB).  A rejected configuration leaves the previous one in force."""
+        c = DisplayConfig()
+        for k, v in fields.items():
+            if k not in dict(DisplayConfig._fields_):
+                raise TypeError(f"unknown display field {k!r}")
+            setattr(c, k, v)
+        _check(load().sdrg_engine_set_display(self._h, ctypes.byref(c)), "set_display")
+
+    def display_config(self) -> dict:
+        c = DisplayConfig()
+        _check(load().sdrg_engine_get_display(self._h, ctypes.byref(c)), "get_display")
+        return {k: getattr(c, k) for k, _ in DisplayConfig._fields_}
+
+    def display_geometry(self) -> tuple[int, int, int]:
+        """(first_bin, n_bins, row_bytes) the next display call would use."""
+        lo, nb, rb = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _check(load().sdrg_engine_display_geometry(self._h, ctypes.byref(lo), ctypes.byref(nb), ctypes.byref(rb)),
+               "display_geometry")
+        return lo.value, nb.value, rb.value
+
+    def display_device(self, spectra_ptr: int, out_ptr: int) -> None:
+        """Device path: spectra [n_streams][N] float32 in, display rows [n_streams][row_bytes] out; asynchronous on the
+        main stream (right after process_device it reads that call's spectra)."""
+        _check(load().sdrg_engine_display_device(self._h, spectra_ptr, out_ptr), "display_device")
+
+    def display(self, spectra: np.ndarray | None = None) -> np.ndarray:
+        """Host path: the display rows [n_streams][width], float32 dB or uint8 codes, of caller spectra
+        ([n_streams][samplesPerReading] float32) or, with None, of the spectra the last process() call with
+        STAGE_SPECTRUM left on the device."""
+        cfg = self.display_config()
+        ptr = None
+        if spectra is not None:
+            n = self.cfg.samplesPerReading
+            spectra = np.ascontiguousarray(spectra, dtype=np.float32)
+            if spectra.shape != (self.n_streams, n):
+                raise SdrgError(f"spectra {spectra.shape}: expected ({self.n_streams}, {n})")
+            ptr = spectra.ctypes.data_as(ctypes.c_void_p)
+        out = np.empty((self.n_streams, cfg["width"]), np.uint8 if cfg["format"] == DISPLAY_U8 else np.float32)
+        _check(load().sdrg_engine_display_host(self._h, ptr, out.ctypes.data_as(ctypes.c_void_p)), "display_host")
+        return out
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
                        pcm_ptr: int | None, now_ms: int = 0) -> None:
