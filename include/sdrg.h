@@ -519,6 +519,66 @@ int32_t sdrg_engine_display_device(sdrg_engine *eng, const float *spectra, void 
  * since), so process_host(spectra = NULL, ...) + display_host(NULL, rows) copies back only the display rows. */
 int32_t sdrg_engine_display_host(sdrg_engine *eng, const float *spectra, void *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the integration stage.  Per stream and bin, the mean or the largest of
+ * the last `period` power spectra, or an exponential moving average: the non-coherent integration that the
+ * reference's FFTProcessor prepares (integrationPeriod = 10 and a ring it fills and never reads) and does not do.
+ * The engine keeps the history in device memory: one configuration and one history per engine, every call feeds one
+ * frame per stream, so all streams advance together.
+ *   in / out  spectra and out are [n_streams][N] float, N the samples_per_reading in force; all N elements of a row
+ *             are plain data (also the element N - 1 the spectrum of an odd N never writes).  out == spectra is
+ *             allowed (in place); any other overlap is undefined.
+ *   t, c      t = 0, 1, ... counts the integrate calls since the last reset, x_t is this call's value of a bin and
+ *             c = min(t + 1, period).
+ *   MEAN      S, a double, is (double)x_i summed for i = t - c + 1 .. t in that order (oldest first), starting from
+ *             the oldest value; out = (float)(S / (double)c).  Recomputed from the history at every call (a running
+ *             sum would keep a residue of every strong frame that ever passed).  period = 1 returns the input's bits.
+ *   MAX       the largest of those c values.
+ *   EMA       t = 0: y = x.  Otherwise d = x - y; y = y + alpha * d (three float operations, no contraction).
+ *             out = y; the engine keeps y.
+ *   domain    MEAN and MAX: finite powers >= +0 and +inf.  EMA: finite powers >= +0.
+ *   period    in [1, 64]; MEAN and MAX only (EMA neither reads nor checks it).
+ *   alpha     finite, in (0, 1]; EMA only (MEAN and MAX neither read nor check it).
+ *   reset     the next call is t = 0 after: every successful sdrg_engine_set_integration, sdrg_engine_integrate_reset,
+ *             sdrg_engine_reset_state, and at an integrate call at which samples_per_reading, sample_rate or
+ *             center_frequency of the configuration in force differ from those at the previous integrate call (the
+ *             bins mean other frequencies; compared on the host, at the call).
+ *   depth     the number of frames the last output integrates: c for MEAN and MAX, t + 1 for EMA, 0 after a reset.
+ * A call that fails (a null pointer, no configuration set, SDRG_E_NOMEM) changes nothing and advances nothing.
+ * ---------------------------------------------------------------------------------------------- */
+enum { SDRG_INTEGRATE_MEAN = 0, SDRG_INTEGRATE_MAX = 1, SDRG_INTEGRATE_EMA = 2 };
+enum { SDRG_INTEGRATE_MAX_PERIOD = 64 };
+typedef struct sdrg_integrate_config {
+    int32_t mode;
+    int32_t period;   /* MEAN, MAX */
+    float alpha;      /* EMA */
+} sdrg_integrate_config;
+
+/* Checks the mode and the field it uses; a rejected call leaves the previous configuration and history in force, an
+ * accepted one resets the history.  An integrate call before any set_integration returns SDRG_E_INVALID. */
+int32_t sdrg_engine_set_integration(sdrg_engine *eng, const sdrg_integrate_config *cfg);
+/* The configuration in force and the depth of the last output; either pointer may be NULL.  SDRG_E_INVALID when
+ * cfg_out is given and no configuration has been set. */
+int32_t sdrg_engine_get_integration(const sdrg_engine *eng, sdrg_integrate_config *cfg_out, int32_t *depth_out);
+int32_t sdrg_engine_integrate_reset(sdrg_engine *eng);
+/* Device buffers.  Runs on the main stream (the caller's after sdrg_engine_set_stream): issued right after
+ * sdrg_engine_process_device it follows that call's spectrum in every pipelining mode, and a following
+ * sdrg_engine_signal_strength_device(out, ...) or sdrg_engine_display_device(out, ...) follows it.  Under
+ * SDRG_PIPELINE_STATS_ASYNC, when out overlaps a spectra buffer whose statistics are still in flight, the kernel
+ * waits (on the GPU) for them: integrating a call's spectra in place never changes what its statistics see.
+ * Complete after sdrg_engine_synchronize, or on a stream after sdrg_engine_wait_outputs.  The ring (period x
+ * n_streams x N floats) or the EMA state (n_streams x N floats) is allocated at the first call that needs it. */
+int32_t sdrg_engine_integrate_device(sdrg_engine *eng, const float *spectra, float *out);
+/* Host buffers, synchronous.  spectra == NULL: the spectra the last sdrg_engine_process_host call with
+ * SDRG_STAGE_SPECTRUM left on the device (the rule and the refusals of sdrg_engine_display_host(NULL)).
+ * out == NULL: the history advances and the integrated rows stay on the device only. */
+int32_t sdrg_engine_integrate_host(sdrg_engine *eng, const float *spectra, float *out);
+/* The display rows (current display configuration, [n_streams][row_bytes]) of the rows the last
+ * sdrg_engine_integrate_host call left on the device; SDRG_E_INVALID when there are none or samples_per_reading has
+ * changed since.  process_host(spectra = NULL) + integrate_host(NULL, NULL) + display_integrated_host(rows) copies
+ * back only the display rows. */
+int32_t sdrg_engine_display_integrated_host(sdrg_engine *eng, void *rows_out);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

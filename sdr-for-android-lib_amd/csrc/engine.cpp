@@ -279,6 +279,23 @@ struct sdrg_engine {
     int host_spec_n = 0;          // N of the spectra the last process_host call with SPECTRUM left in d_spec_stage
     hipEvent_t ev_display = nullptr;  // recorded by wait_outputs after a display call the waiting stream must follow
     bool display_unmarked = false;    // a display kernel was enqueued on s_main after the last marker
+    // integration stage (sdrg_engine_set_integration / integrate_device / integrate_host; integrate.hip)
+    sdrg_integrate_config integ{};
+    bool integ_set = false;
+    int64_t integ_t = 0;       // integrate calls since the last reset
+    int32_t integ_depth = 0;   // frames the last output integrates
+    bool integ_seen = false;   // integ_n / _fs / _fc hold the configuration at the previous integrate call
+    int integ_n = 0;
+    int64_t integ_fs = 0, integ_fc = 0;
+    float *d_integ_ring = nullptr;  // MEAN / MAX: [period][integrate_slot_stride(n_streams * N)]
+    size_t integ_ring_elems = 0;
+    float *d_integ_ema = nullptr;   // EMA: y [n_streams][N]
+    size_t integ_ema_elems = 0;
+    float *d_integ_in = nullptr;    // integrate_host's copy of the caller's spectra
+    size_t integ_in_elems = 0;
+    float *d_integ_out = nullptr;   // integrate_host's rows
+    size_t integ_out_elems = 0;
+    int integ_out_n = 0;            // N of the rows the last integrate_host call left in d_integ_out
 };
 
 namespace {
@@ -1028,7 +1045,8 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     e->spec_bank.detect_stream = e->audio_bank.detect_stream = nullptr;
     void *bufs[] = {e->d_stats, e->d_ssb, e->d_twiddles, e->d_taps, e->d_nco_tab, e->d_chunk_table, e->d_ssb_scratch,
                     e->d_spec_scratch, e->d_fft_scratch, e->d_pool, e->d_rec_scratch, e->d_iq_stage, e->d_spec_stage,
-                    e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->d_disp_in, e->d_disp_out};
+                    e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->d_disp_in, e->d_disp_out,
+                    e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
@@ -1211,6 +1229,8 @@ int32_t sdrg_engine_reset_state(sdrg_engine *e) {
     e->cf_changed_pending = false;
     e->spec_bank.reset_pending = true;
     e->audio_bank.reset_pending = true;
+    e->integ_t = 0;  // the integration history
+    e->integ_depth = 0;
     return SDRG_OK;
 }
 
@@ -1586,6 +1606,156 @@ int32_t sdrg_engine_display_host(sdrg_engine *e, const float *spectra, void *out
         HIP_TRY(hipMemcpyAsync(e->d_disp_in, spectra, sizeof(float) * B * (size_t)p.n, hipMemcpyHostToDevice, e->s_main));
     HIP_TRY(launch_display(src, e->n_streams, p, e->d_disp_out, e->s_main));
     HIP_TRY(hipMemcpyAsync(out, e->d_disp_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
+    return SDRG_OK;
+}
+
+// ---- integration stage (integrate.hip) ----------------------------------------------------------------------------
+
+int32_t sdrg_engine_set_integration(sdrg_engine *e, const sdrg_integrate_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!cfg) return fail(SDRG_E_INVALID, "null integration config");
+    if (cfg->mode == SDRG_INTEGRATE_MEAN || cfg->mode == SDRG_INTEGRATE_MAX) {
+        if (cfg->period < 1 || cfg->period > SDRG_INTEGRATE_MAX_PERIOD)
+            return fail(SDRG_E_INVALID, "integration period %d outside [1, %d]", cfg->period, SDRG_INTEGRATE_MAX_PERIOD);
+    } else if (cfg->mode == SDRG_INTEGRATE_EMA) {
+        if (!(cfg->alpha > 0.0f && cfg->alpha <= 1.0f))  // also NaN
+            return fail(SDRG_E_INVALID, "integration alpha %g outside (0, 1]", (double)cfg->alpha);
+    } else {
+        return fail(SDRG_E_INVALID, "unknown integration mode %d", cfg->mode);
+    }
+    e->integ = *cfg;
+    e->integ_set = true;
+    e->integ_t = 0;
+    e->integ_depth = 0;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_integration(const sdrg_engine *e, sdrg_integrate_config *cfg_out, int32_t *depth_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (cfg_out && !e->integ_set) return fail(SDRG_E_INVALID, "no integration configuration set");
+    if (cfg_out) *cfg_out = e->integ;
+    if (depth_out) *depth_out = e->integ_depth;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_integrate_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->integ_t = 0;
+    e->integ_depth = 0;
+    return SDRG_OK;
+}
+
+// the new buffer first, so a call that cannot have it leaves the old one (and the history in it) as it was
+static int32_t integrate_buffer(float **p, size_t *have, size_t need) {
+    if (*have >= need && *p) return SDRG_OK;
+    float *q = nullptr;
+    const hipError_t er = hipMalloc(reinterpret_cast<void **>(&q), need * sizeof(float));
+    if (er == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return fail(SDRG_E_NOMEM, "hipMalloc of %zu bytes for the integration stage failed", need * sizeof(float));
+    }
+    HIP_TRY(er);
+    if (*p) (void)hipFree(*p);  // synchronises with the kernels that use it
+    *p = q;
+    *have = need;
+    return SDRG_OK;
+}
+
+// one integrate call on the main stream: src, dst device [n_streams][N], dst may be src
+static int32_t integrate_enqueue(sdrg_engine *e, const float *src, float *dst) {
+    const sdrg_integrate_config &c = e->integ;
+    const int n = e->cfg.samples_per_reading;
+    const size_t count = (size_t)e->n_streams * (size_t)n, stride = integrate_slot_stride(count);
+    // a resize or a retune since the previous call: the bins mean other frequencies, the history is forgotten
+    const bool moved = e->integ_seen && (n != e->integ_n || e->cfg.sample_rate != e->integ_fs ||
+                                         e->cfg.center_frequency != e->integ_fc);
+    const int64_t t = moved ? 0 : e->integ_t;
+    IntegrateParams p{c.mode, 1, 0, (int)std::min<int64_t>(t + 1, INT32_MAX), c.alpha};
+    int32_t rc;
+    if (c.mode == SDRG_INTEGRATE_EMA) {
+        rc = integrate_buffer(&e->d_integ_ema, &e->integ_ema_elems, count);
+    } else {
+        p.period = c.period;
+        p.slot = (int)(t % c.period);
+        p.depth = (int)std::min<int64_t>(t + 1, c.period);
+        rc = integrate_buffer(&e->d_integ_ring, &e->integ_ring_elems, (size_t)c.period * stride);
+    }
+    if (rc) return rc;
+    // SDRG_PIPELINE_STATS_ASYNC: statistics of earlier calls may still read their spectra on s_stats; a dst that
+    // overlaps such a buffer (in-place integration of the call's own spectra) is written after them
+    if (e->stats_async)
+        for (int k = 0; k < sdrg_engine::SA_RING; k++)
+            if (e->sa_live[k] && e->sa_spec[k] < dst + count && dst < e->sa_spec[k] + count)
+                HIP_TRY(hipStreamWaitEvent(e->s_main, e->ev_stats_end[k], 0));
+    HIP_TRY(launch_integrate(src, count, p, e->d_integ_ring, stride, e->d_integ_ema, dst, e->s_main));
+    e->integ_t = t + 1;
+    e->integ_depth = p.depth;
+    e->integ_seen = true;
+    e->integ_n = n;
+    e->integ_fs = e->cfg.sample_rate;
+    e->integ_fc = e->cfg.center_frequency;
+    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers dst as it covers display rows
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_integrate_device(sdrg_engine *e, const float *spectra, float *out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!spectra || !out) return fail(SDRG_E_INVALID, "null spectra or out");
+    if (!e->integ_set) return fail(SDRG_E_INVALID, "no integration configuration set (sdrg_engine_set_integration)");
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    return integrate_enqueue(e, spectra, out);
+}
+
+int32_t sdrg_engine_integrate_host(sdrg_engine *e, const float *spectra, float *out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!e->integ_set) return fail(SDRG_E_INVALID, "no integration configuration set (sdrg_engine_set_integration)");
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const int n = e->cfg.samples_per_reading;
+    const size_t count = (size_t)e->n_streams * (size_t)n;
+    const float *src = e->d_spec_stage;
+    int32_t rc;
+    if (spectra) {  // a staging buffer of its own, as sdrg_engine_display_host
+        rc = integrate_buffer(&e->d_integ_in, &e->integ_in_elems, count);
+        if (rc) return rc;
+        src = e->d_integ_in;
+    } else if (!e->d_spec_stage || e->host_spec_n == 0) {
+        return fail(SDRG_E_INVALID, "no spectra on the device: no sdrg_engine_process_host call with SDRG_STAGE_SPECTRUM yet");
+    } else if (e->host_spec_n != n) {
+        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the spectra on the device were computed",
+                    e->host_spec_n, n);
+    }
+    rc = integrate_buffer(&e->d_integ_out, &e->integ_out_elems, count);
+    if (rc) return rc;
+    if (spectra) HIP_TRY(hipMemcpyAsync(e->d_integ_in, spectra, sizeof(float) * count, hipMemcpyHostToDevice, e->s_main));
+    rc = integrate_enqueue(e, src, e->d_integ_out);
+    if (rc) return rc;
+    e->integ_out_n = n;  // sdrg_engine_display_integrated_host reads these rows
+    if (out) HIP_TRY(hipMemcpyAsync(out, e->d_integ_out, sizeof(float) * count, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_display_integrated_host(sdrg_engine *e, void *rows_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!rows_out) return fail(SDRG_E_INVALID, "null rows_out");
+    DisplayParams p;
+    int32_t rc = display_params(e, &p);
+    if (rc) return rc;
+    if (!e->d_integ_out || e->integ_out_n == 0)
+        return fail(SDRG_E_INVALID, "no integrated rows on the device: no sdrg_engine_integrate_host call yet");
+    if (e->integ_out_n != p.n)
+        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the rows on the device were integrated",
+                    e->integ_out_n, p.n);
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const size_t out_bytes = (size_t)e->n_streams * display_row_bytes(p);
+    rc = ensure_device(&e->d_disp_out, &e->disp_out_bytes, out_bytes);
+    if (rc) return rc;
+    HIP_TRY(launch_display(e->d_integ_out, e->n_streams, p, e->d_disp_out, e->s_main));
+    HIP_TRY(hipMemcpyAsync(rows_out, e->d_disp_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
     HIP_TRY(hipStreamSynchronize(e->s_main));
     return SDRG_OK;
 }

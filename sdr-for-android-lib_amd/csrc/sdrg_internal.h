@@ -144,4 +144,16 @@ struct DisplayParams {
 };
 hipError_t launch_display(const float *spectra, int n_streams, const DisplayParams &p, void *out, hipStream_t stream);
 
+// Integration stage (integrate.hip): element-wise over count = n_streams * N floats.  MEAN / MAX: ring is
+// [period][slot_stride] floats (slot_stride = integrate_slot_stride(count), 16-byte aligned), the depth - 1 frames before
+// this one in the slots slot - (depth - 1) .. slot - 1 (mod period); the call writes its input to `slot`.  EMA: ema is
+// [count] floats, not read when depth == 1.  out may be spectra.
+struct IntegrateParams {
+    int mode, period, slot, depth;
+    float alpha;
+};
+size_t integrate_slot_stride(size_t count);
+hipError_t launch_integrate(const float *spectra, size_t count, const IntegrateParams &p, float *ring, size_t slot_stride,
+                            float *ema, float *out, hipStream_t stream);
+
 }  // namespace sdrg

@@ -35,6 +35,8 @@ PULSE_SPECTRAL, PULSE_AUDIO = 0, 1
 DISPLAY_SPAN_FULL, DISPLAY_SPAN_FOCUS, DISPLAY_SPAN_BINS = 0, 1, 2  # sdrg_display_config.span
 DISPLAY_MAX, DISPLAY_MEAN = 0, 1                                    # .reduce
 DISPLAY_DB_F32, DISPLAY_U8 = 0, 1                                   # .format
+INTEGRATE_MEAN, INTEGRATE_MAX, INTEGRATE_EMA = 0, 1, 2              # sdrg_integrate_config.mode
+INTEGRATE_MAX_PERIOD = 64
 STATUS = {0: "SDRG_OK", -1: "SDRG_E_INVALID", -2: "SDRG_E_UNSUPPORTED", -3: "SDRG_E_NOMEM", -4: "SDRG_E_HIP",
           -5: "SDRG_E_NODEVICE"}
 BYTES_PER_SAMPLE = {CF32: 8, CS8: 2, CU8: 2, CS16: 4}
@@ -108,6 +110,8 @@ EXPORTS = [
     "sdrg_device_alloc", "sdrg_device_free", "sdrg_memcpy", "sdrg_measure_hbm_copy",
     "sdrg_display_column_range", "sdrg_display_code", "sdrg_engine_set_display", "sdrg_engine_get_display",
     "sdrg_engine_display_geometry", "sdrg_engine_display_device", "sdrg_engine_display_host",
+    "sdrg_engine_set_integration", "sdrg_engine_get_integration", "sdrg_engine_integrate_reset",
+    "sdrg_engine_integrate_device", "sdrg_engine_integrate_host", "sdrg_engine_display_integrated_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -152,6 +156,11 @@ class DisplayConfig(ctypes.Structure):
     _fields_ = [("span", ctypes.c_int32), ("first_bin", ctypes.c_int32), ("n_bins", ctypes.c_int32),
                 ("width", ctypes.c_int32), ("reduce", ctypes.c_int32), ("format", ctypes.c_int32),
                 ("db_min", ctypes.c_float), ("db_max", ctypes.c_float)]
+
+
+class IntegrateConfig(ctypes.Structure):
+    """sdrg_integrate_config: the integration stage's mode, period (MEAN, MAX) and alpha (EMA) (include/sdrg.h)."""
+    _fields_ = [("mode", ctypes.c_int32), ("period", ctypes.c_int32), ("alpha", ctypes.c_float)]
 
 
 class _Timings(ctypes.Structure):
@@ -315,6 +324,12 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_display_geometry": (_I32, [P, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
         "sdrg_engine_display_device": (_I32, [P, P, P]),
         "sdrg_engine_display_host": (_I32, [P, P, P]),
+        "sdrg_engine_set_integration": (_I32, [P, ctypes.POINTER(IntegrateConfig)]),
+        "sdrg_engine_get_integration": (_I32, [P, ctypes.POINTER(IntegrateConfig), ctypes.POINTER(_I32)]),
+        "sdrg_engine_integrate_reset": (_I32, [P]),
+        "sdrg_engine_integrate_device": (_I32, [P, P, P]),
+        "sdrg_engine_integrate_host": (_I32, [P, P, P]),
+        "sdrg_engine_display_integrated_host": (_I32, [P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -702,6 +717,58 @@ class Engine:
             ptr = spectra.ctypes.data_as(ctypes.c_void_p)
         out = np.empty((self.n_streams, cfg["width"]), np.uint8 if cfg["format"] == DISPLAY_U8 else np.float32)
         _check(load().sdrg_engine_display_host(self._h, ptr, out.ctypes.data_as(ctypes.c_void_p)), "display_host")
+        return out
+
+    # ---- integration stage ------------------------------------------------------------------------
+    def set_integration(self, mode: int = INTEGRATE_MEAN, period: int = 0, alpha: float = 0.0) -> None:
+        """sdrg_engine_set_integration: MEAN / MAX over the last `period` frames (1 .. 64) or EMA with `alpha` in
+        (0, 1].  Resets the history; a rejected configuration leaves the previous one and its history in force."""
+        c = IntegrateConfig(mode, period, alpha)
+        _check(load().sdrg_engine_set_integration(self._h, ctypes.byref(c)), "set_integration")
+
+    def integration(self) -> dict:
+        """The configuration in force and `depth`, the number of frames the last output integrates (0 after a
+        reset)."""
+        c, depth = IntegrateConfig(), ctypes.c_int32()
+        _check(load().sdrg_engine_get_integration(self._h, ctypes.byref(c), ctypes.byref(depth)), "get_integration")
+        return dict(mode=c.mode, period=c.period, alpha=c.alpha, depth=depth.value)
+
+    def integration_depth(self) -> int:
+        depth = ctypes.c_int32()
+        _check(load().sdrg_engine_get_integration(self._h, None, ctypes.byref(depth)), "get_integration")
+        return depth.value
+
+    def integrate_reset(self) -> None:
+        _check(load().sdrg_engine_integrate_reset(self._h), "integrate_reset")
+
+    def integrate_device(self, spectra_ptr: int, out_ptr: int) -> None:
+        """Device path: spectra [n_streams][N] float32 in, integrated rows of the same shape out (out_ptr may be
+        spectra_ptr); asynchronous on the main stream (right after process_device it reads that call's spectra)."""
+        _check(load().sdrg_engine_integrate_device(self._h, spectra_ptr, out_ptr), "integrate_device")
+
+    def integrate(self, spectra: np.ndarray | None = None, want_output: bool = True) -> np.ndarray | None:
+        """Host path: feeds caller spectra ([n_streams][samplesPerReading] float32) or, with None, the spectra the
+        last process() call with STAGE_SPECTRUM left on the device, and returns the integrated rows; with
+        want_output=False they stay on the device (display_integrated() shows them) and None is returned."""
+        n = self.cfg.samplesPerReading
+        ptr = None
+        if spectra is not None:
+            spectra = np.ascontiguousarray(spectra, dtype=np.float32)
+            if spectra.shape != (self.n_streams, n):
+                raise SdrgError(f"spectra {spectra.shape}: expected ({self.n_streams}, {n})")
+            ptr = spectra.ctypes.data_as(ctypes.c_void_p)
+        out = np.empty((self.n_streams, n), np.float32) if want_output else None
+        _check(load().sdrg_engine_integrate_host(self._h, ptr, out.ctypes.data_as(ctypes.c_void_p) if want_output else None),
+               "integrate_host")
+        return out
+
+    def display_integrated(self) -> np.ndarray:
+        """The display rows [n_streams][width] (current display configuration) of the rows the last integrate() call
+        left on the device."""
+        cfg = self.display_config()
+        out = np.empty((self.n_streams, cfg["width"]), np.uint8 if cfg["format"] == DISPLAY_U8 else np.float32)
+        _check(load().sdrg_engine_display_integrated_host(self._h, out.ctypes.data_as(ctypes.c_void_p)),
+               "display_integrated_host")
         return out
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
