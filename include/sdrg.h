@@ -579,6 +579,71 @@ int32_t sdrg_engine_integrate_host(sdrg_engine *eng, const float *spectra, float
  * back only the display rows. */
 int32_t sdrg_engine_display_integrated_host(sdrg_engine *eng, void *rows_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the peak table stage.  Per stream, the at most max_peaks strongest
+ * local maxima of a span of one row x[0..N) of fftshifted linear power (a spectrum, or an integrated row), with a
+ * minimum spacing and a threshold over the span's noise floor: the marker table of a spectrum display
+ * (4096 x 16384: 16 max_peaks + 16 bytes per stream instead of 64 KiB).
+ *   span       [lo, lo + nb): the display stage's three modes and rules (SDRG_DISPLAY_SPAN_FULL / FOCUS / BINS, above),
+ *              resolved at each peaks call: an empty focus window, or lo + nb > N, fails that call with
+ *              SDRG_E_INVALID and enqueues nothing.  p_j = x[lo + j], j in [0, nb).
+ *   floor      F = the element of rank floor(nb / 2) (0-based) of p sorted ascending (the reference's gaps[size/2]
+ *              convention, fft_process.cpp:256); an exact select.
+ *   dB         dB(v) = 10.0f * log10f(v + 1e-20f), glibc's log10f bit for bit, as the display stage.  floor_db = dB(F).
+ *   candidate  with d = min_separation, bin j is a candidate iff p_j > p_i for every i in [max(0, j - d), j) and
+ *              p_j >= p_i for every i in (j, min(nb - 1, j + d)]: the first maximum of its window clipped to the span
+ *              (d > nb is allowed).  Two candidates are more than d bins apart; a plateau yields its lowest bin, a
+ *              constant row bin 0 only, a skirt falling monotonically from a strong bin nothing.
+ *   threshold  db_j = dB(p_j); snr_j = db_j - floor_db (one float subtraction).  A candidate is above iff
+ *              snr_j >= threshold_db (a NaN snr is not above).
+ *   result     n_above = the number of above candidates; count = min(n_above, max_peaks); the peaks are the first
+ *              `count` above candidates ordered by power descending, then bin ascending.
+ *   domain     finite powers >= +0 and +inf; -0, negative powers and NaN are undefined.  All N elements of a row are
+ *              data (also the element N - 1 the spectrum of an odd N never writes).
+ *   config     max_peaks in [1, SDRG_PEAKS_MAX], min_separation in [1, SDRG_PEAKS_MAX_SEPARATION], threshold_db finite
+ *              or -inf.
+ *   outputs    peaks [n_streams][max_peaks] sdrg_peak and summary [n_streams] sdrg_peaks_summary; every byte of both
+ *              is written by each call.  bin = lo + j (the row index), power = the bits read, db = db_j,
+ *              snr_db = snr_j; the entries past count are {-1, 0, 0, 0}.
+ * ---------------------------------------------------------------------------------------------- */
+enum { SDRG_PEAKS_MAX = 64, SDRG_PEAKS_MAX_SEPARATION = 4096 };
+typedef struct sdrg_peaks_config {
+    int32_t span, first_bin, n_bins;   /* SDRG_DISPLAY_SPAN_*; first_bin / n_bins: SPAN_BINS only */
+    int32_t max_peaks;
+    int32_t min_separation;
+    float threshold_db;
+} sdrg_peaks_config;
+typedef struct sdrg_peak {
+    int32_t bin;
+    float power, db, snr_db;
+} sdrg_peak;
+typedef struct sdrg_peaks_summary {
+    int32_t count, n_above;
+    float floor_power, floor_db;
+} sdrg_peaks_summary;
+
+/* Host-only, no device: the offset of bin `bin` of an fftshifted spectrum of n bins from the centre frequency, Hz:
+ * ((double)(bin - n / 2) * (double)sample_rate) / (double)n  (n >= 1, bin in [0, n)). */
+int32_t sdrg_bin_offset_hz(int32_t n, int64_t sample_rate, int32_t bin, double *out);
+
+/* Set the configuration every later peaks call uses.  Checks what does not depend on N (a known span, BINS:
+ * first_bin >= 0 and n_bins >= 1, max_peaks, min_separation, threshold_db); a rejected call leaves the previous
+ * configuration in force.  A peaks call before any set_peaks returns SDRG_E_INVALID. */
+int32_t sdrg_engine_set_peaks(sdrg_engine *eng, const sdrg_peaks_config *cfg);
+int32_t sdrg_engine_get_peaks(const sdrg_engine *eng, sdrg_peaks_config *out);
+/* spectra [n_streams][samples_per_reading] float, peaks [n_streams][max_peaks] and summary [n_streams] in device
+ * memory.  Reads spectra only.  Runs on the main stream (the caller's after sdrg_engine_set_stream): issued right after
+ * sdrg_engine_process_device or sdrg_engine_integrate_device it follows that call in every pipelining mode.  Complete
+ * after sdrg_engine_synchronize, or on a stream after sdrg_engine_wait_outputs. */
+int32_t sdrg_engine_peaks_device(sdrg_engine *eng, const float *spectra, sdrg_peak *peaks, sdrg_peaks_summary *summary);
+/* Host buffers, synchronous.  spectra == NULL: the spectra the last sdrg_engine_process_host call with
+ * SDRG_STAGE_SPECTRUM left on the device (the rule and the refusals of sdrg_engine_display_host(NULL)). */
+int32_t sdrg_engine_peaks_host(sdrg_engine *eng, const float *spectra, sdrg_peak *peaks, sdrg_peaks_summary *summary);
+/* The peak tables of the rows the last sdrg_engine_integrate_host call left on the device (the rule and the refusals of
+ * sdrg_engine_display_integrated_host): process_host(spectra = NULL) + integrate_host(NULL, NULL) +
+ * peaks_integrated_host copies back 16 max_peaks + 16 bytes per stream. */
+int32_t sdrg_engine_peaks_integrated_host(sdrg_engine *eng, sdrg_peak *peaks, sdrg_peaks_summary *summary);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

@@ -296,6 +296,13 @@ struct sdrg_engine {
     float *d_integ_out = nullptr;   // integrate_host's rows
     size_t integ_out_elems = 0;
     int integ_out_n = 0;            // N of the rows the last integrate_host call left in d_integ_out
+    // peak table stage (sdrg_engine_set_peaks / peaks_device / peaks_host; peaks.hip)
+    sdrg_peaks_config peaks{};
+    bool peaks_set = false;
+    float *d_peaks_in = nullptr;         // peaks_host's copy of the caller's spectra
+    size_t peaks_in_elems = 0;
+    unsigned char *d_peaks_out = nullptr;  // the host calls' tables: [n_streams][max_peaks] sdrg_peak, then the summaries
+    size_t peaks_out_bytes = 0;
 };
 
 namespace {
@@ -1046,7 +1053,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     void *bufs[] = {e->d_stats, e->d_ssb, e->d_twiddles, e->d_taps, e->d_nco_tab, e->d_chunk_table, e->d_ssb_scratch,
                     e->d_spec_scratch, e->d_fft_scratch, e->d_pool, e->d_rec_scratch, e->d_iq_stage, e->d_spec_stage,
                     e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->d_disp_in, e->d_disp_out,
-                    e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out};
+                    e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out, e->d_peaks_in, e->d_peaks_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
@@ -1524,26 +1531,39 @@ int32_t sdrg_engine_get_display(const sdrg_engine *e, sdrg_display_config *out) 
     return SDRG_OK;
 }
 
-// the configuration in force resolved against the current N and focus window
-static int32_t display_params(const sdrg_engine *e, DisplayParams *p) {
-    if (!e->disp_set) return fail(SDRG_E_INVALID, "no display configuration set (sdrg_engine_set_display)");
-    const sdrg_display_config &c = e->disp;
+// a span (SDRG_DISPLAY_SPAN_*, first_bin, n_bins) of the display or the peak table stage (`what`) resolved against the
+// current N and focus window: the bins [*lo, *lo + *nb) of a row of *n
+static int32_t resolve_span(const sdrg_engine *e, const char *what, int32_t span, int32_t first_bin, int32_t n_bins,
+                            int *n_out, int *lo_out, int *nb_out) {
     const int n = e->cfg.samples_per_reading;
     int64_t lo = 0, nb = n;
-    if (c.span == SDRG_DISPLAY_SPAN_FOCUS) {
+    if (span == SDRG_DISPLAY_SPAN_FOCUS) {
         if (e->fft_fs == 0) return fail(SDRG_E_INVALID, "the statistics' sample rate is 0");
         const StatsGeometry geo = stats_geometry(e->fft_fs, e->fft_fc, n, e->fft_focus);
         if (geo.focus_len <= 0) return fail(SDRG_E_INVALID, "the focus window is empty (focus range %d kHz)", e->fft_focus);
         lo = geo.focus_lo;
         nb = geo.focus_len;
-    } else if (c.span == SDRG_DISPLAY_SPAN_BINS) {
-        lo = c.first_bin;
-        nb = c.n_bins;
+    } else if (span == SDRG_DISPLAY_SPAN_BINS) {
+        lo = first_bin;
+        nb = n_bins;
     }
     if (lo < 0 || nb < 1 || lo + nb > n)
-        return fail(SDRG_E_INVALID, "display span [%lld, %lld) outside the %d bins of a frame", (long long)lo,
+        return fail(SDRG_E_INVALID, "%s span [%lld, %lld) outside the %d bins of a frame", what, (long long)lo,
                     (long long)(lo + nb), n);
-    *p = DisplayParams{n, (int)lo, (int)nb, c.width, c.reduce, c.format, 0.0f, 0.0f};
+    *n_out = n;
+    *lo_out = (int)lo;
+    *nb_out = (int)nb;
+    return SDRG_OK;
+}
+
+// the configuration in force resolved against the current N and focus window
+static int32_t display_params(const sdrg_engine *e, DisplayParams *p) {
+    if (!e->disp_set) return fail(SDRG_E_INVALID, "no display configuration set (sdrg_engine_set_display)");
+    const sdrg_display_config &c = e->disp;
+    int n, lo, nb;
+    const int32_t rc = resolve_span(e, "display", c.span, c.first_bin, c.n_bins, &n, &lo, &nb);
+    if (rc) return rc;
+    *p = DisplayParams{n, lo, nb, c.width, c.reduce, c.format, 0.0f, 0.0f};
     if (c.format == SDRG_DISPLAY_U8) {
         p->db_min = c.db_min;
         p->scale = 255.0f / (c.db_max - c.db_min);
@@ -1758,6 +1778,120 @@ int32_t sdrg_engine_display_integrated_host(sdrg_engine *e, void *rows_out) {
     HIP_TRY(hipMemcpyAsync(rows_out, e->d_disp_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
     HIP_TRY(hipStreamSynchronize(e->s_main));
     return SDRG_OK;
+}
+
+// ---- peak table stage (peaks.hip) ---------------------------------------------------------------------------------
+
+int32_t sdrg_bin_offset_hz(int32_t n, int64_t sample_rate, int32_t bin, double *out) {
+    if (!out) return fail(SDRG_E_INVALID, "null output");
+    if (n < 1 || bin < 0 || bin >= n) return fail(SDRG_E_INVALID, "n %d must be >= 1 and bin %d in [0, n)", n, bin);
+    *out = ((double)(bin - n / 2) * (double)sample_rate) / (double)n;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_peaks(sdrg_engine *e, const sdrg_peaks_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!cfg) return fail(SDRG_E_INVALID, "null peaks config");
+    if (cfg->span != SDRG_DISPLAY_SPAN_FULL && cfg->span != SDRG_DISPLAY_SPAN_FOCUS && cfg->span != SDRG_DISPLAY_SPAN_BINS)
+        return fail(SDRG_E_INVALID, "unknown peaks span %d", cfg->span);
+    if (cfg->span == SDRG_DISPLAY_SPAN_BINS && (cfg->first_bin < 0 || cfg->n_bins < 1))
+        return fail(SDRG_E_INVALID, "peaks span: first_bin %d must be >= 0 and n_bins %d >= 1", cfg->first_bin, cfg->n_bins);
+    if (cfg->max_peaks < 1 || cfg->max_peaks > SDRG_PEAKS_MAX)
+        return fail(SDRG_E_INVALID, "max_peaks %d outside [1, %d]", cfg->max_peaks, SDRG_PEAKS_MAX);
+    if (cfg->min_separation < 1 || cfg->min_separation > SDRG_PEAKS_MAX_SEPARATION)
+        return fail(SDRG_E_INVALID, "min_separation %d outside [1, %d]", cfg->min_separation, SDRG_PEAKS_MAX_SEPARATION);
+    if (std::isnan(cfg->threshold_db) || cfg->threshold_db == INFINITY)
+        return fail(SDRG_E_INVALID, "threshold_db must be finite or -inf");
+    e->peaks = *cfg;
+    e->peaks_set = true;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_peaks(const sdrg_engine *e, sdrg_peaks_config *out) {
+    if (!e || !out) return fail(SDRG_E_INVALID, "null argument");
+    if (!e->peaks_set) return fail(SDRG_E_INVALID, "no peaks configuration set");
+    *out = e->peaks;
+    return SDRG_OK;
+}
+
+// the configuration in force resolved against the current N and focus window
+static int32_t peaks_params(const sdrg_engine *e, PeaksParams *p) {
+    if (!e->peaks_set) return fail(SDRG_E_INVALID, "no peaks configuration set (sdrg_engine_set_peaks)");
+    const sdrg_peaks_config &c = e->peaks;
+    int n, lo, nb;
+    const int32_t rc = resolve_span(e, "peaks", c.span, c.first_bin, c.n_bins, &n, &lo, &nb);
+    if (rc) return rc;
+    *p = PeaksParams{n, lo, nb, c.max_peaks, c.min_separation, c.threshold_db};
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_peaks_device(sdrg_engine *e, const float *spectra, sdrg_peak *peaks, sdrg_peaks_summary *summary) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!spectra || !peaks || !summary) return fail(SDRG_E_INVALID, "null spectra, peaks or summary");
+    PeaksParams p;
+    int32_t rc = peaks_params(e, &p);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    HIP_TRY(launch_peaks(spectra, e->n_streams, p, peaks, summary, e->s_main));
+    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers the tables as it covers display rows
+    return SDRG_OK;
+}
+
+// src (device, [n_streams][p.n]) -> the caller's host tables, synchronous
+static int32_t peaks_to_host(sdrg_engine *e, const float *src, const PeaksParams &p, sdrg_peak *peaks,
+                             sdrg_peaks_summary *summary) {
+    const size_t B = (size_t)e->n_streams, pk_bytes = B * (size_t)p.max_peaks * sizeof(sdrg_peak),
+                 sm_bytes = B * sizeof(sdrg_peaks_summary);
+    int32_t rc = ensure_device(&e->d_peaks_out, &e->peaks_out_bytes, pk_bytes + sm_bytes);
+    if (rc) return rc;
+    sdrg_peak *d_pk = reinterpret_cast<sdrg_peak *>(e->d_peaks_out);
+    sdrg_peaks_summary *d_sm = reinterpret_cast<sdrg_peaks_summary *>(e->d_peaks_out + pk_bytes);
+    HIP_TRY(launch_peaks(src, e->n_streams, p, d_pk, d_sm, e->s_main));
+    HIP_TRY(hipMemcpyAsync(peaks, d_pk, pk_bytes, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipMemcpyAsync(summary, d_sm, sm_bytes, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_peaks_host(sdrg_engine *e, const float *spectra, sdrg_peak *peaks, sdrg_peaks_summary *summary) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!peaks || !summary) return fail(SDRG_E_INVALID, "null peaks or summary");
+    PeaksParams p;
+    int32_t rc = peaks_params(e, &p);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const size_t count = (size_t)e->n_streams * (size_t)p.n;
+    const float *src = e->d_spec_stage;
+    if (spectra) {  // a staging buffer of its own, as sdrg_engine_display_host
+        rc = ensure_device(&e->d_peaks_in, &e->peaks_in_elems, count);
+        if (rc) return rc;
+        src = e->d_peaks_in;
+        HIP_TRY(hipMemcpyAsync(e->d_peaks_in, spectra, sizeof(float) * count, hipMemcpyHostToDevice, e->s_main));
+    } else if (!e->d_spec_stage || e->host_spec_n == 0) {
+        return fail(SDRG_E_INVALID, "no spectra on the device: no sdrg_engine_process_host call with SDRG_STAGE_SPECTRUM yet");
+    } else if (e->host_spec_n != p.n) {
+        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the spectra on the device were computed",
+                    e->host_spec_n, p.n);
+    }
+    return peaks_to_host(e, src, p, peaks, summary);
+}
+
+int32_t sdrg_engine_peaks_integrated_host(sdrg_engine *e, sdrg_peak *peaks, sdrg_peaks_summary *summary) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!peaks || !summary) return fail(SDRG_E_INVALID, "null peaks or summary");
+    PeaksParams p;
+    int32_t rc = peaks_params(e, &p);
+    if (rc) return rc;
+    if (!e->d_integ_out || e->integ_out_n == 0)
+        return fail(SDRG_E_INVALID, "no integrated rows on the device: no sdrg_engine_integrate_host call yet");
+    if (e->integ_out_n != p.n)
+        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the rows on the device were integrated",
+                    e->integ_out_n, p.n);
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    return peaks_to_host(e, e->d_integ_out, p, peaks, summary);
 }
 
 int32_t sdrg_engine_set_callbacks(sdrg_engine *e, const sdrg_callbacks *cbs) {

@@ -156,4 +156,14 @@ size_t integrate_slot_stride(size_t count);
 hipError_t launch_integrate(const float *spectra, size_t count, const IntegrateParams &p, float *ring, size_t slot_stride,
                             float *ema, float *out, hipStream_t stream);
 
+// Peak table stage (peaks.hip): per row of n floats, the span [lo, lo + nb): noise floor (rank nb / 2), the candidates
+// (first maximum of a window of +- min_sep bins), those at least threshold_db over the floor, the max_peaks strongest.
+// peaks: [n_streams][max_peaks], summary: [n_streams]; every byte of both is written.
+struct PeaksParams {
+    int n, lo, nb, max_peaks, min_sep;
+    float threshold_db;
+};
+hipError_t launch_peaks(const float *spectra, int n_streams, const PeaksParams &p, sdrg_peak *peaks,
+                        sdrg_peaks_summary *summary, hipStream_t stream);
+
 }  // namespace sdrg

@@ -37,6 +37,7 @@ DISPLAY_MAX, DISPLAY_MEAN = 0, 1                                    # .reduce
 DISPLAY_DB_F32, DISPLAY_U8 = 0, 1                                   # .format
 INTEGRATE_MEAN, INTEGRATE_MAX, INTEGRATE_EMA = 0, 1, 2              # sdrg_integrate_config.mode
 INTEGRATE_MAX_PERIOD = 64
+PEAKS_MAX, PEAKS_MAX_SEPARATION = 64, 4096                          # SDRG_PEAKS_MAX, SDRG_PEAKS_MAX_SEPARATION
 STATUS = {0: "SDRG_OK", -1: "SDRG_E_INVALID", -2: "SDRG_E_UNSUPPORTED", -3: "SDRG_E_NOMEM", -4: "SDRG_E_HIP",
           -5: "SDRG_E_NODEVICE"}
 BYTES_PER_SAMPLE = {CF32: 8, CS8: 2, CU8: 2, CS16: 4}
@@ -81,6 +82,9 @@ PULSE_OUTPUT_DTYPE = np.dtype(
     align=True,
 )
 
+PEAK_DTYPE = np.dtype([("bin", "<i4"), ("power", "<f4"), ("db", "<f4"), ("snr_db", "<f4")])  # sdrg_peak
+PEAKS_SUMMARY_DTYPE = np.dtype([("count", "<i4"), ("n_above", "<i4"), ("floor_power", "<f4"), ("floor_db", "<f4")])
+
 # Every entry point include/sdrg.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "sdrg_abi_version", "sdrg_last_error", "sdrg_ssb_pcm_len", "sdrg_focus_window", "sdrg_host_alloc", "sdrg_host_free", "sdrg_ssb_design", "sdrg_engine_create", "sdrg_engine_destroy",
@@ -112,6 +116,8 @@ EXPORTS = [
     "sdrg_engine_display_geometry", "sdrg_engine_display_device", "sdrg_engine_display_host",
     "sdrg_engine_set_integration", "sdrg_engine_get_integration", "sdrg_engine_integrate_reset",
     "sdrg_engine_integrate_device", "sdrg_engine_integrate_host", "sdrg_engine_display_integrated_host",
+    "sdrg_bin_offset_hz", "sdrg_engine_set_peaks", "sdrg_engine_get_peaks", "sdrg_engine_peaks_device",
+    "sdrg_engine_peaks_host", "sdrg_engine_peaks_integrated_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -161,6 +167,12 @@ class DisplayConfig(ctypes.Structure):
 class IntegrateConfig(ctypes.Structure):
     """sdrg_integrate_config: the integration stage's mode, period (MEAN, MAX) and alpha (EMA) (include/sdrg.h)."""
     _fields_ = [("mode", ctypes.c_int32), ("period", ctypes.c_int32), ("alpha", ctypes.c_float)]
+
+
+class PeaksConfig(ctypes.Structure):
+    """sdrg_peaks_config: the peak table stage's span, table size, spacing and threshold (include/sdrg.h)."""
+    _fields_ = [("span", ctypes.c_int32), ("first_bin", ctypes.c_int32), ("n_bins", ctypes.c_int32),
+                ("max_peaks", ctypes.c_int32), ("min_separation", ctypes.c_int32), ("threshold_db", ctypes.c_float)]
 
 
 class _Timings(ctypes.Structure):
@@ -330,6 +342,12 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_integrate_device": (_I32, [P, P, P]),
         "sdrg_engine_integrate_host": (_I32, [P, P, P]),
         "sdrg_engine_display_integrated_host": (_I32, [P, P]),
+        "sdrg_bin_offset_hz": (_I32, [_I32, _I64, _I32, ctypes.POINTER(ctypes.c_double)]),
+        "sdrg_engine_set_peaks": (_I32, [P, ctypes.POINTER(PeaksConfig)]),
+        "sdrg_engine_get_peaks": (_I32, [P, ctypes.POINTER(PeaksConfig)]),
+        "sdrg_engine_peaks_device": (_I32, [P, P, P, P]),
+        "sdrg_engine_peaks_host": (_I32, [P, P, P, P]),
+        "sdrg_engine_peaks_integrated_host": (_I32, [P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -483,6 +501,13 @@ def display_code(db: float, db_min: float, db_max: float) -> int:
     code = ctypes.c_uint8()
     _check(load().sdrg_display_code(db, db_min, db_max, ctypes.byref(code)), "display_code")
     return code.value
+
+
+def bin_offset_hz(n: int, sample_rate: int, bin: int) -> float:
+    """The offset of bin `bin` of an fftshifted spectrum of n bins from the centre frequency, Hz (host-side)."""
+    out = ctypes.c_double()
+    _check(load().sdrg_bin_offset_hz(n, sample_rate, bin, ctypes.byref(out)), "bin_offset_hz")
+    return out.value
 
 
 def ssb_design(samp_count: int, sample_rate: int, sound_mode: int = 1) -> dict:
@@ -770,6 +795,52 @@ class Engine:
         _check(load().sdrg_engine_display_integrated_host(self._h, out.ctypes.data_as(ctypes.c_void_p)),
                "display_integrated_host")
         return out
+
+    # ---- peak table stage ------------------------------------------------------------------------
+    def set_peaks(self, **fields) -> None:
+        """sdrg_engine_set_peaks: span, first_bin, n_bins, max_peaks, min_separation, threshold_db (fields left out
+        are 0)."""
+        c = PeaksConfig()
+        for k, v in fields.items():
+            if k not in dict(PeaksConfig._fields_):
+                raise TypeError(f"unknown peaks field {k!r}")
+            setattr(c, k, v)
+        _check(load().sdrg_engine_set_peaks(self._h, ctypes.byref(c)), "set_peaks")
+
+    def peaks_config(self) -> dict:
+        c = PeaksConfig()
+        _check(load().sdrg_engine_get_peaks(self._h, ctypes.byref(c)), "get_peaks")
+        return {k: getattr(c, k) for k, _ in PeaksConfig._fields_}
+
+    def peaks_device(self, spectra_ptr: int, peaks_ptr: int, summary_ptr: int) -> None:
+        """Device path: spectra [n_streams][N] float32 in, peaks [n_streams][max_peaks] PEAK_DTYPE and summary
+        [n_streams] PEAKS_SUMMARY_DTYPE out; asynchronous on the main stream."""
+        _check(load().sdrg_engine_peaks_device(self._h, spectra_ptr, peaks_ptr, summary_ptr), "peaks_device")
+
+    def _peaks_out(self):
+        k = self.peaks_config()["max_peaks"]
+        return np.empty((self.n_streams, k), PEAK_DTYPE), np.empty(self.n_streams, PEAKS_SUMMARY_DTYPE)
+
+    def peaks(self, spectra: np.ndarray | None = None):
+        """Host path: (peaks [n_streams][max_peaks], summary [n_streams]) of caller spectra [n_streams][N], or, with
+        spectra=None, of the spectra the last process() call with STAGE_SPECTRUM left on the device."""
+        pk, sm = self._peaks_out()
+        ptr = None
+        if spectra is not None:
+            spectra = np.ascontiguousarray(spectra, dtype=np.float32)
+            if spectra.shape != (self.n_streams, self.cfg.samplesPerReading):
+                raise SdrgError(f"spectra {spectra.shape}: expected ({self.n_streams}, {self.cfg.samplesPerReading})")
+            ptr = spectra.ctypes.data_as(ctypes.c_void_p)
+        _check(load().sdrg_engine_peaks_host(self._h, ptr, pk.ctypes.data_as(ctypes.c_void_p),
+                                             sm.ctypes.data_as(ctypes.c_void_p)), "peaks_host")
+        return pk, sm
+
+    def peaks_integrated(self):
+        """(peaks, summary) of the rows the last integrate() call left on the device."""
+        pk, sm = self._peaks_out()
+        _check(load().sdrg_engine_peaks_integrated_host(self._h, pk.ctypes.data_as(ctypes.c_void_p),
+                                                        sm.ctypes.data_as(ctypes.c_void_p)), "peaks_integrated_host")
+        return pk, sm
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
                        pcm_ptr: int | None, now_ms: int = 0) -> None:
