@@ -644,6 +644,74 @@ int32_t sdrg_engine_peaks_host(sdrg_engine *eng, const float *spectra, sdrg_peak
  * peaks_integrated_host copies back 16 max_peaks + 16 bytes per stream. */
 int32_t sdrg_engine_peaks_integrated_host(sdrg_engine *eng, sdrg_peak *peaks, sdrg_peaks_summary *summary);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the DDC stage (digital down-converter).  Per stream, a channel at
+ * offset_hz from the centre frequency: the raw IQ mixed down by a phase-continuous NCO, low-passed by a T-tap FIR and
+ * decimated by D, as CF32.  Over the whole life of a stream (the calls' frames concatenated, whatever their lengths and
+ * formats) y[m] = sum_k h[k] v[m D - k]; each call writes the outputs its frame completes.  All arithmetic is float
+ * unless stated; fs = (uint32_t) of the bridge's current sample rate (the rate the SSB chain follows), N =
+ * samples_per_reading at the call.
+ *   config     offset_hz finite; decimation D in [1, SDRG_DDC_MAX_DECIMATION]; taps T odd in [1, SDRG_DDC_MAX_TAPS];
+ *              0 < cutoff_hz <= fs / 2 with the fs at set_ddc.  A rejected set_ddc leaves the previous configuration and
+ *              state in force; an accepted one, and sdrg_engine_ddc_reset, restart every stream: g0 = 0, history +0.
+ *   per call   inc = round(frac(offset_hz / fs) * 2^32) mod 2^32 (the SSB variant's NCO increment) and the taps are
+ *              resolved from the current fs; an fs other than the previous ddc call's restarts the streams first;
+ *              cutoff_hz > fs / 2 fails the call with SDRG_E_INVALID and commits nothing (no restart either).  A change
+ *              of samples_per_reading restarts nothing.
+ *   taps       sdrg_ddc_design, in double: for k in [0, T): c = k - (T - 1) / 2, f = cutoff_hz / fs,
+ *              ideal = 2 f if c == 0 else sin(2 pi f c) / (pi c), w = 0.5 - 0.5 cos(2 pi (k + 1) / (T + 1)),
+ *              h[k] = (float)(ideal w / sum(ideal w)).
+ *   unpack     CS8 (float)v * (1/128), CU8 ((float)v - 127.4f) * (1/128), CS16 (float)v * (1/32768), CF32 as is.
+ *   mix        sample t of the frame has the global index g = g0 + t (uint64); ph = (uint32)(inc * g);
+ *              H = hi[ph >> 22], L = lo[(ph >> 12) & 1023] of sdrg_nco_tables; wr = H.re L.re - H.im L.im,
+ *              wi = H.re L.im + H.im L.re; vr = xr wr - xi wi, vi = xr wi + xi wr: every product and every sum
+ *              rounded on its own.  inc = 0 goes through the table too (hi[0] lo[0] = 1).
+ *   filter     for every m with g0 <= m D < g0 + N: acc = +0.0f, then for k = 0 .. T - 1 in this order
+ *              acc = acc + h[k] * v[m D - k], each component on its own (a rounded multiply, then a rounded add);
+ *              v[g] = +0 for g < 0.  n_out = ceil((g0 + N) / D) - ceil(g0 / D), the same for every stream, 0 when the
+ *              frame holds no multiple of D.  The group delay of (T - 1) / 2 input samples is not compensated.
+ *   output     out [n_streams][cap][2] float, cap = ceil(N / D); every byte is written by every call, the entries from
+ *              n_out on are +0.  *n_out is set on the host before the call returns.
+ *   state      per stream the last T - 1 mixed samples (floats, in device memory, allocated at the first ddc call), per
+ *              engine g0, advanced by N once the call's launches have been issued: a failed call commits nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_DDC_MAX_TAPS 511
+#define SDRG_DDC_MAX_DECIMATION 512
+typedef struct sdrg_ddc_config {
+    double offset_hz;
+    double cutoff_hz;
+    int32_t decimation;
+    int32_t taps;
+} sdrg_ddc_config;
+
+/* Host-only, no device.  The taps of cfg at sample_rate (cfg->taps floats), after the checks of set_ddc (offset_hz
+ * included); sample_rate must be in [1, 2^32). */
+int32_t sdrg_ddc_design(int64_t sample_rate, const sdrg_ddc_config *cfg, float *taps);
+/* Host-only: the NCO's phasor tables, 4096 floats: hi[1024] then lo[1024], each {re, im}; hi[a] = e^{-j 2 pi a / 2^10},
+ * lo[b] = e^{-j 2 pi b / 2^20}, computed in double and rounded to float (the tables of the SSB variant's NCO). */
+int32_t sdrg_nco_tables(float *tab);
+/* Host-only: how many consecutive outputs one workgroup of the DDC kernel computes for (decimation, taps): an output
+ * index that is a multiple of it starts a new tile (for tests that want windows across every tile seam). */
+int32_t sdrg_ddc_tile_outputs(int32_t decimation, int32_t taps, int32_t *tile);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the DDC.  A ddc call while it is off returns SDRG_E_INVALID and writes
+ * nothing. */
+int32_t sdrg_engine_set_ddc(sdrg_engine *eng, const sdrg_ddc_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), the NCO increment at the current sample rate and g0, the
+ * samples every stream has consumed since the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_ddc(const sdrg_engine *eng, sdrg_ddc_config *cfg, uint32_t *nco_increment,
+                            uint64_t *samples_consumed);
+int32_t sdrg_engine_ddc_reset(sdrg_engine *eng);
+/* cap = ceil(N / D) for the current samples_per_reading: the row length of `out`, in complex samples. */
+int32_t sdrg_engine_ddc_max_out(const sdrg_engine *eng, int32_t *cap);
+/* iq [n_streams][N] raw samples of format fmt (SDRG_IQ_*) and out [n_streams][cap][2] float in device memory.  Reads iq
+ * only and shares nothing with sdrg_engine_process_device.  Runs on the main stream (the caller's after
+ * sdrg_engine_set_stream); complete after sdrg_engine_synchronize, or on a stream after sdrg_engine_wait_outputs.  out
+ * may be handed to another engine's sdrg_engine_process_device as CF32 input (samples_per_reading = cap there). */
+int32_t sdrg_engine_ddc_device(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
+/* Host buffers, synchronous. */
+int32_t sdrg_engine_ddc_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

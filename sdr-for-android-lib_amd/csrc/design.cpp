@@ -221,4 +221,29 @@ void nco_tables(float *tab) {
     }
 }
 
+// The DDC stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *ddc_check(uint32_t sample_rate, double offset_hz, double cutoff_hz, int decimation, int taps) {
+    if (sample_rate == 0) return "sample_rate must be > 0";
+    if (!std::isfinite(offset_hz)) return "offset_hz must be finite";
+    if (decimation < 1 || decimation > 512) return "decimation outside [1, 512]";
+    if (taps < 1 || taps > 511 || (taps & 1) == 0) return "taps must be odd and in [1, 511]";
+    if (!(cutoff_hz > 0.0 && cutoff_hz <= (double)sample_rate / 2.0)) return "cutoff_hz outside (0, sample_rate / 2]";
+    return nullptr;
+}
+
+// The DDC stage's low-pass (sdrg.h): a Hann-windowed sinc of `taps` (odd) coefficients with unit DC gain, in double
+void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h) {
+    const double f = cutoff_hz / (double)sample_rate;
+    double v[511];
+    double sum = 0.0;
+    for (int k = 0; k < taps; k++) {
+        const int c = k - (taps - 1) / 2;
+        const double ideal = c == 0 ? 2.0 * f : std::sin(2.0 * M_PI * f * (double)c) / (M_PI * (double)c);
+        const double w = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)(k + 1) / (double)(taps + 1));
+        v[k] = ideal * w;
+        sum += v[k];
+    }
+    for (int k = 0; k < taps; k++) h[k] = (float)(v[k] / sum);
+}
+
 }  // namespace sdrg

@@ -303,6 +303,23 @@ struct sdrg_engine {
     size_t peaks_in_elems = 0;
     unsigned char *d_peaks_out = nullptr;  // the host calls' tables: [n_streams][max_peaks] sdrg_peak, then the summaries
     size_t peaks_out_bytes = 0;
+    // DDC stage (sdrg_engine_set_ddc / ddc_device / ddc_host; ddc.hip)
+    sdrg_ddc_config ddc{};
+    bool ddc_set = false;
+    uint64_t ddc_g0 = 0;        // samples every stream has consumed since the last restart
+    bool ddc_fresh = true;      // the next call starts from a history of zeros
+    int ddc_half = 0;           // the half of d_ddc_hist the next call reads
+    uint32_t ddc_fs = 0;        // the sample rate of the previous ddc call (0: none since set_ddc)
+    float *d_ddc_hist = nullptr;  // [2][n_streams][taps - 1][2]: the mixed samples before the next frame, ping-pong
+    size_t ddc_hist_elems = 0;
+    float *d_ddc_w = nullptr;     // [N][2]: the phasors of the frame in flight, shared by the streams
+    size_t ddc_w_elems = 0;
+    uint32_t ddc_taps_fs = 0;   // the sample rate ddc_taps was designed for (0: not designed)
+    DdcTaps ddc_taps{};
+    void *d_ddc_in = nullptr;   // ddc_host's copy of the caller's iq
+    size_t ddc_in_bytes = 0;
+    float *d_ddc_out = nullptr;  // ddc_host's rows
+    size_t ddc_out_elems = 0;
 };
 
 namespace {
@@ -1053,7 +1070,8 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     void *bufs[] = {e->d_stats, e->d_ssb, e->d_twiddles, e->d_taps, e->d_nco_tab, e->d_chunk_table, e->d_ssb_scratch,
                     e->d_spec_scratch, e->d_fft_scratch, e->d_pool, e->d_rec_scratch, e->d_iq_stage, e->d_spec_stage,
                     e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->d_disp_in, e->d_disp_out,
-                    e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out, e->d_peaks_in, e->d_peaks_out};
+                    e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out, e->d_peaks_in, e->d_peaks_out, e->d_ddc_hist,
+                    e->d_ddc_w, e->d_ddc_in, e->d_ddc_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
@@ -1892,6 +1910,182 @@ int32_t sdrg_engine_peaks_integrated_host(sdrg_engine *e, sdrg_peak *peaks, sdrg
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     return peaks_to_host(e, e->d_integ_out, p, peaks, summary);
+}
+
+// ---- DDC stage (ddc.hip) ------------------------------------------------------------------------------------------
+
+int32_t sdrg_ddc_design(int64_t sample_rate, const sdrg_ddc_config *cfg, float *taps) {
+    if (!cfg || !taps) return fail(SDRG_E_INVALID, "null ddc config or taps");
+    if (sample_rate < 1 || sample_rate > (int64_t)UINT32_MAX)
+        return fail(SDRG_E_INVALID, "sample_rate %lld outside [1, 2^32)", (long long)sample_rate);
+    if (const char *bad = ddc_check((uint32_t)sample_rate, cfg->offset_hz, cfg->cutoff_hz, cfg->decimation, cfg->taps))
+        return fail(SDRG_E_INVALID, "ddc: %s", bad);
+    ddc_design((uint32_t)sample_rate, cfg->cutoff_hz, cfg->taps, taps);
+    return SDRG_OK;
+}
+
+int32_t sdrg_nco_tables(float *tab) {
+    if (!tab) return fail(SDRG_E_INVALID, "null table");
+    nco_tables(tab);
+    return SDRG_OK;
+}
+
+int32_t sdrg_ddc_tile_outputs(int32_t decimation, int32_t taps, int32_t *tile) {
+    if (!tile) return fail(SDRG_E_INVALID, "null tile");
+    if (const char *bad = ddc_check(2, 0.0, 1.0, decimation, taps)) return fail(SDRG_E_INVALID, "ddc: %s", bad);
+    *tile = ddc_tile_outputs(decimation, taps);
+    return SDRG_OK;
+}
+
+static void ddc_restart(sdrg_engine *e) {
+    e->ddc_g0 = 0;
+    e->ddc_fresh = true;
+    e->ddc_fs = 0;
+}
+
+int32_t sdrg_engine_set_ddc(sdrg_engine *e, const sdrg_ddc_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (cfg) {
+        if (const char *bad = ddc_check((uint32_t)e->cfg.sample_rate, cfg->offset_hz, cfg->cutoff_hz, cfg->decimation,
+                                        cfg->taps))
+            return fail(SDRG_E_INVALID, "ddc: %s", bad);
+        e->ddc = *cfg;
+    }
+    e->ddc_set = cfg != nullptr;
+    e->ddc_taps_fs = 0;
+    ddc_restart(e);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_ddc(const sdrg_engine *e, sdrg_ddc_config *cfg, uint32_t *nco_increment_out,
+                            uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!e->ddc_set) return fail(SDRG_E_INVALID, "no ddc configuration set");
+    if (cfg) *cfg = e->ddc;
+    if (nco_increment_out) *nco_increment_out = nco_increment(e->ddc.offset_hz, (uint32_t)e->cfg.sample_rate);
+    if (samples_consumed) *samples_consumed = e->ddc_g0;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_ddc_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    ddc_restart(e);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_ddc_max_out(const sdrg_engine *e, int32_t *cap) {
+    if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
+    if (!e->ddc_set) return fail(SDRG_E_INVALID, "no ddc configuration set (sdrg_engine_set_ddc)");
+    *cap = (e->cfg.samples_per_reading + e->ddc.decimation - 1) / e->ddc.decimation;
+    return SDRG_OK;
+}
+
+// what one ddc call needs beside its buffers, resolved before anything is touched
+struct DdcCall {
+    uint32_t fs;
+    bool restart;  // the sample rate changed since the previous ddc call
+    int n, cap, n_out;
+};
+
+static int32_t ddc_resolve(const sdrg_engine *e, int32_t fmt, DdcCall *c) {
+    if (!e->ddc_set) return fail(SDRG_E_INVALID, "no ddc configuration set (sdrg_engine_set_ddc)");
+    if (bytes_per_sample(fmt) == 0) return fail(SDRG_E_INVALID, "unknown iq format %d", fmt);
+    c->fs = (uint32_t)e->cfg.sample_rate;
+    if (e->ddc.cutoff_hz > (double)c->fs / 2.0)
+        return fail(SDRG_E_INVALID, "ddc cutoff %g Hz above half the sample rate %u", e->ddc.cutoff_hz, c->fs);
+    c->restart = e->ddc_fs != 0 && e->ddc_fs != c->fs;
+    const uint64_t g0 = c->restart ? 0 : e->ddc_g0, D = (uint64_t)e->ddc.decimation;
+    c->n = e->cfg.samples_per_reading;
+    c->cap = (c->n + e->ddc.decimation - 1) / e->ddc.decimation;
+    c->n_out = (int)((g0 + (uint64_t)c->n + D - 1) / D - (g0 + D - 1) / D);
+    return SDRG_OK;
+}
+
+// one ddc call on the main stream: iq, out in device memory
+static int32_t ddc_enqueue(sdrg_engine *e, const DdcCall &c, const void *iq, int32_t fmt, float *out) {
+    const sdrg_ddc_config &cfg = e->ddc;
+    const int T = cfg.taps, D = cfg.decimation;
+    const size_t half = (size_t)e->n_streams * (size_t)(T - 1) * 2;
+    if (e->ddc_hist_elems < 2 * half || !e->d_ddc_hist) {
+        // only a larger T asks for more, and set_ddc restarted the streams: nothing to keep
+        int32_t rc = ensure_device(&e->d_ddc_hist, &e->ddc_hist_elems, std::max<size_t>(2 * half, 2));
+        if (rc) return rc;
+    }
+    {  // a longer frame than any before: hipFree waits for the calls that read the old row
+        int32_t rc = ensure_device(&e->d_ddc_w, &e->ddc_w_elems, 2 * (size_t)c.n);
+        if (rc) return rc;
+    }
+    if (!e->d_nco_tab) {
+        std::vector<float> tab(4096);
+        nco_tables(tab.data());
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_nco_tab), sizeof(float) * tab.size()));
+        HIP_TRY(hipMemcpy(e->d_nco_tab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    }
+    if (e->ddc_taps_fs != c.fs) {  // the taps travel in the kernel arguments: nothing on the device to replace
+        ddc_design(c.fs, cfg.cutoff_hz, T, e->ddc_taps.h);
+        e->ddc_taps_fs = c.fs;
+    }
+    const bool fresh = c.restart || e->ddc_fresh;
+    const uint64_t g0 = c.restart ? 0 : e->ddc_g0;
+    DdcParams p{};
+    p.n = c.n;
+    p.decim = D;
+    p.taps = T;
+    p.first = (int)(((uint64_t)D - g0 % (uint64_t)D) % (uint64_t)D);
+    p.n_out = c.n_out;
+    p.cap = c.cap;
+    p.inc = nco_increment(cfg.offset_hz, c.fs);
+    p.g0_lo = (uint32_t)g0;
+    p.nco_tab = e->d_nco_tab;
+    p.hist_old = fresh ? nullptr : e->d_ddc_hist + (size_t)e->ddc_half * half;
+    p.hist_new = e->d_ddc_hist + (size_t)(e->ddc_half ^ 1) * half;
+    p.phasors = e->d_ddc_w;
+    HIP_TRY(launch_ddc(iq, fmt, e->n_streams, p, e->ddc_taps, out, e->s_main));
+    e->ddc_g0 = g0 + (uint64_t)c.n;
+    e->ddc_fresh = false;
+    e->ddc_half ^= 1;
+    e->ddc_fs = c.fs;
+    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers out as it covers display rows
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_ddc_device(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    DdcCall c;
+    int32_t rc = ddc_resolve(e, fmt, &c);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    rc = ddc_enqueue(e, c, iq, fmt, static_cast<float *>(out));
+    if (rc) return rc;
+    *n_out = c.n_out;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_ddc_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    DdcCall c;
+    int32_t rc = ddc_resolve(e, fmt, &c);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const size_t in_bytes = (size_t)e->n_streams * (size_t)c.n * (size_t)bytes_per_sample(fmt);
+    const size_t out_elems = (size_t)e->n_streams * (size_t)c.cap * 2;
+    char *in = static_cast<char *>(e->d_ddc_in);
+    rc = ensure_device(&in, &e->ddc_in_bytes, in_bytes);
+    e->d_ddc_in = in;
+    if (rc) return rc;
+    rc = ensure_device(&e->d_ddc_out, &e->ddc_out_elems, out_elems);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_ddc_in, iq, in_bytes, hipMemcpyHostToDevice, e->s_main));
+    rc = ddc_enqueue(e, c, e->d_ddc_in, fmt, e->d_ddc_out);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->d_ddc_out, sizeof(float) * out_elems, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
+    *n_out = c.n_out;
+    return SDRG_OK;
 }
 
 int32_t sdrg_engine_set_callbacks(sdrg_engine *e, const sdrg_callbacks *cbs) {

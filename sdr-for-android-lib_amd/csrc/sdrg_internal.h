@@ -166,4 +166,25 @@ struct PeaksParams {
 hipError_t launch_peaks(const float *spectra, int n_streams, const PeaksParams &p, sdrg_peak *peaks,
                         sdrg_peaks_summary *summary, hipStream_t stream);
 
+// DDC stage (ddc.hip): per stream, out[j] = sum_k h[k] v[first + j decim - k], j in [0, n_out), v the frame's n raw
+// samples mixed by the NCO (phase inc * (g0_lo + t) at local index t) and, at t in [-(taps - 1), 0), hist_old
+// [n_streams][taps - 1][2] (nullptr: zeros).  Writes out [n_streams][cap][2] whole (zeros from n_out on), the mixed
+// samples at t in [n - (taps - 1), n) to hist_new, and the frame's phasors to `phasors` (scratch of n float2, all streams
+// share it).  tile, row, n_tiles and vec_ok are the launcher's.
+struct DdcParams {
+    int n, decim, taps, first, n_out, cap;
+    uint32_t inc, g0_lo;
+    const float *nco_tab;    // nco_tables() on the device
+    const float *hist_old;
+    float *hist_new;
+    float *phasors;
+    int tile, row, n_tiles, vec_ok;
+};
+struct DdcTaps {
+    float h[SDRG_DDC_MAX_TAPS];
+};
+int ddc_tile_outputs(int decim, int taps);  // outputs per workgroup
+hipError_t launch_ddc(const void *iq, int fmt, int n_streams, const DdcParams &p, const DdcTaps &taps, float *out,
+                      hipStream_t stream);
+
 }  // namespace sdrg

@@ -38,6 +38,7 @@ DISPLAY_DB_F32, DISPLAY_U8 = 0, 1                                   # .format
 INTEGRATE_MEAN, INTEGRATE_MAX, INTEGRATE_EMA = 0, 1, 2              # sdrg_integrate_config.mode
 INTEGRATE_MAX_PERIOD = 64
 PEAKS_MAX, PEAKS_MAX_SEPARATION = 64, 4096                          # SDRG_PEAKS_MAX, SDRG_PEAKS_MAX_SEPARATION
+DDC_MAX_TAPS, DDC_MAX_DECIMATION = 511, 512                         # SDRG_DDC_MAX_TAPS, SDRG_DDC_MAX_DECIMATION
 STATUS = {0: "SDRG_OK", -1: "SDRG_E_INVALID", -2: "SDRG_E_UNSUPPORTED", -3: "SDRG_E_NOMEM", -4: "SDRG_E_HIP",
           -5: "SDRG_E_NODEVICE"}
 BYTES_PER_SAMPLE = {CF32: 8, CS8: 2, CU8: 2, CS16: 4}
@@ -118,6 +119,8 @@ EXPORTS = [
     "sdrg_engine_integrate_device", "sdrg_engine_integrate_host", "sdrg_engine_display_integrated_host",
     "sdrg_bin_offset_hz", "sdrg_engine_set_peaks", "sdrg_engine_get_peaks", "sdrg_engine_peaks_device",
     "sdrg_engine_peaks_host", "sdrg_engine_peaks_integrated_host",
+    "sdrg_ddc_design", "sdrg_nco_tables", "sdrg_ddc_tile_outputs", "sdrg_engine_set_ddc", "sdrg_engine_get_ddc",
+    "sdrg_engine_ddc_reset", "sdrg_engine_ddc_max_out", "sdrg_engine_ddc_device", "sdrg_engine_ddc_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -173,6 +176,12 @@ class PeaksConfig(ctypes.Structure):
     """sdrg_peaks_config: the peak table stage's span, table size, spacing and threshold (include/sdrg.h)."""
     _fields_ = [("span", ctypes.c_int32), ("first_bin", ctypes.c_int32), ("n_bins", ctypes.c_int32),
                 ("max_peaks", ctypes.c_int32), ("min_separation", ctypes.c_int32), ("threshold_db", ctypes.c_float)]
+
+
+class DdcConfig(ctypes.Structure):
+    """sdrg_ddc_config: the DDC stage's channel offset, low-pass cutoff, decimation and tap count (include/sdrg.h)."""
+    _fields_ = [("offset_hz", ctypes.c_double), ("cutoff_hz", ctypes.c_double), ("decimation", ctypes.c_int32),
+                ("taps", ctypes.c_int32)]
 
 
 class _Timings(ctypes.Structure):
@@ -348,6 +357,16 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_peaks_device": (_I32, [P, P, P, P]),
         "sdrg_engine_peaks_host": (_I32, [P, P, P, P]),
         "sdrg_engine_peaks_integrated_host": (_I32, [P, P, P]),
+        "sdrg_ddc_design": (_I32, [_I64, ctypes.POINTER(DdcConfig), P]),
+        "sdrg_nco_tables": (_I32, [P]),
+        "sdrg_ddc_tile_outputs": (_I32, [_I32, _I32, ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_ddc": (_I32, [P, ctypes.POINTER(DdcConfig)]),
+        "sdrg_engine_get_ddc": (_I32, [P, ctypes.POINTER(DdcConfig), ctypes.POINTER(ctypes.c_uint32),
+                                       ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_ddc_reset": (_I32, [P]),
+        "sdrg_engine_ddc_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_ddc_device": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_ddc_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -508,6 +527,29 @@ def bin_offset_hz(n: int, sample_rate: int, bin: int) -> float:
     out = ctypes.c_double()
     _check(load().sdrg_bin_offset_hz(n, sample_rate, bin, ctypes.byref(out)), "bin_offset_hz")
     return out.value
+
+
+def ddc_design(sample_rate: int, offset_hz: float = 0.0, cutoff_hz: float = 0.0, decimation: int = 1,
+               taps: int = 1) -> np.ndarray:
+    """The DDC stage's taps for a configuration at sample_rate (host-side, no device): float32 [taps]."""
+    c = DdcConfig(offset_hz, cutoff_hz, decimation, taps)
+    h = np.zeros(max(int(taps), 1) if 0 < int(taps) <= DDC_MAX_TAPS else 1, np.float32)
+    _check(load().sdrg_ddc_design(sample_rate, ctypes.byref(c), h.ctypes.data_as(ctypes.c_void_p)), "ddc_design")
+    return h
+
+
+def nco_tables() -> np.ndarray:
+    """The NCO's phasor tables (host-side): float32 [2][1024][2], hi then lo, {re, im}."""
+    tab = np.zeros((2, 1024, 2), np.float32)
+    _check(load().sdrg_nco_tables(tab.ctypes.data_as(ctypes.c_void_p)), "nco_tables")
+    return tab
+
+
+def ddc_tile_outputs(decimation: int, taps: int) -> int:
+    """Consecutive outputs per workgroup of the DDC kernel for (decimation, taps)."""
+    t = _I32()
+    _check(load().sdrg_ddc_tile_outputs(decimation, taps, ctypes.byref(t)), "ddc_tile_outputs")
+    return t.value
 
 
 def ssb_design(samp_count: int, sample_rate: int, sound_mode: int = 1) -> dict:
@@ -841,6 +883,58 @@ class Engine:
         _check(load().sdrg_engine_peaks_integrated_host(self._h, pk.ctypes.data_as(ctypes.c_void_p),
                                                         sm.ctypes.data_as(ctypes.c_void_p)), "peaks_integrated_host")
         return pk, sm
+
+    # ---- DDC stage -------------------------------------------------------------------------------
+    def set_ddc(self, **fields) -> None:
+        """sdrg_engine_set_ddc: offset_hz, cutoff_hz, decimation, taps (fields left out are 0); set_ddc(off=True)
+        switches the stage off."""
+        if fields.pop("off", False):
+            if fields:
+                raise TypeError("off=True takes no other field")
+            _check(load().sdrg_engine_set_ddc(self._h, None), "set_ddc")
+            return
+        c = DdcConfig()
+        for k, v in fields.items():
+            if k not in dict(DdcConfig._fields_):
+                raise TypeError(f"unknown ddc field {k!r}")
+            setattr(c, k, v)
+        _check(load().sdrg_engine_set_ddc(self._h, ctypes.byref(c)), "set_ddc")
+
+    def ddc_config(self) -> dict:
+        """The configuration in force, plus nco_increment (at the current sample rate) and samples_consumed."""
+        c, inc, g0 = DdcConfig(), ctypes.c_uint32(), ctypes.c_uint64()
+        _check(load().sdrg_engine_get_ddc(self._h, ctypes.byref(c), ctypes.byref(inc), ctypes.byref(g0)), "get_ddc")
+        d = {k: getattr(c, k) for k, _ in DdcConfig._fields_}
+        d.update(nco_increment=inc.value, samples_consumed=g0.value)
+        return d
+
+    def ddc_reset(self) -> None:
+        _check(load().sdrg_engine_ddc_reset(self._h), "ddc_reset")
+
+    def ddc_max_out(self) -> int:
+        """ceil(samplesPerReading / decimation): the row length of a ddc call's output, in complex samples."""
+        cap = _I32()
+        _check(load().sdrg_engine_ddc_max_out(self._h, ctypes.byref(cap)), "ddc_max_out")
+        return cap.value
+
+    def ddc_device(self, iq_ptr: int, fmt: int, out_ptr: int) -> int:
+        """Device path: iq [n_streams][N] raw samples in, out [n_streams][ddc_max_out()] complex64 out; asynchronous
+        on the main stream.  Returns n_out, the outputs this call produced per stream (the rest of a row is zero)."""
+        n_out = _I32()
+        _check(load().sdrg_engine_ddc_device(self._h, iq_ptr, fmt, out_ptr, ctypes.byref(n_out)), "ddc_device")
+        return n_out.value
+
+    def ddc(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
+        """Host path: iq is [n_streams][samplesPerReading * 2] raw samples; returns complex64 [n_streams][n_out]."""
+        n = self.cfg.samplesPerReading
+        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
+        if iq.size != self.n_streams * n * 2:
+            raise SdrgError(f"iq has {iq.size} values, expected {self.n_streams}x{n}x2")
+        out = np.empty((self.n_streams, self.ddc_max_out()), np.complex64)
+        n_out = _I32()
+        _check(load().sdrg_engine_ddc_host(self._h, iq.ctypes.data_as(ctypes.c_void_p), fmt,
+                                           out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_out)), "ddc_host")
+        return out[:, :n_out.value]
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
                        pcm_ptr: int | None, now_ms: int = 0) -> None:
