@@ -712,6 +712,100 @@ int32_t sdrg_engine_ddc_device(sdrg_engine *eng, const void *iq, int32_t fmt, vo
 /* Host buffers, synchronous. */
 int32_t sdrg_engine_ddc_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the demodulator stage.  Per stream, the n CF32 channel samples of a call
+ * (the DDC's out, or any [n_streams][max_in][2] float rows in device memory) become audio at channel_rate / R: detector
+ * (AM envelope or FM phase step), DC block, de-emphasis, a T2-tap real FIR decimating by R, gain, and int16 PCM or
+ * float.  Over the whole life of a stream (the calls' samples concatenated, whatever their lengths) the result is that
+ * of one call; each call writes the outputs its samples complete.  All arithmetic is float, every product, sum,
+ * quotient and root rounded on its own, unless "double" is stated; denormals are kept.  A non-finite input sample makes
+ * that stream's output unspecified from then on (the recurrences and the history carry it).  fc = channel_rate_hz.
+ *   config     mode SDRG_DEMOD_AM or SDRG_DEMOD_FM; fc > 0, finite; deviation_hz > 0 and finite with (float) kf finite
+ *              (FM only, ignored for AM); dc_cutoff_hz >= 0, finite (0: no DC block); deemphasis_us >= 0, finite (0: no
+ *              de-emphasis); audio_decimation R in [1, SDRG_DEMOD_MAX_DECIMATION]; audio_taps T2 odd in
+ *              [1, SDRG_DEMOD_MAX_TAPS]; 0 < audio_cutoff_hz <= fc / 2; gain finite; out_format SDRG_DEMOD_OUT_S16 or
+ *              SDRG_DEMOD_OUT_F32; max_in in [1, 2^20]: the row length of the input in complex samples, every call's
+ *              n <= max_in.  A rejected set_demod leaves the previous configuration and state in force; an accepted one,
+ *              and sdrg_engine_demod_reset, restart every stream: g = 0 and every state +0.
+ *   design     sdrg_demod_design, in double, each result then rounded to float: kf = fc / (2 pi deviation_hz) (FM; +0 for
+ *              AM); alpha = 1 - exp(-2 pi dc_cutoff_hz / fc); a = 1 - exp(-1 / (fc deemphasis_us 1e-6)), +0 when
+ *              deemphasis_us is 0; the taps are the formula of sdrg_ddc_design with f = audio_cutoff_hz / fc, T = T2.
+ *   detector   sample i of the call has the global index g + i; z = (zr, zi) is the sample, w = (wr, wi) the stream's
+ *              previous sample (the last one of the previous call at i = 0).
+ *              AM: e = sqrtf(zr zr + zi zi), the root correctly rounded.
+ *              FM: pr = zr wr + zi wi; pi = zi wr - zr wi; e = sdrg_atan2f(pi, pr) * kf.  At global index 0 there is no
+ *              previous sample and e = +0 (the sign of a zero product would otherwise decide between 0 and pi).
+ *   atan2f     sdrg_atan2f(y, x): ax = |x|, ay = |y|, mx = max(ax, ay), mn = min(ax, ay); q = mx > 0 ? mn / mx : 0, the
+ *              quotient correctly rounded; s = q q; p = c7, then p = p s + c_k for k = 6 .. 0; r = p q; if ay > ax,
+ *              r = 0x1.921fb6p+0f - r; if the sign bit of x is set, r = 0x1.921fb6p+1f - r; the result is
+ *              copysignf(r, y).  c0 = 0x1.ffffecp-1f, c1 = -0x1.554ce6p-2f, c2 = 0x1.988d5p-3f, c3 = -0x1.1d09a6p-3f,
+ *              c4 = 0x1.8bc022p-4f, c5 = -0x1.cbe51p-5f, c6 = 0x1.68671ep-6f, c7 = -0x1.0bce58p-8f.  Within 3.6e-7 rad
+ *              of atan2 (about 1.5 ulp of pi).
+ *   DC block   if alpha != 0: u = e - m, then m = m + alpha u; otherwise u = e.
+ *   de-emph    if a != 0: t = u - s, then s = s + a t, and v = s; otherwise v = u.
+ *   filter     for every m with g <= m R < g + n: acc = +0.0f, then for k = 0 .. T2 - 1 in this order
+ *              acc = acc + h[k] * v[m R - k] (a rounded multiply, then a rounded add); v[j] = +0 for j < 0.
+ *              n_out = ceil((g + n) / R) - ceil(g / R), the same for every stream, 0 when the call holds no multiple
+ *              of R.  The group delay of (T2 - 1) / 2 channel samples is not compensated.
+ *   output     o = y * gain.  SDRG_DEMOD_OUT_F32 writes o; SDRG_DEMOD_OUT_S16 writes
+ *              (int16_t) rintf(fminf(fmaxf(o, -1.0f), 1.0f) * 32767.0f), ties to even.  out [n_streams][cap],
+ *              cap = ceil(max_in / R); every byte is written by every call, the entries from n_out on are zero.  n = 0 is
+ *              a valid call: no outputs, the state unchanged.  *n_out is set on the host before the call returns.
+ *   state      per stream w (2 floats), m, s and the last T2 - 1 values of v, in device memory (allocated at the first
+ *              demod call), in two halves a call reads and writes in turn; per engine g, advanced by n once the call's
+ *              launches have been issued: a failed call commits nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_DEMOD_AM 0
+#define SDRG_DEMOD_FM 1
+#define SDRG_DEMOD_OUT_S16 0
+#define SDRG_DEMOD_OUT_F32 1
+#define SDRG_DEMOD_MAX_TAPS 255
+#define SDRG_DEMOD_MAX_DECIMATION 64
+#define SDRG_DEMOD_MAX_IN 1048576
+typedef struct sdrg_demod_config {
+    double channel_rate_hz;
+    double deviation_hz;
+    double dc_cutoff_hz;
+    double deemphasis_us;
+    double audio_cutoff_hz;
+    int32_t mode;
+    int32_t audio_decimation;
+    int32_t audio_taps;
+    int32_t out_format;
+    int32_t max_in;
+    float gain;
+} sdrg_demod_config;
+
+/* Host-only, no device.  After the checks of set_demod: *kf, *alpha, *a and taps[cfg->audio_taps] of the design above;
+ * any of the four pointers may be NULL. */
+int32_t sdrg_demod_design(const sdrg_demod_config *cfg, float *kf, float *alpha, float *a, float *taps);
+/* Host-only: *tile, how many consecutive FIR outputs one workgroup computes for (R, T2) (an output index that is a
+ * multiple of it starts a new tile), and *chunk, how many samples of a stream the recurrence kernel takes per step (a
+ * sample index that is a multiple of it starts a new step): for tests that want data across every seam. */
+int32_t sdrg_demod_geometry(int32_t audio_decimation, int32_t audio_taps, int32_t *tile, int32_t *chunk);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the demodulator.  A demod call while it is off returns SDRG_E_INVALID
+ * and writes nothing. */
+int32_t sdrg_engine_set_demod(sdrg_engine *eng, const sdrg_demod_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its four design results (taps: audio_taps floats) and g, the
+ * samples every stream has consumed since the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_demod(const sdrg_engine *eng, sdrg_demod_config *cfg, float *kf, float *alpha, float *a,
+                              float *taps, uint64_t *samples_consumed);
+int32_t sdrg_engine_demod_reset(sdrg_engine *eng);
+/* cap = ceil(max_in / R): the row length of `out`, in int16 or float by out_format. */
+int32_t sdrg_engine_demod_max_out(const sdrg_engine *eng, int32_t *cap);
+/* chan [n_streams][max_in][2] float, of which the first n complex samples of every row are this call's (0 <= n <=
+ * max_in), and out [n_streams][cap] in device memory.  Reads chan only.  Stream rules and waiting as
+ * sdrg_engine_ddc_device: runs on the main stream (the caller's after sdrg_engine_set_stream); complete after
+ * sdrg_engine_synchronize, or on a stream after sdrg_engine_wait_outputs. */
+int32_t sdrg_engine_demod_device(sdrg_engine *eng, const void *chan, int32_t n, void *out, int32_t *n_out);
+/* Host buffers of the same shapes, synchronous. */
+int32_t sdrg_engine_demod_host(sdrg_engine *eng, const void *chan, int32_t n, void *out, int32_t *n_out);
+/* Tune and listen: sdrg_engine_ddc_host's iq through the DDC and the demodulator, the channel left on the device (the
+ * demodulator's n is the DDC call's n_out); only the audio rows out [n_streams][cap] come back.  SDRG_E_INVALID if
+ * either stage is off or max_in is smaller than the DDC's cap; a refused call commits nothing in either stage. */
+int32_t sdrg_engine_ddc_demod_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

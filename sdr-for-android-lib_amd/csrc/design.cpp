@@ -233,7 +233,10 @@ const char *ddc_check(uint32_t sample_rate, double offset_hz, double cutoff_hz, 
 
 // The DDC stage's low-pass (sdrg.h): a Hann-windowed sinc of `taps` (odd) coefficients with unit DC gain, in double
 void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h) {
-    const double f = cutoff_hz / (double)sample_rate;
+    lowpass_design(cutoff_hz / (double)sample_rate, taps, h);
+}
+
+void lowpass_design(double f, int taps, float *h) {
     double v[511];
     double sum = 0.0;
     for (int k = 0; k < taps; k++) {
@@ -244,6 +247,38 @@ void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h) {
         sum += v[k];
     }
     for (int k = 0; k < taps; k++) h[k] = (float)(v[k] / sum);
+}
+
+// The demodulator stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *demod_check(const sdrg_demod_config &c) {
+    if (c.mode != SDRG_DEMOD_AM && c.mode != SDRG_DEMOD_FM) return "mode must be SDRG_DEMOD_AM or SDRG_DEMOD_FM";
+    if (!(c.channel_rate_hz > 0.0) || !std::isfinite(c.channel_rate_hz)) return "channel_rate_hz must be > 0 and finite";
+    if (c.mode == SDRG_DEMOD_FM) {
+        if (!(c.deviation_hz > 0.0) || !std::isfinite(c.deviation_hz)) return "deviation_hz must be > 0 and finite";
+        if (!std::isfinite((float)(c.channel_rate_hz / (2.0 * M_PI * c.deviation_hz))))
+            return "channel_rate_hz / (2 pi deviation_hz) is not a finite float";
+    }
+    if (!(c.dc_cutoff_hz >= 0.0) || !std::isfinite(c.dc_cutoff_hz)) return "dc_cutoff_hz must be >= 0 and finite";
+    if (!(c.deemphasis_us >= 0.0) || !std::isfinite(c.deemphasis_us)) return "deemphasis_us must be >= 0 and finite";
+    if (c.audio_decimation < 1 || c.audio_decimation > SDRG_DEMOD_MAX_DECIMATION) return "audio_decimation outside [1, 64]";
+    if (c.audio_taps < 1 || c.audio_taps > SDRG_DEMOD_MAX_TAPS || (c.audio_taps & 1) == 0)
+        return "audio_taps must be odd and in [1, 255]";
+    if (!(c.audio_cutoff_hz > 0.0 && c.audio_cutoff_hz <= c.channel_rate_hz / 2.0))
+        return "audio_cutoff_hz outside (0, channel_rate_hz / 2]";
+    if (!std::isfinite(c.gain)) return "gain must be finite";
+    if (c.out_format != SDRG_DEMOD_OUT_S16 && c.out_format != SDRG_DEMOD_OUT_F32)
+        return "out_format must be SDRG_DEMOD_OUT_S16 or SDRG_DEMOD_OUT_F32";
+    if (c.max_in < 1 || c.max_in > SDRG_DEMOD_MAX_IN) return "max_in outside [1, 2^20]";
+    return nullptr;
+}
+
+// The demodulator stage's constants (sdrg.h), in double, each rounded to float once
+void demod_design(const sdrg_demod_config &c, float *kf, float *alpha, float *a, float *h) {
+    const double fc = c.channel_rate_hz;
+    if (kf) *kf = c.mode == SDRG_DEMOD_FM ? (float)(fc / (2.0 * M_PI * c.deviation_hz)) : 0.0f;
+    if (alpha) *alpha = (float)(1.0 - std::exp(-2.0 * M_PI * c.dc_cutoff_hz / fc));
+    if (a) *a = c.deemphasis_us > 0.0 ? (float)(1.0 - std::exp(-1.0 / (fc * c.deemphasis_us * 1e-6))) : 0.0f;
+    if (h) lowpass_design(c.audio_cutoff_hz / fc, c.audio_taps, h);
 }
 
 }  // namespace sdrg

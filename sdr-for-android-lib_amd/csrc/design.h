@@ -19,6 +19,11 @@ void nco_tables(float *tab);  // [2][1024][2] floats
 // DDC stage: the configuration rules (nullptr = valid) and the Hann-sinc low-pass of unit DC gain
 const char *ddc_check(uint32_t sample_rate, double offset_hz, double cutoff_hz, int decimation, int taps);
 void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h);
+// the same low-pass at the relative cutoff f = cutoff / rate (cycles per sample)
+void lowpass_design(double f, int taps, float *h);
+// Demodulator stage: the configuration rules (nullptr = valid) and kf, alpha, a and the taps (any pointer may be null)
+const char *demod_check(const sdrg_demod_config &cfg);
+void demod_design(const sdrg_demod_config &cfg, float *kf, float *alpha, float *a, float *h);
 // AudioPulseDetector::makeLP2 / makeHP2 (audio_pulse_detector.cpp:29-55), Q = 0.7071: {b0, b1, b2, a1, a2}
 void design_pulse_sos(float fs, float fc, bool highpass, float c[5]);
 StatsGeometry stats_geometry(uint32_t sample_rate, uint32_t center_frequency, int n, int focus_khz);

@@ -320,6 +320,22 @@ struct sdrg_engine {
     size_t ddc_in_bytes = 0;
     float *d_ddc_out = nullptr;  // ddc_host's rows
     size_t ddc_out_elems = 0;
+    // demodulator stage (sdrg_engine_set_demod / demod_device / demod_host / ddc_demod_host; demod.hip)
+    sdrg_demod_config demod{};
+    bool demod_set = false;
+    uint64_t demod_g = 0;        // samples every stream has consumed since the last restart
+    bool demod_fresh = true;     // the next call starts from a state of zeros
+    int demod_half = 0;          // the half of d_demod_state the next call reads
+    float demod_kf = 0.0f, demod_alpha = 0.0f, demod_a = 0.0f;  // demod_design of `demod`
+    DemodTaps demod_taps{};
+    float *d_demod_state = nullptr;  // [2]{[n_streams][4]: wr, wi, m, s; [n_streams][T2 - 1]: v}, ping-pong
+    size_t demod_state_elems = 0;
+    float *d_demod_scratch = nullptr;  // [n_streams][max_in]: e, then v, of the call in flight
+    size_t demod_scratch_elems = 0;
+    float *d_demod_in = nullptr;   // demod_host's copy of the caller's rows
+    size_t demod_in_elems = 0;
+    char *d_demod_out = nullptr;   // demod_host's and ddc_demod_host's audio rows
+    size_t demod_out_bytes = 0;
 };
 
 namespace {
@@ -1071,7 +1087,8 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
                     e->d_spec_scratch, e->d_fft_scratch, e->d_pool, e->d_rec_scratch, e->d_iq_stage, e->d_spec_stage,
                     e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->d_disp_in, e->d_disp_out,
                     e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out, e->d_peaks_in, e->d_peaks_out, e->d_ddc_hist,
-                    e->d_ddc_w, e->d_ddc_in, e->d_ddc_out};
+                    e->d_ddc_w, e->d_ddc_in, e->d_ddc_out, e->d_demod_state, e->d_demod_scratch, e->d_demod_in,
+                    e->d_demod_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
@@ -2085,6 +2102,200 @@ int32_t sdrg_engine_ddc_host(sdrg_engine *e, const void *iq, int32_t fmt, void *
     HIP_TRY(hipMemcpyAsync(out, e->d_ddc_out, sizeof(float) * out_elems, hipMemcpyDeviceToHost, e->s_main));
     HIP_TRY(hipStreamSynchronize(e->s_main));
     *n_out = c.n_out;
+    return SDRG_OK;
+}
+
+// ---- demodulator stage (demod.hip) --------------------------------------------------------------------------------
+
+int32_t sdrg_demod_design(const sdrg_demod_config *cfg, float *kf, float *alpha, float *a, float *taps) {
+    if (!cfg) return fail(SDRG_E_INVALID, "null demod config");
+    if (const char *bad = demod_check(*cfg)) return fail(SDRG_E_INVALID, "demod: %s", bad);
+    demod_design(*cfg, kf, alpha, a, taps);
+    return SDRG_OK;
+}
+
+int32_t sdrg_demod_geometry(int32_t audio_decimation, int32_t audio_taps, int32_t *tile, int32_t *chunk) {
+    if (!tile || !chunk) return fail(SDRG_E_INVALID, "null tile or chunk");
+    if (audio_decimation < 1 || audio_decimation > SDRG_DEMOD_MAX_DECIMATION || audio_taps < 1 ||
+        audio_taps > SDRG_DEMOD_MAX_TAPS || (audio_taps & 1) == 0)
+        return fail(SDRG_E_INVALID, "demod: audio_decimation outside [1, 64] or audio_taps not odd in [1, 255]");
+    *tile = demod_tile_outputs(audio_decimation, audio_taps);
+    *chunk = DEMOD_CHUNK;
+    return SDRG_OK;
+}
+
+static void demod_restart(sdrg_engine *e) {
+    e->demod_g = 0;
+    e->demod_fresh = true;
+}
+
+int32_t sdrg_engine_set_demod(sdrg_engine *e, const sdrg_demod_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (cfg) {
+        if (const char *bad = demod_check(*cfg)) return fail(SDRG_E_INVALID, "demod: %s", bad);
+        e->demod = *cfg;
+        demod_design(*cfg, &e->demod_kf, &e->demod_alpha, &e->demod_a, e->demod_taps.h);
+    }
+    e->demod_set = cfg != nullptr;
+    demod_restart(e);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_demod(const sdrg_engine *e, sdrg_demod_config *cfg, float *kf, float *alpha, float *a,
+                              float *taps, uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set");
+    if (cfg) *cfg = e->demod;
+    if (kf) *kf = e->demod_kf;
+    if (alpha) *alpha = e->demod_alpha;
+    if (a) *a = e->demod_a;
+    if (taps) std::copy(e->demod_taps.h, e->demod_taps.h + e->demod.audio_taps, taps);
+    if (samples_consumed) *samples_consumed = e->demod_g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_demod_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    demod_restart(e);
+    return SDRG_OK;
+}
+
+static int demod_cap(const sdrg_engine *e) {
+    return (e->demod.max_in + e->demod.audio_decimation - 1) / e->demod.audio_decimation;
+}
+
+int32_t sdrg_engine_demod_max_out(const sdrg_engine *e, int32_t *cap) {
+    if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
+    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set (sdrg_engine_set_demod)");
+    *cap = demod_cap(e);
+    return SDRG_OK;
+}
+
+// the checks of one demod call, and its n_out, before anything is touched
+static int32_t demod_resolve(const sdrg_engine *e, int32_t n, int32_t *n_out) {
+    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set (sdrg_engine_set_demod)");
+    if (n < 0 || n > e->demod.max_in) return fail(SDRG_E_INVALID, "demod: n %d outside [0, max_in = %d]", n, e->demod.max_in);
+    const uint64_t g = e->demod_g, R = (uint64_t)e->demod.audio_decimation;
+    *n_out = (int32_t)((g + (uint64_t)n + R - 1) / R - (g + R - 1) / R);
+    return SDRG_OK;
+}
+
+static size_t demod_out_size(const sdrg_engine *e) {
+    return (size_t)e->n_streams * (size_t)demod_cap(e) *
+           (e->demod.out_format == SDRG_DEMOD_OUT_F32 ? sizeof(float) : sizeof(int16_t));
+}
+
+// one demod call on the main stream: chan (rows of in_stride complex samples), out in device memory
+static int32_t demod_enqueue(sdrg_engine *e, const float *chan, int in_stride, int n, int n_out, void *out) {
+    const sdrg_demod_config &cfg = e->demod;
+    const int T = cfg.audio_taps, R = cfg.audio_decimation;
+    const size_t B = (size_t)e->n_streams, half = B * 4 + B * (size_t)(T - 1);
+    // only another configuration asks for more, and set_demod restarted the streams: nothing to keep
+    int32_t rc = ensure_device(&e->d_demod_state, &e->demod_state_elems, 2 * half);
+    if (rc) return rc;
+    rc = ensure_device(&e->d_demod_scratch, &e->demod_scratch_elems, B * (size_t)cfg.max_in);
+    if (rc) return rc;
+    float *old_half = e->d_demod_state + (size_t)e->demod_half * half;
+    float *new_half = e->d_demod_state + (size_t)(e->demod_half ^ 1) * half;
+    DemodParams p{};
+    p.n = n;
+    p.in_stride = in_stride;
+    p.scratch_stride = cfg.max_in;
+    p.decim = R;
+    p.taps = T;
+    p.first = (int)(((uint64_t)R - e->demod_g % (uint64_t)R) % (uint64_t)R);
+    p.n_out = n_out;
+    p.cap = demod_cap(e);
+    p.mode = cfg.mode;
+    p.out_format = cfg.out_format;
+    p.fresh = e->demod_fresh ? 1 : 0;
+    p.kf = e->demod_kf;
+    p.alpha = e->demod_alpha;
+    p.a = e->demod_a;
+    p.gain = cfg.gain;
+    p.state_old = old_half;
+    p.hist_old = old_half + B * 4;
+    p.state_new = new_half;
+    p.hist_new = new_half + B * 4;
+    p.scratch = e->d_demod_scratch;
+    HIP_TRY(launch_demod(chan, e->n_streams, p, e->demod_taps, out, e->s_main));
+    if (n > 0) {  // a call without samples wrote out only: the state stays where it is
+        e->demod_g += (uint64_t)n;
+        e->demod_fresh = false;
+        e->demod_half ^= 1;
+    }
+    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers out as it covers display rows
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_demod_device(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!chan || !out || !n_out) return fail(SDRG_E_INVALID, "null chan, out or n_out");
+    int32_t count;
+    int32_t rc = demod_resolve(e, n, &count);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    rc = demod_enqueue(e, static_cast<const float *>(chan), e->demod.max_in, n, count, out);
+    if (rc) return rc;
+    *n_out = count;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_demod_host(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!chan || !out || !n_out) return fail(SDRG_E_INVALID, "null chan, out or n_out");
+    int32_t count;
+    int32_t rc = demod_resolve(e, n, &count);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const size_t in_elems = (size_t)e->n_streams * (size_t)e->demod.max_in * 2, out_bytes = demod_out_size(e);
+    rc = ensure_device(&e->d_demod_in, &e->demod_in_elems, in_elems);
+    if (rc) return rc;
+    rc = ensure_device(&e->d_demod_out, &e->demod_out_bytes, out_bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_demod_in, chan, sizeof(float) * in_elems, hipMemcpyHostToDevice, e->s_main));
+    rc = demod_enqueue(e, e->d_demod_in, e->demod.max_in, n, count, e->d_demod_out);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->d_demod_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
+    *n_out = count;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set (sdrg_engine_set_demod)");
+    DdcCall c;
+    int32_t rc = ddc_resolve(e, fmt, &c);
+    if (rc) return rc;
+    if (e->demod.max_in < c.cap)
+        return fail(SDRG_E_INVALID, "demod max_in %d smaller than the ddc's row length %d", e->demod.max_in, c.cap);
+    int32_t count;
+    rc = demod_resolve(e, c.n_out, &count);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const size_t in_bytes = (size_t)e->n_streams * (size_t)c.n * (size_t)bytes_per_sample(fmt);
+    const size_t chan_elems = (size_t)e->n_streams * (size_t)c.cap * 2, out_bytes = demod_out_size(e);
+    char *in = static_cast<char *>(e->d_ddc_in);
+    rc = ensure_device(&in, &e->ddc_in_bytes, in_bytes);
+    e->d_ddc_in = in;
+    if (rc) return rc;
+    rc = ensure_device(&e->d_ddc_out, &e->ddc_out_elems, chan_elems);
+    if (rc) return rc;
+    rc = ensure_device(&e->d_demod_out, &e->demod_out_bytes, out_bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_ddc_in, iq, in_bytes, hipMemcpyHostToDevice, e->s_main));
+    rc = ddc_enqueue(e, c, e->d_ddc_in, fmt, e->d_ddc_out);
+    if (rc) return rc;
+    rc = demod_enqueue(e, e->d_ddc_out, c.cap, c.n_out, count, e->d_demod_out);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->d_demod_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
+    *n_out = count;
     return SDRG_OK;
 }
 

@@ -187,4 +187,28 @@ int ddc_tile_outputs(int decim, int taps);  // outputs per workgroup
 hipError_t launch_ddc(const void *iq, int fmt, int n_streams, const DdcParams &p, const DdcTaps &taps, float *out,
                       hipStream_t stream);
 
+// Demodulator stage (demod.hip): per stream the n complex samples at chan + stream * in_stride (float2) through the
+// detector (mode, kf; the previous sample from state_old), the DC block and the de-emphasis (alpha, a; m and s from
+// state_old) in `scratch` [n_streams][scratch_stride] floats, then out[j] = gain * sum_k h[k] v[first + j decim - k],
+// j in [0, n_out), v at indices below 0 from hist_old [n_streams][taps - 1].  Writes out [n_streams][cap] whole (zeros
+// from n_out on, int16 or float by out_format), {wr, wi, m, s} per stream to state_new and the last taps - 1 values of
+// v to hist_new.  fresh: no previous sample, and state_old / hist_old read as zeros.  n = 0 writes out only.  tile, row
+// and n_tiles are the launcher's.
+struct DemodParams {
+    int n, in_stride, scratch_stride, decim, taps, first, n_out, cap;
+    int mode, out_format, fresh;
+    float kf, alpha, a, gain;
+    const float *state_old, *hist_old;
+    float *state_new, *hist_new;
+    float *scratch;
+    int tile, row, n_tiles;
+};
+struct DemodTaps {
+    float h[SDRG_DEMOD_MAX_TAPS];
+};
+constexpr int DEMOD_CHUNK = 64;                // samples of a stream per step of the recurrence kernel
+int demod_tile_outputs(int decim, int taps);  // FIR outputs per workgroup
+hipError_t launch_demod(const float *chan, int n_streams, const DemodParams &p, const DemodTaps &taps, void *out,
+                        hipStream_t stream);
+
 }  // namespace sdrg

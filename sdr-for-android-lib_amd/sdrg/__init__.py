@@ -39,6 +39,10 @@ INTEGRATE_MEAN, INTEGRATE_MAX, INTEGRATE_EMA = 0, 1, 2              # sdrg_integ
 INTEGRATE_MAX_PERIOD = 64
 PEAKS_MAX, PEAKS_MAX_SEPARATION = 64, 4096                          # SDRG_PEAKS_MAX, SDRG_PEAKS_MAX_SEPARATION
 DDC_MAX_TAPS, DDC_MAX_DECIMATION = 511, 512                         # SDRG_DDC_MAX_TAPS, SDRG_DDC_MAX_DECIMATION
+DEMOD_AM, DEMOD_FM = 0, 1                                           # SDRG_DEMOD_AM, SDRG_DEMOD_FM
+DEMOD_OUT_S16, DEMOD_OUT_F32 = 0, 1                                 # SDRG_DEMOD_OUT_*
+DEMOD_MAX_TAPS, DEMOD_MAX_DECIMATION, DEMOD_MAX_IN = 255, 64, 1 << 20  # SDRG_DEMOD_MAX_*
+DEMOD_OUT_DTYPE = {DEMOD_OUT_S16: np.int16, DEMOD_OUT_F32: np.float32}
 STATUS = {0: "SDRG_OK", -1: "SDRG_E_INVALID", -2: "SDRG_E_UNSUPPORTED", -3: "SDRG_E_NOMEM", -4: "SDRG_E_HIP",
           -5: "SDRG_E_NODEVICE"}
 BYTES_PER_SAMPLE = {CF32: 8, CS8: 2, CU8: 2, CS16: 4}
@@ -121,6 +125,9 @@ EXPORTS = [
     "sdrg_engine_peaks_host", "sdrg_engine_peaks_integrated_host",
     "sdrg_ddc_design", "sdrg_nco_tables", "sdrg_ddc_tile_outputs", "sdrg_engine_set_ddc", "sdrg_engine_get_ddc",
     "sdrg_engine_ddc_reset", "sdrg_engine_ddc_max_out", "sdrg_engine_ddc_device", "sdrg_engine_ddc_host",
+    "sdrg_demod_design", "sdrg_demod_geometry", "sdrg_engine_set_demod", "sdrg_engine_get_demod",
+    "sdrg_engine_demod_reset", "sdrg_engine_demod_max_out", "sdrg_engine_demod_device", "sdrg_engine_demod_host",
+    "sdrg_engine_ddc_demod_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -182,6 +189,25 @@ class DdcConfig(ctypes.Structure):
     """sdrg_ddc_config: the DDC stage's channel offset, low-pass cutoff, decimation and tap count (include/sdrg.h)."""
     _fields_ = [("offset_hz", ctypes.c_double), ("cutoff_hz", ctypes.c_double), ("decimation", ctypes.c_int32),
                 ("taps", ctypes.c_int32)]
+
+
+class DemodConfig(ctypes.Structure):
+    """sdrg_demod_config: the demodulator stage's mode, rates, filters, gain, output format and row length
+    (include/sdrg.h)."""
+    _fields_ = [("channel_rate_hz", ctypes.c_double), ("deviation_hz", ctypes.c_double),
+                ("dc_cutoff_hz", ctypes.c_double), ("deemphasis_us", ctypes.c_double),
+                ("audio_cutoff_hz", ctypes.c_double), ("mode", ctypes.c_int32), ("audio_decimation", ctypes.c_int32),
+                ("audio_taps", ctypes.c_int32), ("out_format", ctypes.c_int32), ("max_in", ctypes.c_int32),
+                ("gain", ctypes.c_float)]
+
+
+def _demod_config(fields: dict) -> DemodConfig:
+    c = DemodConfig()
+    for k, v in fields.items():
+        if k not in dict(DemodConfig._fields_):
+            raise TypeError(f"unknown demod field {k!r}")
+        setattr(c, k, v)
+    return c
 
 
 class _Timings(ctypes.Structure):
@@ -367,6 +393,17 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_ddc_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
         "sdrg_engine_ddc_device": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_ddc_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_demod_design": (_I32, [ctypes.POINTER(DemodConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
+                                     ctypes.POINTER(_F), P]),
+        "sdrg_demod_geometry": (_I32, [_I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_demod": (_I32, [P, ctypes.POINTER(DemodConfig)]),
+        "sdrg_engine_get_demod": (_I32, [P, ctypes.POINTER(DemodConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
+                                         ctypes.POINTER(_F), P, ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_demod_reset": (_I32, [P]),
+        "sdrg_engine_demod_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_demod_device": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_demod_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_ddc_demod_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -550,6 +587,25 @@ def ddc_tile_outputs(decimation: int, taps: int) -> int:
     t = _I32()
     _check(load().sdrg_ddc_tile_outputs(decimation, taps, ctypes.byref(t)), "ddc_tile_outputs")
     return t.value
+
+
+def demod_design(**fields) -> dict:
+    """The demodulator stage's design for a configuration (host-side, no device): kf, alpha, a as np.float32 and
+    taps float32 [audio_taps].  The fields are sdrg_demod_config's (fields left out are 0)."""
+    c = _demod_config(fields)
+    kf, alpha, a = _F(), _F(), _F()
+    h = np.zeros(c.audio_taps if 0 < c.audio_taps <= DEMOD_MAX_TAPS else 1, np.float32)
+    _check(load().sdrg_demod_design(ctypes.byref(c), ctypes.byref(kf), ctypes.byref(alpha), ctypes.byref(a),
+                                    h.ctypes.data_as(ctypes.c_void_p)), "demod_design")
+    return {"kf": np.float32(kf.value), "alpha": np.float32(alpha.value), "a": np.float32(a.value), "taps": h}
+
+
+def demod_geometry(audio_decimation: int, audio_taps: int) -> tuple:
+    """(tile, chunk): FIR outputs per workgroup for (R, T2), and samples per step of the recurrence kernel."""
+    tile, chunk = _I32(), _I32()
+    _check(load().sdrg_demod_geometry(audio_decimation, audio_taps, ctypes.byref(tile), ctypes.byref(chunk)),
+           "demod_geometry")
+    return tile.value, chunk.value
 
 
 def ssb_design(samp_count: int, sample_rate: int, sound_mode: int = 1) -> dict:
@@ -934,6 +990,78 @@ class Engine:
         n_out = _I32()
         _check(load().sdrg_engine_ddc_host(self._h, iq.ctypes.data_as(ctypes.c_void_p), fmt,
                                            out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_out)), "ddc_host")
+        return out[:, :n_out.value]
+
+    # ---- demodulator stage -----------------------------------------------------------------------
+    def set_demod(self, **fields) -> None:
+        """sdrg_engine_set_demod: the fields of sdrg_demod_config (fields left out are 0); set_demod(off=True) switches
+        the stage off."""
+        if fields.pop("off", False):
+            if fields:
+                raise TypeError("off=True takes no other field")
+            _check(load().sdrg_engine_set_demod(self._h, None), "set_demod")
+            return
+        c = _demod_config(fields)
+        _check(load().sdrg_engine_set_demod(self._h, ctypes.byref(c)), "set_demod")
+
+    def demod_config(self) -> dict:
+        """The configuration in force, plus its design (kf, alpha, a as np.float32, taps) and samples_consumed."""
+        c, kf, alpha, a, g = DemodConfig(), _F(), _F(), _F(), ctypes.c_uint64()
+        h = np.zeros(DEMOD_MAX_TAPS, np.float32)
+        _check(load().sdrg_engine_get_demod(self._h, ctypes.byref(c), ctypes.byref(kf), ctypes.byref(alpha),
+                                            ctypes.byref(a), h.ctypes.data_as(ctypes.c_void_p), ctypes.byref(g)),
+               "get_demod")
+        d = {k: getattr(c, k) for k, _ in DemodConfig._fields_}
+        d.update(kf=np.float32(kf.value), alpha=np.float32(alpha.value), a=np.float32(a.value),
+                 taps=h[:c.audio_taps].copy(), samples_consumed=g.value)
+        return d
+
+    def demod_reset(self) -> None:
+        _check(load().sdrg_engine_demod_reset(self._h), "demod_reset")
+
+    def demod_max_out(self) -> int:
+        """ceil(max_in / audio_decimation): the row length of a demod call's output."""
+        cap = _I32()
+        _check(load().sdrg_engine_demod_max_out(self._h, ctypes.byref(cap)), "demod_max_out")
+        return cap.value
+
+    def demod_device(self, chan_ptr: int, n: int, out_ptr: int) -> int:
+        """Device path: chan [n_streams][max_in] complex64 in (the first n of every row are the call's), out
+        [n_streams][demod_max_out()] int16 or float32 out; asynchronous on the main stream.  Returns n_out."""
+        n_out = _I32()
+        _check(load().sdrg_engine_demod_device(self._h, chan_ptr, n, out_ptr, ctypes.byref(n_out)), "demod_device")
+        return n_out.value
+
+    def _demod_out(self) -> np.ndarray:
+        fmt = self.demod_config()["out_format"]
+        return np.empty((self.n_streams, self.demod_max_out()), DEMOD_OUT_DTYPE[fmt])
+
+    def demod(self, chan: np.ndarray) -> np.ndarray:
+        """Host path: chan is complex64 [n_streams][n], n <= max_in; returns int16 or float32 [n_streams][n_out]."""
+        chan = np.asarray(chan, np.complex64).reshape(self.n_streams, -1)
+        n, max_in = chan.shape[1], self.demod_config()["max_in"]
+        if n > max_in:
+            raise SdrgError(f"chan has {n} samples per stream, max_in is {max_in}")
+        rows = np.zeros((self.n_streams, max_in), np.complex64)
+        rows[:, :n] = chan
+        out = self._demod_out()
+        n_out = _I32()
+        _check(load().sdrg_engine_demod_host(self._h, rows.ctypes.data_as(ctypes.c_void_p), n,
+                                             out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_out)), "demod_host")
+        return out[:, :n_out.value]
+
+    def ddc_demod(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
+        """Tune and listen: iq [n_streams][samplesPerReading * 2] raw samples through the DDC and the demodulator, the
+        channel left on the device; returns the audio, int16 or float32 [n_streams][n_out]."""
+        n = self.cfg.samplesPerReading
+        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
+        if iq.size != self.n_streams * n * 2:
+            raise SdrgError(f"iq has {iq.size} values, expected {self.n_streams}x{n}x2")
+        out = self._demod_out()
+        n_out = _I32()
+        _check(load().sdrg_engine_ddc_demod_host(self._h, iq.ctypes.data_as(ctypes.c_void_p), fmt,
+                                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_out)),
+               "ddc_demod_host")
         return out[:, :n_out.value]
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
