@@ -806,6 +806,87 @@ int32_t sdrg_engine_demod_host(sdrg_engine *eng, const void *chan, int32_t n, vo
  * either stage is off or max_in is smaller than the DDC's cap; a refused call commits nothing in either stage. */
 int32_t sdrg_engine_ddc_demod_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the channelizer stage, a uniform polyphase filter bank.  Per stream, M
+ * channels spaced fs / M apart share one prototype low-pass of L = M P taps and come out at the rate O fs / M
+ * (D = M / O), as CF32: one read of the wideband frame for every channel of the band.  Nothing depends on the sample
+ * rate in Hz: a rate change restarts nothing, and neither does a change of samples_per_reading.  N =
+ * samples_per_reading at the call.
+ *   config     cutoff_rel, the prototype's cutoff in units of the channel spacing fs / M, 0 < cutoff_rel <= M / 2;
+ *              channels M a power of two in [2, SDRG_CHANNELIZER_MAX_CHANNELS]; taps_per_channel P in
+ *              [1, SDRG_CHANNELIZER_MAX_TAPS_PER_CHANNEL] with L = M P <= SDRG_CHANNELIZER_MAX_TAPS; oversample O 1 or
+ *              2; the rows written are [first_channel, first_channel + n_channels) of the fftshifted channel order,
+ *              n_channels >= 1, first_channel >= 0, first_channel + n_channels <= M.  A rejected set_channelizer
+ *              leaves the previous configuration and state in force; an accepted one, and
+ *              sdrg_engine_channelizer_reset, restart every stream: g0 = 0, history +0.
+ *   prototype  sdrg_channelizer_design, in double: h[0 .. L - 2] is the formula of sdrg_ddc_design with
+ *              f = cutoff_rel / M and T = L - 1 (odd), and h[L - 1] = +0.  So at cutoff_hz / fs == cutoff_rel / M the
+ *              bank's taps are sdrg_ddc_design's for T = L - 1.
+ *   unpack     the DDC's: CS8 (float)v * (1/128), CU8 ((float)v - 127.4f) * (1/128), CS16 (float)v * (1/32768), CF32
+ *              as is.
+ *   channel    c in [0, M) is centred at c fs / M (c >= M / 2: negative).  Over the whole life of a stream (the calls'
+ *              frames concatenated, whatever their lengths and formats), x[g] = +0 for g < 0, the output time m sits
+ *              at the input index m D:
+ *                u_p[m] = sum_{q = 0}^{P - 1} h[p + q M] x[m D - p - q M], p in [0, M)    (the branch sums)
+ *                Y_c[m] = sum_p u_p[m] e^{+j 2 pi c p / M}
+ *                y_c[m] = Y_c[m] at O = 1, (-1)^{c m} Y_c[m] at O = 2.
+ *              This is sum_n h[n] v_c[m D - n] with v_c[g] = x[g] e^{-j 2 pi c g / M}: the DDC at offset_hz = c fs / M
+ *              with the same taps and decimation D, in its phase convention; the group delay of (L - 2) / 2 input
+ *              samples is not compensated.
+ *   arithmetic float throughout; fused multiply-adds, any association of the sums and any FFT algorithm are allowed:
+ *              the result is specified by the bound below, not by its bytes.  With eps = 2^-24, per output and channel
+ *                |y - exact| <= (P + 2) eps sum_n |h[n]| |x[m D - n]| + 8 log2(M) eps sqrt(M) ||u[m]||_2.
+ *              Two properties hold byte for byte all the same: an output depends only on its window of L samples (and
+ *              on c and m), so a stream cut into calls anywhere gives the bytes of one call; and the same call on the
+ *              same state gives the same bytes.  After a non-finite CF32 sample a stream's output is unspecified.
+ *   output     out [n_streams][n_channels][cap][2] float, cap = ceil(N / D).  Row r is channel k = first_channel + r
+ *              of the fftshifted order, c = (k + M / 2) mod M; sdrg_bin_offset_hz(M, fs, k) is its centre's offset.
+ *              With g0 samples consumed before it, a call writes the outputs with g0 <= m D < g0 + N:
+ *              n_out = ceil((g0 + N) / D) - ceil(g0 / D) of them, the same for every stream and row.  Every byte of
+ *              out is written by every call, +0 from n_out on in every row.  *n_out is set on the host before the
+ *              call returns.  Viewed as [n_streams n_channels][cap][2], out is what an engine of that many streams
+ *              takes as sdrg_engine_demod_device input (max_in = cap, n = n_out) or as CF32 process_device input.
+ *   state      per stream the last L - 1 unpacked samples as float pairs, in device memory, in two halves a call reads
+ *              and writes in turn (allocated at the first call); per engine g0, advanced by N once the call's launch
+ *              has been issued: a failed call commits nothing.  The taps live in a device buffer written by
+ *              set_channelizer, never by a call.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_CHANNELIZER_MAX_CHANNELS 256
+#define SDRG_CHANNELIZER_MAX_TAPS_PER_CHANNEL 32
+#define SDRG_CHANNELIZER_MAX_TAPS 4096
+typedef struct sdrg_channelizer_config {
+    double cutoff_rel;
+    int32_t channels;
+    int32_t taps_per_channel;
+    int32_t oversample;
+    int32_t first_channel;
+    int32_t n_channels;
+} sdrg_channelizer_config;
+
+/* Host-only, no device.  The prototype of cfg (channels * taps_per_channel floats), after the checks of
+ * set_channelizer. */
+int32_t sdrg_channelizer_design(const sdrg_channelizer_config *cfg, float *taps);
+/* Host-only: how many consecutive output times one workgroup of the channelizer kernel computes for cfg: an output
+ * index that is a multiple of it starts a new tile (for tests that want windows across every tile seam). */
+int32_t sdrg_channelizer_tile_outputs(const sdrg_channelizer_config *cfg, int32_t *tile);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the channelizer.  A channelizer call while it is off returns
+ * SDRG_E_INVALID and writes nothing. */
+int32_t sdrg_engine_set_channelizer(sdrg_engine *eng, const sdrg_channelizer_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off) and g0, the samples every stream has consumed since the last
+ * restart; either pointer may be NULL. */
+int32_t sdrg_engine_get_channelizer(const sdrg_engine *eng, sdrg_channelizer_config *cfg, uint64_t *samples_consumed);
+int32_t sdrg_engine_channelizer_reset(sdrg_engine *eng);
+/* cap = ceil(N / D) for the current samples_per_reading: the row length of `out`, in complex samples. */
+int32_t sdrg_engine_channelizer_max_out(const sdrg_engine *eng, int32_t *cap);
+/* iq [n_streams][N] raw samples of format fmt (SDRG_IQ_*) and out [n_streams][n_channels][cap][2] float in device
+ * memory.  Reads iq only and shares nothing with sdrg_engine_process_device or the DDC.  Stream rules and waiting as
+ * sdrg_engine_ddc_device: runs on the main stream (the caller's after sdrg_engine_set_stream); complete after
+ * sdrg_engine_synchronize, or on a stream after sdrg_engine_wait_outputs. */
+int32_t sdrg_engine_channelizer_device(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
+/* Host buffers, synchronous. */
+int32_t sdrg_engine_channelizer_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

@@ -10,6 +10,8 @@
 #include <cmath>
 #include <stdint.h>
 
+#include <vector>
+
 #include "design.h"
 #include "glibc_logf.h"
 
@@ -237,7 +239,7 @@ void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h) {
 }
 
 void lowpass_design(double f, int taps, float *h) {
-    double v[511];
+    std::vector<double> v((size_t)taps);  // the channelizer's prototype has up to 4095 coefficients
     double sum = 0.0;
     for (int k = 0; k < taps; k++) {
         const int c = k - (taps - 1) / 2;
@@ -247,6 +249,26 @@ void lowpass_design(double f, int taps, float *h) {
         sum += v[k];
     }
     for (int k = 0; k < taps; k++) h[k] = (float)(v[k] / sum);
+}
+
+// The channelizer stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *chan_check(const sdrg_channelizer_config &c) {
+    const int M = c.channels, P = c.taps_per_channel;
+    if (M < 2 || M > SDRG_CHANNELIZER_MAX_CHANNELS || (M & (M - 1)) != 0) return "channels must be a power of two in [2, 256]";
+    if (P < 1 || P > SDRG_CHANNELIZER_MAX_TAPS_PER_CHANNEL) return "taps_per_channel outside [1, 32]";
+    if (M * P > SDRG_CHANNELIZER_MAX_TAPS) return "channels * taps_per_channel above 4096";
+    if (c.oversample != 1 && c.oversample != 2) return "oversample must be 1 or 2";
+    if (!(c.cutoff_rel > 0.0 && c.cutoff_rel <= (double)M / 2.0)) return "cutoff_rel outside (0, channels / 2]";
+    if (c.n_channels < 1 || c.first_channel < 0 || c.first_channel > M - c.n_channels)
+        return "[first_channel, first_channel + n_channels) outside [0, channels]";
+    return nullptr;
+}
+
+// The channelizer's prototype (sdrg.h): the DDC's low-pass of L - 1 coefficients at f = cutoff_rel / M, then +0
+void chan_design(const sdrg_channelizer_config &c, float *h) {
+    const int L = c.channels * c.taps_per_channel;
+    lowpass_design(c.cutoff_rel / (double)c.channels, L - 1, h);
+    h[L - 1] = 0.0f;
 }
 
 // The demodulator stage's configuration rules (sdrg.h): nullptr, or what is wrong

@@ -21,6 +21,9 @@ const char *ddc_check(uint32_t sample_rate, double offset_hz, double cutoff_hz, 
 void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h);
 // the same low-pass at the relative cutoff f = cutoff / rate (cycles per sample)
 void lowpass_design(double f, int taps, float *h);
+// Channelizer stage: the configuration rules (nullptr = valid) and the prototype, channels * taps_per_channel floats
+const char *chan_check(const sdrg_channelizer_config &cfg);
+void chan_design(const sdrg_channelizer_config &cfg, float *h);
 // Demodulator stage: the configuration rules (nullptr = valid) and kf, alpha, a and the taps (any pointer may be null)
 const char *demod_check(const sdrg_demod_config &cfg);
 void demod_design(const sdrg_demod_config &cfg, float *kf, float *alpha, float *a, float *h);

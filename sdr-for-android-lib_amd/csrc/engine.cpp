@@ -336,6 +336,19 @@ struct sdrg_engine {
     size_t demod_in_elems = 0;
     char *d_demod_out = nullptr;   // demod_host's and ddc_demod_host's audio rows
     size_t demod_out_bytes = 0;
+    // channelizer stage (sdrg_engine_set_channelizer / channelizer_device / channelizer_host; channelizer.hip)
+    sdrg_channelizer_config chan{};
+    bool chan_set = false;
+    uint64_t chan_g0 = 0;        // samples every stream has consumed since the last restart
+    bool chan_fresh = true;      // the next call starts from a history of zeros
+    int chan_half = 0;           // the half of d_chan_hist the next call reads
+    float *d_chan_hist = nullptr;  // [2][n_streams][L - 1][2]: the unpacked samples before the next frame, ping-pong
+    size_t chan_hist_elems = 0;
+    float *d_chan_taps = nullptr;  // [L] taps, then [CHAN_TWIDDLES][2]: written by set_channelizer
+    void *d_chan_in = nullptr;     // channelizer_host's copy of the caller's iq
+    size_t chan_in_bytes = 0;
+    float *d_chan_out = nullptr;   // channelizer_host's rows
+    size_t chan_out_elems = 0;
 };
 
 namespace {
@@ -1088,7 +1101,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
                     e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->d_disp_in, e->d_disp_out,
                     e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out, e->d_peaks_in, e->d_peaks_out, e->d_ddc_hist,
                     e->d_ddc_w, e->d_ddc_in, e->d_ddc_out, e->d_demod_state, e->d_demod_scratch, e->d_demod_in,
-                    e->d_demod_out};
+                    e->d_demod_out, e->d_chan_hist, e->d_chan_taps, e->d_chan_in, e->d_chan_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
@@ -2296,6 +2309,170 @@ int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, 
     HIP_TRY(hipMemcpyAsync(out, e->d_demod_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
     HIP_TRY(hipStreamSynchronize(e->s_main));
     *n_out = count;
+    return SDRG_OK;
+}
+
+// ---- channelizer stage (channelizer.hip) ---------------------------------------------------------------------------
+
+int32_t sdrg_channelizer_design(const sdrg_channelizer_config *cfg, float *taps) {
+    if (!cfg || !taps) return fail(SDRG_E_INVALID, "null channelizer config or taps");
+    if (const char *bad = chan_check(*cfg)) return fail(SDRG_E_INVALID, "channelizer: %s", bad);
+    chan_design(*cfg, taps);
+    return SDRG_OK;
+}
+
+int32_t sdrg_channelizer_tile_outputs(const sdrg_channelizer_config *cfg, int32_t *tile) {
+    if (!cfg || !tile) return fail(SDRG_E_INVALID, "null channelizer config or tile");
+    if (const char *bad = chan_check(*cfg)) return fail(SDRG_E_INVALID, "channelizer: %s", bad);
+    *tile = chan_tile_outputs(cfg->channels);
+    return SDRG_OK;
+}
+
+static void chan_restart(sdrg_engine *e) {
+    e->chan_g0 = 0;
+    e->chan_fresh = true;
+}
+
+int32_t sdrg_engine_set_channelizer(sdrg_engine *e, const sdrg_channelizer_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (cfg) {
+        if (const char *bad = chan_check(*cfg)) return fail(SDRG_E_INVALID, "channelizer: %s", bad);
+        // the taps and the DFT's twiddles go into a buffer of their own; the old one is freed afterwards, which waits
+        // for the calls that still read it
+        const size_t L = (size_t)cfg->channels * (size_t)cfg->taps_per_channel;
+        std::vector<float> host(L + 2 * (size_t)CHAN_TWIDDLES);
+        chan_design(*cfg, host.data());
+        for (int t = 0; t < CHAN_TWIDDLES; t++) {
+            const double a = 2.0 * M_PI * (double)t / (double)CHAN_TWIDDLES;
+            host[L + 2 * (size_t)t] = (float)std::cos(a);
+            host[L + 2 * (size_t)t + 1] = (float)-std::sin(a);
+        }
+        DeviceScope dscope(e->device);
+        HIP_TRY(dscope.error());
+        float *fresh = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&fresh), sizeof(float) * host.size()));
+        hipError_t er = hipMemcpy(fresh, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
+        if (er != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(SDRG_E_HIP, "channelizer taps upload: %s", hipGetErrorString(er));
+        }
+        if (e->d_chan_taps) (void)hipFree(e->d_chan_taps);
+        e->d_chan_taps = fresh;
+        e->chan = *cfg;
+    }
+    e->chan_set = cfg != nullptr;
+    chan_restart(e);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_channelizer(const sdrg_engine *e, sdrg_channelizer_config *cfg, uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!e->chan_set) return fail(SDRG_E_INVALID, "no channelizer configuration set");
+    if (cfg) *cfg = e->chan;
+    if (samples_consumed) *samples_consumed = e->chan_g0;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_channelizer_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    chan_restart(e);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_channelizer_max_out(const sdrg_engine *e, int32_t *cap) {
+    if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
+    if (!e->chan_set) return fail(SDRG_E_INVALID, "no channelizer configuration set (sdrg_engine_set_channelizer)");
+    const int D = e->chan.channels / e->chan.oversample;
+    *cap = (e->cfg.samples_per_reading + D - 1) / D;
+    return SDRG_OK;
+}
+
+// what one channelizer call needs beside its buffers, resolved before anything is touched
+struct ChanCall {
+    int n, decim, cap, n_out;
+};
+
+static int32_t chan_resolve(const sdrg_engine *e, int32_t fmt, ChanCall *c) {
+    if (!e->chan_set) return fail(SDRG_E_INVALID, "no channelizer configuration set (sdrg_engine_set_channelizer)");
+    if (bytes_per_sample(fmt) == 0) return fail(SDRG_E_INVALID, "unknown iq format %d", fmt);
+    c->n = e->cfg.samples_per_reading;
+    c->decim = e->chan.channels / e->chan.oversample;
+    const uint64_t g0 = e->chan_g0, D = (uint64_t)c->decim;
+    c->cap = (c->n + c->decim - 1) / c->decim;
+    c->n_out = (int)((g0 + (uint64_t)c->n + D - 1) / D - (g0 + D - 1) / D);
+    return SDRG_OK;
+}
+
+// one channelizer call on the main stream: iq, out in device memory
+static int32_t chan_enqueue(sdrg_engine *e, const ChanCall &c, const void *iq, int32_t fmt, float *out) {
+    const sdrg_channelizer_config &cfg = e->chan;
+    const size_t L = (size_t)cfg.channels * (size_t)cfg.taps_per_channel;
+    const size_t half = (size_t)e->n_streams * (L - 1) * 2;
+    if (e->chan_hist_elems < 2 * half || !e->d_chan_hist) {
+        // only a larger L asks for more, and set_channelizer restarted the streams: nothing to keep
+        int32_t rc = ensure_device(&e->d_chan_hist, &e->chan_hist_elems, 2 * half);
+        if (rc) return rc;
+    }
+    const uint64_t g0 = e->chan_g0, D = (uint64_t)c.decim;
+    ChanParams p{};
+    p.n = c.n;
+    p.channels = cfg.channels;
+    p.taps_per_channel = cfg.taps_per_channel;
+    p.oversample = cfg.oversample;
+    p.decim = c.decim;
+    p.first = (int)((D - g0 % D) % D);
+    p.n_out = c.n_out;
+    p.cap = c.cap;
+    p.first_channel = cfg.first_channel;
+    p.n_channels = cfg.n_channels;
+    p.m_parity = (int)(((g0 + D - 1) / D) & 1);  // the global time of the call's first output
+    p.taps = e->d_chan_taps;
+    p.hist_old = e->chan_fresh ? nullptr : e->d_chan_hist + (size_t)e->chan_half * half;
+    p.hist_new = e->d_chan_hist + (size_t)(e->chan_half ^ 1) * half;
+    HIP_TRY(launch_channelizer(iq, fmt, e->n_streams, p, out, e->s_main));
+    e->chan_g0 = g0 + (uint64_t)c.n;
+    e->chan_fresh = false;
+    e->chan_half ^= 1;
+    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers out as it covers display rows
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_channelizer_device(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    ChanCall c;
+    int32_t rc = chan_resolve(e, fmt, &c);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    rc = chan_enqueue(e, c, iq, fmt, static_cast<float *>(out));
+    if (rc) return rc;
+    *n_out = c.n_out;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_channelizer_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    ChanCall c;
+    int32_t rc = chan_resolve(e, fmt, &c);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const size_t in_bytes = (size_t)e->n_streams * (size_t)c.n * (size_t)bytes_per_sample(fmt);
+    const size_t out_elems = (size_t)e->n_streams * (size_t)e->chan.n_channels * (size_t)c.cap * 2;
+    char *in = static_cast<char *>(e->d_chan_in);
+    rc = ensure_device(&in, &e->chan_in_bytes, in_bytes);
+    e->d_chan_in = in;
+    if (rc) return rc;
+    rc = ensure_device(&e->d_chan_out, &e->chan_out_elems, out_elems);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_chan_in, iq, in_bytes, hipMemcpyHostToDevice, e->s_main));
+    rc = chan_enqueue(e, c, e->d_chan_in, fmt, e->d_chan_out);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->d_chan_out, sizeof(float) * out_elems, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
+    *n_out = c.n_out;
     return SDRG_OK;
 }
 

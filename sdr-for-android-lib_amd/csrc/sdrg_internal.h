@@ -211,4 +211,25 @@ int demod_tile_outputs(int decim, int taps);  // FIR outputs per workgroup
 hipError_t launch_demod(const float *chan, int n_streams, const DemodParams &p, const DemodTaps &taps, void *out,
                         hipStream_t stream);
 
+// Channelizer stage (channelizer.hip): per stream and output time j in [0, n_out), the branch sums u_p = sum_q
+// h[p + q channels] x[first + j decim - p - q channels] (x the frame's n unpacked samples and, at indices in
+// [-(L - 1), 0), hist_old [n_streams][L - 1][2], nullptr: zeros; L = channels taps_per_channel), their DFT
+// Y_c = sum_p u_p e^{+j 2 pi c p / channels}, and at oversample 2 the sign (-1)^{c (m_parity + j)}.  Writes the rows
+// [first_channel, first_channel + n_channels) of the fftshifted order to out [n_streams][n_channels][cap][2] whole
+// (zeros from n_out on) and the unpacked samples at [n - (L - 1), n) to hist_new.  taps: [L] floats, then
+// e^{-j 2 pi t / 256}, t in [0, 256), as float pairs, in device memory.  log2m, tile, log2tile, n_tiles, region and
+// vec_ok are the launcher's.
+struct ChanParams {
+    int n, channels, taps_per_channel, oversample, decim, first, n_out, cap;
+    int first_channel, n_channels, m_parity;
+    const float *taps;
+    const float *hist_old;
+    float *hist_new;
+    int log2m, tile, log2tile, n_tiles, region, vec_ok;
+};
+constexpr int CHAN_TWIDDLES = 256;
+int chan_tile_outputs(int channels);  // output times per workgroup
+hipError_t launch_channelizer(const void *iq, int fmt, int n_streams, const ChanParams &p, float *out,
+                              hipStream_t stream);
+
 }  // namespace sdrg

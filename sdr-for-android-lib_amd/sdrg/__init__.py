@@ -42,6 +42,7 @@ DDC_MAX_TAPS, DDC_MAX_DECIMATION = 511, 512                         # SDRG_DDC_M
 DEMOD_AM, DEMOD_FM = 0, 1                                           # SDRG_DEMOD_AM, SDRG_DEMOD_FM
 DEMOD_OUT_S16, DEMOD_OUT_F32 = 0, 1                                 # SDRG_DEMOD_OUT_*
 DEMOD_MAX_TAPS, DEMOD_MAX_DECIMATION, DEMOD_MAX_IN = 255, 64, 1 << 20  # SDRG_DEMOD_MAX_*
+CHANNELIZER_MAX_CHANNELS, CHANNELIZER_MAX_TAPS_PER_CHANNEL, CHANNELIZER_MAX_TAPS = 256, 32, 4096  # SDRG_CHANNELIZER_*
 DEMOD_OUT_DTYPE = {DEMOD_OUT_S16: np.int16, DEMOD_OUT_F32: np.float32}
 STATUS = {0: "SDRG_OK", -1: "SDRG_E_INVALID", -2: "SDRG_E_UNSUPPORTED", -3: "SDRG_E_NOMEM", -4: "SDRG_E_HIP",
           -5: "SDRG_E_NODEVICE"}
@@ -128,6 +129,9 @@ EXPORTS = [
     "sdrg_demod_design", "sdrg_demod_geometry", "sdrg_engine_set_demod", "sdrg_engine_get_demod",
     "sdrg_engine_demod_reset", "sdrg_engine_demod_max_out", "sdrg_engine_demod_device", "sdrg_engine_demod_host",
     "sdrg_engine_ddc_demod_host",
+    "sdrg_channelizer_design", "sdrg_channelizer_tile_outputs", "sdrg_engine_set_channelizer",
+    "sdrg_engine_get_channelizer", "sdrg_engine_channelizer_reset", "sdrg_engine_channelizer_max_out",
+    "sdrg_engine_channelizer_device", "sdrg_engine_channelizer_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -199,6 +203,22 @@ class DemodConfig(ctypes.Structure):
                 ("audio_cutoff_hz", ctypes.c_double), ("mode", ctypes.c_int32), ("audio_decimation", ctypes.c_int32),
                 ("audio_taps", ctypes.c_int32), ("out_format", ctypes.c_int32), ("max_in", ctypes.c_int32),
                 ("gain", ctypes.c_float)]
+
+
+class ChannelizerConfig(ctypes.Structure):
+    """sdrg_channelizer_config: the channelizer stage's prototype cutoff, channel count, taps per channel, oversampling
+    and the span of rows written (include/sdrg.h)."""
+    _fields_ = [("cutoff_rel", ctypes.c_double), ("channels", ctypes.c_int32), ("taps_per_channel", ctypes.c_int32),
+                ("oversample", ctypes.c_int32), ("first_channel", ctypes.c_int32), ("n_channels", ctypes.c_int32)]
+
+
+def _channelizer_config(fields: dict) -> ChannelizerConfig:
+    c = ChannelizerConfig()
+    for k, v in fields.items():
+        if k not in dict(ChannelizerConfig._fields_):
+            raise TypeError(f"unknown channelizer field {k!r}")
+        setattr(c, k, v)
+    return c
 
 
 def _demod_config(fields: dict) -> DemodConfig:
@@ -404,6 +424,14 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_demod_device": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_demod_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_ddc_demod_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_channelizer_design": (_I32, [ctypes.POINTER(ChannelizerConfig), P]),
+        "sdrg_channelizer_tile_outputs": (_I32, [ctypes.POINTER(ChannelizerConfig), ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_channelizer": (_I32, [P, ctypes.POINTER(ChannelizerConfig)]),
+        "sdrg_engine_get_channelizer": (_I32, [P, ctypes.POINTER(ChannelizerConfig), ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_channelizer_reset": (_I32, [P]),
+        "sdrg_engine_channelizer_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_channelizer_device": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_channelizer_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -606,6 +634,23 @@ def demod_geometry(audio_decimation: int, audio_taps: int) -> tuple:
     _check(load().sdrg_demod_geometry(audio_decimation, audio_taps, ctypes.byref(tile), ctypes.byref(chunk)),
            "demod_geometry")
     return tile.value, chunk.value
+
+
+def channelizer_design(**fields) -> np.ndarray:
+    """The channelizer stage's prototype for a configuration (host-side, no device): float32 [channels *
+    taps_per_channel].  The fields are sdrg_channelizer_config's (fields left out are 0)."""
+    c = _channelizer_config(fields)
+    L = c.channels * c.taps_per_channel
+    h = np.zeros(L if 0 < L <= CHANNELIZER_MAX_TAPS else 1, np.float32)
+    _check(load().sdrg_channelizer_design(ctypes.byref(c), h.ctypes.data_as(ctypes.c_void_p)), "channelizer_design")
+    return h
+
+
+def channelizer_tile_outputs(**fields) -> int:
+    """Consecutive output times per workgroup of the channelizer kernel for a configuration."""
+    c, t = _channelizer_config(fields), _I32()
+    _check(load().sdrg_channelizer_tile_outputs(ctypes.byref(c), ctypes.byref(t)), "channelizer_tile_outputs")
+    return t.value
 
 
 def ssb_design(samp_count: int, sample_rate: int, sound_mode: int = 1) -> dict:
@@ -1063,6 +1108,59 @@ class Engine:
                                                  out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_out)),
                "ddc_demod_host")
         return out[:, :n_out.value]
+
+    # ---- channelizer stage ------------------------------------------------------------------------
+    def set_channelizer(self, **fields) -> None:
+        """sdrg_engine_set_channelizer: cutoff_rel, channels, taps_per_channel, oversample, first_channel, n_channels
+        (fields left out are 0); set_channelizer(off=True) switches the stage off."""
+        if fields.pop("off", False):
+            if fields:
+                raise TypeError("off=True takes no other field")
+            _check(load().sdrg_engine_set_channelizer(self._h, None), "set_channelizer")
+            return
+        c = _channelizer_config(fields)
+        _check(load().sdrg_engine_set_channelizer(self._h, ctypes.byref(c)), "set_channelizer")
+
+    def channelizer_config(self) -> dict:
+        """The configuration in force, plus samples_consumed."""
+        c, g0 = ChannelizerConfig(), ctypes.c_uint64()
+        _check(load().sdrg_engine_get_channelizer(self._h, ctypes.byref(c), ctypes.byref(g0)), "get_channelizer")
+        d = {k: getattr(c, k) for k, _ in ChannelizerConfig._fields_}
+        d.update(samples_consumed=g0.value)
+        return d
+
+    def channelizer_reset(self) -> None:
+        _check(load().sdrg_engine_channelizer_reset(self._h), "channelizer_reset")
+
+    def channelizer_max_out(self) -> int:
+        """ceil(samplesPerReading / (channels / oversample)): the row length of a channelizer call's output."""
+        cap = _I32()
+        _check(load().sdrg_engine_channelizer_max_out(self._h, ctypes.byref(cap)), "channelizer_max_out")
+        return cap.value
+
+    def channelizer_device(self, iq_ptr: int, fmt: int, out_ptr: int) -> int:
+        """Device path: iq [n_streams][N] raw samples in, out [n_streams][n_channels][channelizer_max_out()] complex64
+        out; asynchronous on the main stream.  Returns n_out, the outputs this call produced per row (the rest of a row
+        is zero)."""
+        n_out = _I32()
+        _check(load().sdrg_engine_channelizer_device(self._h, iq_ptr, fmt, out_ptr, ctypes.byref(n_out)),
+               "channelizer_device")
+        return n_out.value
+
+    def channelizer(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
+        """Host path: iq is [n_streams][samplesPerReading * 2] raw samples; returns complex64
+        [n_streams][n_channels][n_out]."""
+        n = self.cfg.samplesPerReading
+        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
+        if iq.size != self.n_streams * n * 2:
+            raise SdrgError(f"iq has {iq.size} values, expected {self.n_streams}x{n}x2")
+        rows = self.channelizer_config()["n_channels"]
+        out = np.empty((self.n_streams, rows, self.channelizer_max_out()), np.complex64)
+        n_out = _I32()
+        _check(load().sdrg_engine_channelizer_host(self._h, iq.ctypes.data_as(ctypes.c_void_p), fmt,
+                                                   out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_out)),
+               "channelizer_host")
+        return out[:, :, :n_out.value]
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
                        pcm_ptr: int | None, now_ms: int = 0) -> None:
