@@ -542,11 +542,11 @@ __global__ __attribute__((amdgpu_flat_work_group_size(PIPE_T, PIPE_T), amdgpu_wa
             f2v z = {z1, z2};
             const uint32_t abase = lds_addr(&L.a[0][my_s * ROW]), ybase = lds_addr(&L.y[0][my_s * ROW]);
             const int nit = nch + 8 + LA;
-            unsigned long long sv;
+            unsigned long long sv, t_ret;
             int t_it, t_cc, t_r, t_yo;
             if (SDRG_LPF_INTERLEAVE)
                 asm volatile(SDRG_LPF_LOOP_IL_ASM
-                             : [z] "+v"(z), [sv] "=&s"(sv), [it] "=&s"(t_it), [cc] "=&s"(t_cc), [r] "=&s"(t_r), [yo] "=&s"(t_yo)
+                             : [z] "+v"(z), [sv] "=&s"(sv), [it] "=&s"(t_it), [cc] "=&s"(t_cc), [ret] "=&s"(t_ret), [yo] "=&s"(t_yo)
                              : [abase] "v"(abase), [ybase] "v"(ybase), [c1] "s"(c1), [c2] "s"(c2), [nit] "s"(nit), [nch] "s"(nch)
                              : SDRG_CHUNK_CLOBBERS, "v54", "memory");
             else

@@ -238,12 +238,25 @@ def lpf_loop():
 
 
 def lpf_loop_interleaved(copies=False, split=False):
-    """lpf_loop() with the LDS traffic spread through the VALU stream: sub-blocks are numbered g = 4c + sb across
-    chunks and live in buffer g mod 3; while sub-block g runs, after each 4-sample quad t its output quad is written
-    and quad t of sub-block g + 2 is read (for sb = 2, 3 that is the next chunk's sub-block 0, 1, complete in its
-    ring slot).  So at the barrier only the chunk's last write is outstanding (lgkmcnt(1)), and the first two
-    sub-blocks of the next chunk are already in registers.  The last chunk's reads of a next chunk fetch a stale
-    ring slot and are never used; the block drains them (lgkmcnt(0)) before it ends.
+    """lpf_loop() with the LDS traffic spread through the VALU stream and the chunk barrier inside the chain.
+    Sub-blocks are numbered g = 4c + sb across chunks and live in buffer g mod 3; while sub-block g runs, after each
+    4-sample quad t its output quad is written and quad t of sub-block g + 2 is read (for sb = 2, 3 that is the next
+    chunk's sub-block 0, 1, complete in its ring slot), so the first two sub-blocks of the next chunk are in registers
+    when a chunk ends.
+    The body is rotated by one quad: after chunk c's 16th write the wave captures the state, runs the FIRST quad of
+    chunk c + 1 on registers (the run-ahead quad) and only then waits for its stores (lgkmcnt(1): the 16th write done,
+    its paired read may fly on) and meets the barrier, so the store's latency and the bookkeeping (c + 1, its output
+    slot address in v54, the end test) pass in the chain's own dependency gaps.  The run-ahead quad's outputs stay in
+    their buffer registers: chunk c + 1's output slot still holds chunk c - 3, which the clamp role reads during this
+    iteration, so their write (and the paired read of sub-block g + 2) is the first thing after the barrier.  Every
+    iteration's LDS operations are therefore the ones of the unrotated loop.
+    The bodies reach the one s_barrier by s_call_b64 and come back by s_setpc_b64 to the instruction after the call,
+    which is the next body in chunk-mod-3 order (one s_branch back-edge per three chunks): no dispatch ladder.  The
+    first chunk enters body 2 at its run-ahead quad (v46, v47 hold the carried state as chunk -1's last outputs).
+    After the last chunk the run-ahead quad computes on a stale ring slot and stores nothing; the state was captured
+    before it.  %[nit] >= %[nch] + 3 iterations in all: 2 idle, 1 that reads chunk 0's first two sub-blocks and runs
+    its first quad, nch chunk bodies, the rest idle.
+    Operands as lpf_loop(), with %[ret] (=&s 64-bit: the return address across the barrier) for %[r].
     Lab forms (--lab, not in the product): copies, all 64 lanes with lane l running stream l mod 16 (four copies: a
     dependent chain issues faster on a full EXEC mask, and the copies write the same values to the same LDS
     addresses); split, the chain's VALU on all 64 lanes (lanes 16-63 compute on whatever they hold and store nothing),
@@ -252,81 +265,87 @@ def lpf_loop_interleaved(copies=False, split=False):
     out = []
     u = "%="
     lanes = ["s_mov_b64 exec, -1"] if copies or split else ["s_mov_b64 exec, 0xffff"]
+    bar = f"s_call_b64 %[ret], L_bar_{u}"
+
+    def lds_pair(ops):
+        return (["s_mov_b64 exec, 0xffff"] + ops + ["s_mov_b64 exec, -1"]) if split else ops
+
     out += ["s_mov_b64 %[sv], exec"] + lanes + [
         "s_nop 4",
-        "v_pk_mov_b32 v[46:47], %[z], %[z] op_sel:[1,0]",
-        "v_pk_mov_b32 v[52:53], %[z], %[z] op_sel:[0,1]",
-        "s_mov_b32 %[it], 0",
-        "s_mov_b32 %[cc], -3",
-        "s_mov_b32 %[r], 0",
-        f"L_top_{u}:",
-        "s_cmp_lt_i32 %[cc], 0",
-        f"s_cbranch_scc1 L_pre_{u}",
-        "s_cmp_ge_i32 %[cc], %[nch]",
-        f"s_cbranch_scc1 L_drain_{u}",
-        "s_and_b32 %[yo], %[cc], 3",
-        f"s_mul_i32 %[yo], %[yo], {SLOT}",
-        "v_add_u32 v54, %[yo], %[ybase]",
-        "s_cmp_eq_u32 %[r], 0",
-        f"s_cbranch_scc1 L_r0_{u}",
-        "s_cmp_eq_u32 %[r], 1",
-        f"s_cbranch_scc1 L_r1_{u}",
-        f"s_branch L_r2_{u}",
+        "v_pk_mov_b32 v[46:47], %[z], %[z] op_sel:[1,0]",   # chunk -1's last sub-block buffer (2): v47 = z1, v46 = z2
+        "v_pk_mov_b32 v[52:53], %[z], %[z] op_sel:[0,1]",   # the carried {z1, z2} if no chunk runs
+        "s_mov_b32 %[it], %[nit]",
+        "s_cmp_le_i32 %[nch], 0",
+        f"s_cbranch_scc1 L_idle_{u}",       # no chunk: nit idle iterations
+        bar,                                # iterations 0, 1: c = -3, -2
+        bar,
+    ]
+    # iteration 2 (c = -1): chunk 0 is complete; its sub-blocks 0, 1, then its first quad in body 2's tail
+    out += lds_pair([f"ds_read_b128 v[{BUFS[j] + 4 * i}:{BUFS[j] + 4 * i + 3}], %[abase] offset:{(16 * j + 4 * i) * 4}"
+                     for j in range(2) for i in range(4)])
+    out += [
+        "s_mov_b32 %[cc], -1",
+        "s_waitcnt lgkmcnt(4)",             # sub-block 0 landed
+        f"s_branch L_ra2_{u}",
     ]
     for r in range(3):
         out.append(f"L_r{r}_{u}:")
-        zb = BUFS[(r + 2) % 3]
-        prev1, prev2 = pair(zb + 15), pair(zb + 14)
+        b0 = BUFS[r]
+        prev1, prev2 = pair(b0 + 3), pair(b0 + 2)            # the run-ahead quad's last two outputs
         for sb in range(4):
-            out.append(f"s_waitcnt lgkmcnt({4 if sb == 0 else 8})")
             b = BUFS[(r + sb) % 3]
             rb = BUFS[(r + sb + 2) % 3]                      # buffer of sub-block g + 2
             rslot, rsb = (r, sb + 2) if sb < 2 else ((r + 1) % 3, sb - 2)
+            if sb > 0:                                       # sub-block g's reads (issued during g - 2) landed:
+                out.append("s_waitcnt lgkmcnt(8)")           # the 8 operations of g - 1 may fly on
             for q in range(16):
-                out += lpf_sample(b + q, prev1, prev2)
-                prev2, prev1 = prev1, pair(b + q)
+                if sb > 0 or q >= 4:                         # sb 0's first quad ran ahead, before the barrier
+                    out += lpf_sample(b + q, prev1, prev2)
+                    prev2, prev1 = prev1, pair(b + q)
                 if q % 4 == 3:
                     t = q // 4
-                    if split:
-                        out.append("s_mov_b64 exec, 0xffff")
-                    out.append(f"ds_write_b128 v54, v[{b + 4 * t}:{b + 4 * t + 3}] offset:{(16 * sb + 4 * t) * 4}")
-                    out.append(f"ds_read_b128 v[{rb + 4 * t}:{rb + 4 * t + 3}], %[abase] offset:{rslot * SLOT + (16 * rsb + 4 * t) * 4}")
-                    if split:
-                        out.append("s_mov_b64 exec, -1")
+                    out += lds_pair([
+                        f"ds_write_b128 v54, v[{b + 4 * t}:{b + 4 * t + 3}] offset:{(16 * sb + 4 * t) * 4}",
+                        f"ds_read_b128 v[{rb + 4 * t}:{rb + 4 * t + 3}], %[abase] offset:{rslot * SLOT + (16 * rsb + 4 * t) * 4}"])
         last = BUFS[(r + 3) % 3] + 15
         out.append(f"v_pk_mov_b32 v[52:53], v[{last - 1}:{last}], v[{last - 1}:{last}] op_sel:[1,0]")
-        out.append(f"s_branch L_bar1_{u}")
+        # the next chunk's sub-block 0 (read during this chunk's sub-block 2) landed: sub-block 3's 8 may fly on
+        out.append("s_waitcnt lgkmcnt(8)")
+        out.append(f"L_ra{r}_{u}:")
+        nb = BUFS[(r + 1) % 3]
+        # the next chunk's number, output slot address and end test, one instruction per dependency gap of the quad
+        extra = {2: "s_add_i32 %[cc], %[cc], 1", 3: "s_and_b32 %[yo], %[cc], 3", 4: f"s_mul_i32 %[yo], %[yo], {SLOT}",
+                 5: "v_add_u32 v54, %[yo], %[ybase]", 8: "s_cmp_ge_i32 %[cc], %[nch]"}
+        quad = []
+        for q in range(4):
+            quad += lpf_sample(nb + q, prev1, prev2)
+            prev2, prev1 = prev1, pair(nb + q)
+        for i, ins in enumerate(quad):
+            out.append(ins)
+            if i in extra:
+                out.append(extra[i])
+        out += [
+            f"s_cbranch_scc1 L_last_{u}",   # no next chunk: the quad ran on a stale slot and is dropped
+            "s_waitcnt lgkmcnt(1)",         # this chunk's writes done; the last read of the next chunk may fly on
+            bar,
+        ]
+        if r == 2:
+            out.append(f"s_branch L_r0_{u}")
     out += [
-        f"L_pre_{u}:",                      # c < 0: chunk 0's sub-blocks 0, 1 once c == -1 (chunk 0 is complete)
-        "s_cmp_lg_i32 %[cc], -1",
-        f"s_cbranch_scc1 L_drain_{u}",
-        "s_cmp_le_i32 %[nch], 0",
-        f"s_cbranch_scc1 L_drain_{u}",
-    ]
-    out += ["s_mov_b64 exec, 0xffff"] if split else []
-    out += [f"ds_read_b128 v[{BUFS[0] + 4 * i}:{BUFS[0] + 4 * i + 3}], %[abase] offset:{(4 * i) * 4}" for i in range(4)]
-    out += [f"ds_read_b128 v[{BUFS[1] + 4 * i}:{BUFS[1] + 4 * i + 3}], %[abase] offset:{(16 + 4 * i) * 4}" for i in range(4)]
-    out += ["s_mov_b64 exec, -1"] if split else []
-    out += [
-        f"s_branch L_bar_{u}",
-        f"L_bar1_{u}:",
-        "s_waitcnt lgkmcnt(1)",             # this chunk's writes done; the last read of the next chunk may fly on
-        f"s_branch L_bar_{u}",
-        f"L_drain_{u}:",
-        "s_waitcnt lgkmcnt(0)",
-        f"L_bar_{u}:",
+        f"L_last_{u}:",
+        "s_sub_u32 %[it], %[nit], %[nch]",  # the barriers left: the last chunk's own and nit - (nch + 3) idle ones
+        "s_sub_u32 %[it], %[it], 2",
+        "s_waitcnt lgkmcnt(0)",             # the last chunk's writes, and its reads of a next chunk that does not exist
+        f"L_idle_{u}:",
+        "s_cmp_le_i32 %[it], 0",
+        f"s_cbranch_scc1 L_end_{u}",
+        bar,
+        "s_sub_u32 %[it], %[it], 1",
+        f"s_branch L_idle_{u}",
+        f"L_bar_{u}:",                      # the loop's one barrier: called from every iteration
         "s_barrier",
-        "s_add_u32 %[it], %[it], 1",
-        "s_add_i32 %[cc], %[cc], 1",
-        "s_cmp_le_i32 %[cc], 0",
-        f"s_cbranch_scc1 L_next_{u}",
-        "s_add_u32 %[r], %[r], 1",
-        "s_cmp_eq_u32 %[r], 3",
-        "s_cselect_b32 %[r], 0, %[r]",
-        f"L_next_{u}:",
-        "s_cmp_lt_u32 %[it], %[nit]",
-        f"s_cbranch_scc1 L_top_{u}",
-        "s_waitcnt lgkmcnt(0)",             # the last chunk's reads of a next chunk that does not exist
+        "s_setpc_b64 %[ret]",
+        f"L_end_{u}:",
         "s_mov_b64 exec, %[sv]",
         "s_nop 4",
         "v_pk_mov_b32 %[z], v[52:53], v[52:53] op_sel:[0,1]",
@@ -358,7 +377,8 @@ def main():
     emit("SDRG_AGC_CHUNK_IL_ASM", chunk("agc", il=True))
     print("// the low-pass wave's whole loop with a one-chunk lookahead (SDRG_LPF_LOOKAHEAD; see lpf_loop() in the generator)")
     emit("SDRG_LPF_LOOP_ASM", lpf_loop())
-    print("// the same loop with the chunk's LDS reads and writes interleaved quad by quad (SDRG_LPF_INTERLEAVE)")
+    print("// the same loop with the chunk's LDS reads and writes interleaved quad by quad (SDRG_LPF_INTERLEAVE) and the body")
+    print("// rotated by one quad over the barrier; %[ret] (=&s, 64-bit) for %[r] (see lpf_loop_interleaved() in the generator)")
     emit("SDRG_LPF_LOOP_IL_ASM", lpf_loop_interleaved())
     print("#define SDRG_CHUNK_CLOBBERS \\")
     regs = [f'"v{i}"' for i in range(T0 + 2)]

@@ -32,13 +32,14 @@ __global__ __launch_bounds__(768) void k(unsigned long long *out, int prio, int 
     const f2v c1 = {1.9f, -0.9f}, c2 = {0.01f, -0.005f};
     f2v z = {0.0f, 0.0f};
     unsigned long long sv;
-    int t_it, t_cc, t_r, t_yo;
+    unsigned long long t_ret;
+    int t_it, t_cc, t_yo;
     const int nch = NCH;
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
     if (lane < 16 || V >= 1) {
 #define LOOP(M)                                                                                                  \
     asm volatile(M                                                                                               \
-                 : [z] "+v"(z), [sv] "=&s"(sv), [it] "=&s"(t_it), [cc] "=&s"(t_cc), [r] "=&s"(t_r), [yo] "=&s"(t_yo) \
+                 : [z] "+v"(z), [sv] "=&s"(sv), [it] "=&s"(t_it), [cc] "=&s"(t_cc), [ret] "=&s"(t_ret), [yo] "=&s"(t_yo) \
                  : [abase] "v"(abase), [ybase] "v"(ybase), [c1] "s"(c1), [c2] "s"(c2), [nit] "s"(nit), [nch] "s"(nch) \
                  : SDRG_CHUNK_CLOBBERS, "v54", "memory")
         if constexpr (V == 0) LOOP(SDRG_LPF_LOOP_IL_ASM);
