@@ -2,13 +2,9 @@
 // channels, one prototype low-pass of L = M P taps, decimation D = M / O, the written rows as CF32 (DESIGN.md §3.14,
 // include/sdrg.h).
 //
-// Grid (tiles of output times + 1, streams), 256 threads.  A call's output times j in [0, n_out) read the unpacked
-// samples at the local indices t = first + j D - n, n in [0, L); t in [0, N) is this frame, t in [-(L - 1), 0) the
-// history (the L - 1 unpacked samples before the frame, zeros after a restart).
-//   tile block   `tile` = 2048 / M consecutive output times.  The workgroup stages the (nj - 1) D + L samples they read
-//                into LDS once, linearly: raw samples in aligned 16-byte loads (the chunks the window covers only in
-//                part, at its ends, and bases that are not sample-aligned, sample by sample), unpacked as load_i1 /
-//                load_q1 of ssb_common.h; indices below 0 come from the history.
+// The tile form of fir_tile.h (grid, history, staging) on the unpacked samples, 256 threads: H = L - 1, an output is an
+// output time (M values), and the history holds unpacked samples.  The stage's own:
+//   tile block   `tile` = 2048 / M consecutive output times; the window of (nj - 1) D + L samples is staged linearly.
 //   branch sums  thread (p = tid mod M, g = tid / M) owns branch p at the eight output times j = g + i (256 / M):
 //                u_p[j] = sum_q h[p + q M] x[j D - p - q M], q ascending, one packed FMA on the (re, im) pair per tap,
 //                four taps (read from the device's tap buffer, coalesced over p) and their 32 LDS reads issued per
@@ -20,16 +16,13 @@
 //                W_M^{b k1} from the device's table, in place; then B-point DFTs).  Y_c = F[(M - c) mod M].
 //   stores       the spectra go to LDS transposed, [frequency][output time] (over the window, dead by then), and each
 //                written row's run of `tile` outputs leaves as consecutive 8-byte words: 64 bytes (M = 256) to 8 KiB.
-//   last block   (blockIdx.x == n_tiles) writes the stream's new history, the unpacked samples at t in
-//                [N - (L - 1), N) (from the frame, or moved down from the old history where t < 0), into the other half
-//                of the ping-pong buffer, and zeroes the entries from n_out to cap of every written row: no workgroup
-//                reads what another writes in the same launch.
+//   last block   zeroes the entries from n_out to cap of every written row beside carrying the history.
 // An output's value depends only on its window and on (c, m): the order of its sums is fixed, so any cut of a stream
 // into calls gives the same bytes.  Contraction stays on (the stage is specified by a bound, not operation by operation).
 #include <algorithm>
 
+#include "fir_tile.h"
 #include "sdrg_internal.h"
-#include "ssb_common.h"
 
 namespace sdrg {
 namespace {
@@ -43,26 +36,24 @@ constexpr int CHAN_THREADS = 256;
 constexpr int CHAN_JPT = 8;             // output times per thread in the branch sums: tile = CHAN_JPT * 256 / M
 constexpr int CHAN_LDS_BYTES = 65536;   // window (or transposed spectra) + block, every valid configuration fits
 
+// stage_iq_window's sink: the window is a linear image of the unpacked samples.  (A lane's 8, 4 or 2 stores of a chunk
+// land 64 bytes from its neighbour's; one sample per lane and step, with conflict-free stores, measured 14 to 33 %
+// slower all the same: the loads' latency, not the stores, is what a tile waits for.  DESIGN.md §3.14.)
 template <int FMT>
-__device__ __forceinline__ f2 chan_sample(const char *__restrict__ frame, int t) {
-    return f2{load_i1<FMT>(frame, t), load_q1<FMT>(frame, t)};
-}
-
-// sample s of a 16-byte chunk (8, 4 or 2 samples by format), the expressions of load_i1 / load_q1
-template <int FMT>
-__device__ __forceinline__ f2 chan_unpack(const uint32_t (&w)[4], int s) {
-    if constexpr (FMT == SDRG_IQ_CS8) {
-        const uint32_t h = w[s >> 1] >> (16 * (s & 1));
-        return f2{(float)(int8_t)(h & 0xff) * (1.0f / 128.0f), (float)(int8_t)((h >> 8) & 0xff) * (1.0f / 128.0f)};
-    } else if constexpr (FMT == SDRG_IQ_CU8) {
-        const uint32_t h = w[s >> 1] >> (16 * (s & 1));
-        return f2{((float)(h & 0xff) - 127.4f) * (1.0f / 128.0f), ((float)((h >> 8) & 0xff) - 127.4f) * (1.0f / 128.0f)};
-    } else if constexpr (FMT == SDRG_IQ_CS16) {
-        return f2{(float)(int16_t)(w[s] & 0xffff) * (1.0f / 32768.0f), (float)(int16_t)(w[s] >> 16) * (1.0f / 32768.0f)};
-    } else {
-        return f2{__uint_as_float(w[2 * s]), __uint_as_float(w[2 * s + 1])};
+struct ChanSink {
+    f2 *smp;
+    __device__ __forceinline__ void hist(int u, f2 v) const { smp[u] = v; }
+    __device__ __forceinline__ void sample(int u, int, float xr, float xi) const { smp[u] = f2{xr, xi}; }
+    __device__ __forceinline__ void chunk(int u0, int, const uint32_t (&w)[4]) const {
+        f2 *dst = smp + u0;
+#pragma unroll
+        for (int s = 0; s < 16 / bytes_per_sample<FMT>(); s++) {
+            float xr, xi;
+            iq_chunk_unpack<FMT>(w, s, xr, xi);
+            dst[s] = f2{xr, xi};
+        }
     }
-}
+};
 
 // M = R <= 32: one thread per output time, the whole DFT in registers.  U rows of R + 1, V rows of vs.
 template <int R>
@@ -113,7 +104,7 @@ __device__ __forceinline__ void chan_dft_large(f2 *U, f2 *V, const float2 *__res
 template <int FMT>
 __global__ __launch_bounds__(CHAN_THREADS) void chan_kernel(const char *__restrict__ iq, ChanParams p,
                                                             float *__restrict__ out) {
-    constexpr int BPS = bytes_per_sample<FMT>(), SPC = 16 / BPS;
+    constexpr int BPS = bytes_per_sample<FMT>();
     extern __shared__ __attribute__((aligned(16))) f2 chan_lds[];
     const int tid = threadIdx.x, b = blockIdx.y;
     const int N = p.n, D = p.decim, M = p.channels, L = M * p.taps_per_channel, H = L - 1;
@@ -122,16 +113,8 @@ __global__ __launch_bounds__(CHAN_THREADS) void chan_kernel(const char *__restri
     f2 *orows = reinterpret_cast<f2 *>(out) + (size_t)b * (size_t)p.n_channels * (size_t)p.cap;
 
     if ((int)blockIdx.x == p.n_tiles) {  // the new history and the zero tails of the written rows
-        f2 *hist_new = reinterpret_cast<f2 *>(p.hist_new) + (size_t)b * (size_t)H;
-        for (int i = tid; i < H; i += CHAN_THREADS) {
-            const int t = N - H + i;
-            f2 v = {0.0f, 0.0f};
-            if (t >= 0)
-                v = chan_sample<FMT>(frame, t);
-            else if (hist_old)
-                v = hist_old[t + H];
-            hist_new[i] = v;
-        }
+        carry_history<CHAN_THREADS>(reinterpret_cast<f2 *>(p.hist_new) + (size_t)b * (size_t)H, hist_old, N, H, tid,
+                                    [&](int t) { return f2{load_i1<FMT>(frame, t), load_q1<FMT>(frame, t)}; });
         const int z = p.cap - p.n_out;
         for (int i = tid; i < z * p.n_channels; i += CHAN_THREADS)
             orows[(size_t)(i / z) * (size_t)p.cap + (size_t)(p.n_out + i % z)] = f2{0.0f, 0.0f};
@@ -145,34 +128,7 @@ __global__ __launch_bounds__(CHAN_THREADS) void chan_kernel(const char *__restri
     f2 *smp = chan_lds;                      // the window; later the transposed spectra
     f2 *U = chan_lds + p.region;             // [tile][M + 1]: branch sums, then the DFT's intermediate
 
-    // the part before the frame: history (zeros after a restart)
-    const int n_hist = min(max(-w0, 0), count);
-    for (int u = tid; u < n_hist; u += CHAN_THREADS) {
-        f2 v = {0.0f, 0.0f};
-        if (hist_old) v = hist_old[w0 + u + H];
-        smp[u] = v;
-    }
-    // the part inside the frame, in 16-byte chunks aligned in memory.  (A lane's 8, 4 or 2 stores land 64 bytes from
-    // its neighbour's in this linear image; one sample per lane and step, with conflict-free stores, measured 14 to
-    // 33 % slower all the same: the loads' latency, not the stores, is what a tile waits for.  DESIGN.md §3.14.)
-    if (n_hist < count) {
-        const int t_lo = w0 + n_hist, t_hi = w0 + count;  // [t_lo, t_hi) of the frame
-        const uintptr_t a = reinterpret_cast<uintptr_t>(frame) + (size_t)t_lo * BPS;
-        const int mis = p.vec_ok ? (int)((a & 15) / BPS) : 0;
-        const int n_chunks = (t_hi - t_lo + mis + SPC - 1) / SPC;
-        for (int c = tid; c < n_chunks; c += CHAN_THREADS) {
-            const int tc = t_lo - mis + c * SPC;  // the chunk's first sample
-            if (p.vec_ok && tc >= t_lo && tc + SPC <= t_hi) {
-                const uint4 raw = *reinterpret_cast<const uint4 *>(frame + (size_t)tc * BPS);
-                const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
-                f2 *dst = smp + (tc - w0);
-#pragma unroll
-                for (int s = 0; s < SPC; s++) dst[s] = chan_unpack<FMT>(w, s);
-            } else {  // a chunk across an end of the window, or an iq base that is not sample-aligned
-                for (int t = max(tc, t_lo); t < min(tc + SPC, t_hi); t++) smp[t - w0] = chan_sample<FMT>(frame, t);
-            }
-        }
-    }
+    stage_iq_window<FMT, CHAN_THREADS>(frame, hist_old, w0, count, H, p.vec_ok, tid, ChanSink<FMT>{smp});
     __syncthreads();
 
     // branch sums.  Output times past nj of a last tile read words of the window's region that hold nothing of this
@@ -262,15 +218,9 @@ hipError_t launch_channelizer(const void *iq, int fmt, int n_streams, const Chan
     p.region = std::max((p.tile - 1) * p.decim + M * P, M * (p.tile + 1));
     const size_t lds = sizeof(float) * 2 * ((size_t)p.region + (size_t)p.tile * (size_t)(M + 1));
     if (lds > (size_t)CHAN_LDS_BYTES) return hipErrorInvalidValue;
-    int bps;
-    void (*k)(const char *, ChanParams, float *);
-    switch (fmt) {
-    case SDRG_IQ_CS8: k = chan_kernel<SDRG_IQ_CS8>, bps = 2; break;
-    case SDRG_IQ_CU8: k = chan_kernel<SDRG_IQ_CU8>, bps = 2; break;
-    case SDRG_IQ_CS16: k = chan_kernel<SDRG_IQ_CS16>, bps = 4; break;
-    case SDRG_IQ_CF32: k = chan_kernel<SDRG_IQ_CF32>, bps = 8; break;
-    default: return hipErrorInvalidValue;
-    }
+    void (*k)(const char *, ChanParams, float *) = nullptr;
+    const int bps = for_iq_format(fmt, [&](auto f) { k = chan_kernel<decltype(f)::value>; });
+    if (bps == 0) return hipErrorInvalidValue;
     // rows of whole samples from a sample-aligned base: no sample straddles a 16-byte chunk
     p.vec_ok = reinterpret_cast<uintptr_t>(iq) % (size_t)bps == 0;
     hipLaunchKernelGGL(k, dim3((unsigned)p.n_tiles + 1, (unsigned)n_streams), dim3(CHAN_THREADS), lds, stream,

@@ -14,16 +14,13 @@
 //                store whole rows (256 contiguous bytes per instruction, LDS banks lane), and lane l < DEMOD_GROUP
 //                walks row l (banks (l + j) mod 32: no conflicts).  The loads of the next tile are issued before the
 //                chain of this one.  In place: a workgroup reads and writes the rows of its own streams only.
-//   FIR          the DDC's tile form on a real signal: grid (tiles of outputs + 1, streams); the workgroup stages the
-//                (nj - 1) R + T2 values its outputs read into LDS in the polyphase layout [u mod R][u / R] (rows of an
-//                odd number of dwords; at tap k the wave reads one row at consecutive columns), indices below 0 from
-//                the history; then one output per lane, k ascending, taps from LDS.  The last workgroup of a stream
-//                (blockIdx.x == n_tiles) writes the new history and the zero tail of out.
+//   FIR          the tile form of fir_tile.h (grid, history, polyphase FIR) on the real values v of the scratch row,
+//                H = T2 - 1: the workgroup stages the (nj - 1) R + T2 values its outputs read one per lane and step, the
+//                polyphase position advanced without a division; the gain and the quantisation follow the sum.
 // No workgroup reads what another writes in the same launch.  Compiled with -ffp-contract=off: every product, sum,
 // quotient and root is rounded on its own; `/` and sqrtf are the compiler's correctly rounded, denormal-keeping
 // sequences (tests/cpp/demod_math.hip checks them against IEEE on the device).
-#include <algorithm>
-
+#include "fir_tile.h"
 #include "sdrg_internal.h"
 
 namespace sdrg {
@@ -187,18 +184,9 @@ __global__ __launch_bounds__(DEMOD_THREADS) void demod_fir_kernel(DemodParams p,
     out_t *orow = static_cast<out_t *>(out) + (size_t)b * (size_t)p.cap;
 
     if ((int)blockIdx.x == p.n_tiles) {  // the new history (a call without samples keeps the old one) and the zero tail
-        if (N > 0) {
-            float *hist_new = p.hist_new + (size_t)b * (size_t)H;
-            for (int i = tid; i < H; i += DEMOD_THREADS) {
-                const int t = N - H + i;
-                float x = 0.0f;
-                if (t >= 0)
-                    x = v[t];
-                else if (hist_old)
-                    x = hist_old[t + H];
-                hist_new[i] = x;
-            }
-        }
+        if (N > 0)
+            carry_history<DEMOD_THREADS>(p.hist_new + (size_t)b * (size_t)H, hist_old, N, H, tid,
+                                        [&](int t) { return v[t]; });
         for (int j = p.n_out + tid; j < p.cap; j += DEMOD_THREADS) orow[j] = (out_t)0;
         return;
     }
@@ -226,45 +214,12 @@ __global__ __launch_bounds__(DEMOD_THREADS) void demod_fir_kernel(DemodParams p,
     }
     __syncthreads();
 
-    // output j0 + tid: acc = acc + h[k] * v[u], u = tid R + (T - 1 - k), k ascending
-    if (tid < nj) {
-        constexpr int AHEAD = 8;  // LDS reads in flight per lane: the sums are one chain, the reads are not
-        float acc = 0.0f;
-        int r = H % R;                         // wave-uniform: the row of tap k
-        int at = (H % R) * row + H / R + tid;  // [u mod R][u / R] of this lane at k = 0
-        const int wrap = (R - 1) * row - 1;
-        int k = 0;
-        for (; k + AHEAD <= T; k += AHEAD) {
-            float x[AHEAD];
-            const float4 ha = *reinterpret_cast<const float4 *>(tap_lds + k);
-            const float4 hb = *reinterpret_cast<const float4 *>(tap_lds + k + 4);
-            const float h[AHEAD] = {ha.x, ha.y, ha.z, ha.w, hb.x, hb.y, hb.z, hb.w};
-#pragma unroll
-            for (int i = 0; i < AHEAD; i++) {
-                x[i] = smp[at];
-                at += r == 0 ? wrap : -row;
-                r = r == 0 ? R - 1 : r - 1;
-            }
-#pragma unroll
-            for (int i = 0; i < AHEAD; i++) acc = acc + h[i] * x[i];
-        }
-        for (; k < T; k++) {
-            acc = acc + tap_lds[k] * smp[at];
-            at += r == 0 ? wrap : -row;
-            r = r == 0 ? R - 1 : r - 1;
-        }
-        orow[j0 + tid] = DemodOut<FMT>::make(acc * p.gain);
-    }
+    if (tid < nj) orow[j0 + tid] = DemodOut<FMT>::make(polyphase_fir(tap_lds, smp, T, R, row, tid) * p.gain);
 }
 
 }  // namespace
 
-int demod_tile_outputs(int decim, int taps) {
-    int max_row = DEMOD_LDS_SAMPLES / decim;
-    if ((max_row & 1) == 0) max_row--;
-    const int t = std::min(DEMOD_THREADS, max_row - (taps + decim - 1) / decim + 1);
-    return t > 64 ? t & ~63 : t;  // whole waves in the FIR phase
-}
+int demod_tile_outputs(int decim, int taps) { return fir_tile_outputs(DEMOD_LDS_SAMPLES, DEMOD_THREADS, decim, taps); }
 
 hipError_t launch_demod(const float *chan, int n_streams, const DemodParams &p0, const DemodTaps &taps, void *out,
                         hipStream_t stream) {

@@ -26,6 +26,7 @@
 #include <tuple>
 #include <vector>
 
+#include "decim_cursor.h"
 #include "design.h"
 #include "pulse_bank.h"
 #include "sdrg_internal.h"
@@ -126,6 +127,13 @@ struct EvSet {
     bool ssb_timed = false;  // ssb0 recorded: this call's SSB duration is measured from its own start marker
     int64_t seq = -1;        // the call's number among ALL calls (pipelined SSB: interval to call seq - 1, if profiled)
     bool stats_marked = false;  // `stats` recorded after the statistics (joined calls, whose `end` follows the join)
+};
+
+// a device allocation of n values that only grows (ensure_device)
+template <typename T>
+struct DeviceBuf {
+    T *p = nullptr;
+    size_t n = 0;
 };
 
 }  // namespace
@@ -306,49 +314,32 @@ struct sdrg_engine {
     // DDC stage (sdrg_engine_set_ddc / ddc_device / ddc_host; ddc.hip)
     sdrg_ddc_config ddc{};
     bool ddc_set = false;
-    uint64_t ddc_g0 = 0;        // samples every stream has consumed since the last restart
-    bool ddc_fresh = true;      // the next call starts from a history of zeros
-    int ddc_half = 0;           // the half of d_ddc_hist the next call reads
+    DecimCursor ddc_cur;
     uint32_t ddc_fs = 0;        // the sample rate of the previous ddc call (0: none since set_ddc)
-    float *d_ddc_hist = nullptr;  // [2][n_streams][taps - 1][2]: the mixed samples before the next frame, ping-pong
-    size_t ddc_hist_elems = 0;
-    float *d_ddc_w = nullptr;     // [N][2]: the phasors of the frame in flight, shared by the streams
-    size_t ddc_w_elems = 0;
+    PingPong<float> ddc_hist;   // halves of [n_streams][taps - 1][2]: the mixed samples before the next frame
+    DeviceBuf<float> ddc_w;     // [N][2]: the phasors of the frame in flight, shared by the streams
     uint32_t ddc_taps_fs = 0;   // the sample rate ddc_taps was designed for (0: not designed)
     DdcTaps ddc_taps{};
-    void *d_ddc_in = nullptr;   // ddc_host's copy of the caller's iq
-    size_t ddc_in_bytes = 0;
-    float *d_ddc_out = nullptr;  // ddc_host's rows
-    size_t ddc_out_elems = 0;
+    DeviceBuf<char> ddc_in;     // ddc_host's copy of the caller's iq
+    DeviceBuf<float> ddc_out;   // ddc_host's rows
     // demodulator stage (sdrg_engine_set_demod / demod_device / demod_host / ddc_demod_host; demod.hip)
     sdrg_demod_config demod{};
     bool demod_set = false;
-    uint64_t demod_g = 0;        // samples every stream has consumed since the last restart
-    bool demod_fresh = true;     // the next call starts from a state of zeros
-    int demod_half = 0;          // the half of d_demod_state the next call reads
+    DecimCursor demod_cur;
     float demod_kf = 0.0f, demod_alpha = 0.0f, demod_a = 0.0f;  // demod_design of `demod`
     DemodTaps demod_taps{};
-    float *d_demod_state = nullptr;  // [2]{[n_streams][4]: wr, wi, m, s; [n_streams][T2 - 1]: v}, ping-pong
-    size_t demod_state_elems = 0;
-    float *d_demod_scratch = nullptr;  // [n_streams][max_in]: e, then v, of the call in flight
-    size_t demod_scratch_elems = 0;
-    float *d_demod_in = nullptr;   // demod_host's copy of the caller's rows
-    size_t demod_in_elems = 0;
-    char *d_demod_out = nullptr;   // demod_host's and ddc_demod_host's audio rows
-    size_t demod_out_bytes = 0;
+    PingPong<float> demod_state;     // halves of {[n_streams][4]: wr, wi, m, s; [n_streams][T2 - 1]: v}
+    DeviceBuf<float> demod_scratch;  // [n_streams][max_in]: e, then v, of the call in flight
+    DeviceBuf<float> demod_in;       // demod_host's copy of the caller's rows
+    DeviceBuf<char> demod_out;       // demod_host's and ddc_demod_host's audio rows
     // channelizer stage (sdrg_engine_set_channelizer / channelizer_device / channelizer_host; channelizer.hip)
     sdrg_channelizer_config chan{};
     bool chan_set = false;
-    uint64_t chan_g0 = 0;        // samples every stream has consumed since the last restart
-    bool chan_fresh = true;      // the next call starts from a history of zeros
-    int chan_half = 0;           // the half of d_chan_hist the next call reads
-    float *d_chan_hist = nullptr;  // [2][n_streams][L - 1][2]: the unpacked samples before the next frame, ping-pong
-    size_t chan_hist_elems = 0;
+    DecimCursor chan_cur;
+    PingPong<float> chan_hist;     // halves of [n_streams][L - 1][2]: the unpacked samples before the next frame
     float *d_chan_taps = nullptr;  // [L] taps, then [CHAN_TWIDDLES][2]: written by set_channelizer
-    void *d_chan_in = nullptr;     // channelizer_host's copy of the caller's iq
-    size_t chan_in_bytes = 0;
-    float *d_chan_out = nullptr;   // channelizer_host's rows
-    size_t chan_out_elems = 0;
+    DeviceBuf<char> chan_in;       // channelizer_host's copy of the caller's iq
+    DeviceBuf<float> chan_out;     // channelizer_host's rows
 };
 
 namespace {
@@ -397,6 +388,35 @@ int32_t ensure_device(T **p, size_t *have, size_t need, bool zero = false) {
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), need * sizeof(T)));
     if (zero) HIP_TRY(memset_sync(*p, 0, need * sizeof(T)));
     *have = need;
+    return SDRG_OK;
+}
+
+template <typename T>
+int32_t ensure_device(DeviceBuf<T> *b, size_t need) {
+    return ensure_device(&b->p, &b->n, need);
+}
+
+// Both halves of a decimating stage's ping-pong buffer.  Only another configuration asks for more, and setting one
+// restarts the streams: nothing to keep.  Never empty: a launcher wants a pointer even to a history of no values.
+template <typename T>
+int32_t ensure_device(PingPong<T> *b, size_t half_elems) {
+    return ensure_device(&b->p, &b->n, std::max<size_t>(2 * half_elems, 2));
+}
+
+// One host call of a stage on the main stream: the caller's `in` to the staging buffer, enqueue(staged input, device
+// rows), the rows to the caller's `out`, and the wait.  Every refusal has come before: this allocates and copies.
+template <typename TI, typename TO, typename Enqueue>
+int32_t host_round_trip(sdrg_engine *e, DeviceBuf<TI> *d_in, const void *in, size_t in_elems, DeviceBuf<TO> *d_out,
+                        void *out, size_t out_elems, Enqueue enqueue) {
+    int32_t rc = ensure_device(d_in, in_elems);
+    if (rc) return rc;
+    rc = ensure_device(d_out, out_elems);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_in->p, in, sizeof(TI) * in_elems, hipMemcpyHostToDevice, e->s_main));
+    rc = enqueue(d_in->p, d_out->p);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, d_out->p, sizeof(TO) * out_elems, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
     return SDRG_OK;
 }
 
@@ -1099,9 +1119,9 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     void *bufs[] = {e->d_stats, e->d_ssb, e->d_twiddles, e->d_taps, e->d_nco_tab, e->d_chunk_table, e->d_ssb_scratch,
                     e->d_spec_scratch, e->d_fft_scratch, e->d_pool, e->d_rec_scratch, e->d_iq_stage, e->d_spec_stage,
                     e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->d_disp_in, e->d_disp_out,
-                    e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out, e->d_peaks_in, e->d_peaks_out, e->d_ddc_hist,
-                    e->d_ddc_w, e->d_ddc_in, e->d_ddc_out, e->d_demod_state, e->d_demod_scratch, e->d_demod_in,
-                    e->d_demod_out, e->d_chan_hist, e->d_chan_taps, e->d_chan_in, e->d_chan_out};
+                    e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out, e->d_peaks_in, e->d_peaks_out, e->ddc_hist.p,
+                    e->ddc_w.p, e->ddc_in.p, e->ddc_out.p, e->demod_state.p, e->demod_scratch.p, e->demod_in.p,
+                    e->demod_out.p, e->chan_hist.p, e->d_chan_taps, e->chan_in.p, e->chan_out.p};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
@@ -1968,8 +1988,7 @@ int32_t sdrg_ddc_tile_outputs(int32_t decimation, int32_t taps, int32_t *tile) {
 }
 
 static void ddc_restart(sdrg_engine *e) {
-    e->ddc_g0 = 0;
-    e->ddc_fresh = true;
+    e->ddc_cur.restart();
     e->ddc_fs = 0;
 }
 
@@ -1993,7 +2012,7 @@ int32_t sdrg_engine_get_ddc(const sdrg_engine *e, sdrg_ddc_config *cfg, uint32_t
     if (!e->ddc_set) return fail(SDRG_E_INVALID, "no ddc configuration set");
     if (cfg) *cfg = e->ddc;
     if (nco_increment_out) *nco_increment_out = nco_increment(e->ddc.offset_hz, (uint32_t)e->cfg.sample_rate);
-    if (samples_consumed) *samples_consumed = e->ddc_g0;
+    if (samples_consumed) *samples_consumed = e->ddc_cur.g;
     return SDRG_OK;
 }
 
@@ -2006,14 +2025,14 @@ int32_t sdrg_engine_ddc_reset(sdrg_engine *e) {
 int32_t sdrg_engine_ddc_max_out(const sdrg_engine *e, int32_t *cap) {
     if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
     if (!e->ddc_set) return fail(SDRG_E_INVALID, "no ddc configuration set (sdrg_engine_set_ddc)");
-    *cap = (e->cfg.samples_per_reading + e->ddc.decimation - 1) / e->ddc.decimation;
+    *cap = DecimCursor::cap(e->cfg.samples_per_reading, e->ddc.decimation);
     return SDRG_OK;
 }
 
 // what one ddc call needs beside its buffers, resolved before anything is touched
 struct DdcCall {
     uint32_t fs;
-    bool restart;  // the sample rate changed since the previous ddc call
+    DecimCursor cur;  // where the call starts: the engine's, restarted if the sample rate changed since the previous call
     int n, cap, n_out;
 };
 
@@ -2023,11 +2042,11 @@ static int32_t ddc_resolve(const sdrg_engine *e, int32_t fmt, DdcCall *c) {
     c->fs = (uint32_t)e->cfg.sample_rate;
     if (e->ddc.cutoff_hz > (double)c->fs / 2.0)
         return fail(SDRG_E_INVALID, "ddc cutoff %g Hz above half the sample rate %u", e->ddc.cutoff_hz, c->fs);
-    c->restart = e->ddc_fs != 0 && e->ddc_fs != c->fs;
-    const uint64_t g0 = c->restart ? 0 : e->ddc_g0, D = (uint64_t)e->ddc.decimation;
+    c->cur = e->ddc_cur;
+    if (e->ddc_fs != 0 && e->ddc_fs != c->fs) c->cur.restart();
     c->n = e->cfg.samples_per_reading;
-    c->cap = (c->n + e->ddc.decimation - 1) / e->ddc.decimation;
-    c->n_out = (int)((g0 + (uint64_t)c->n + D - 1) / D - (g0 + D - 1) / D);
+    c->cap = DecimCursor::cap(c->n, e->ddc.decimation);
+    c->n_out = c->cur.n_out(c->n, e->ddc.decimation);
     return SDRG_OK;
 }
 
@@ -2036,15 +2055,11 @@ static int32_t ddc_enqueue(sdrg_engine *e, const DdcCall &c, const void *iq, int
     const sdrg_ddc_config &cfg = e->ddc;
     const int T = cfg.taps, D = cfg.decimation;
     const size_t half = (size_t)e->n_streams * (size_t)(T - 1) * 2;
-    if (e->ddc_hist_elems < 2 * half || !e->d_ddc_hist) {
-        // only a larger T asks for more, and set_ddc restarted the streams: nothing to keep
-        int32_t rc = ensure_device(&e->d_ddc_hist, &e->ddc_hist_elems, std::max<size_t>(2 * half, 2));
-        if (rc) return rc;
-    }
-    {  // a longer frame than any before: hipFree waits for the calls that read the old row
-        int32_t rc = ensure_device(&e->d_ddc_w, &e->ddc_w_elems, 2 * (size_t)c.n);
-        if (rc) return rc;
-    }
+    int32_t rc = ensure_device(&e->ddc_hist, half);
+    if (rc) return rc;
+    // a longer frame than any before: hipFree waits for the calls that read the old row
+    rc = ensure_device(&e->ddc_w, 2 * (size_t)c.n);
+    if (rc) return rc;
     if (!e->d_nco_tab) {
         std::vector<float> tab(4096);
         nco_tables(tab.data());
@@ -2055,31 +2070,29 @@ static int32_t ddc_enqueue(sdrg_engine *e, const DdcCall &c, const void *iq, int
         ddc_design(c.fs, cfg.cutoff_hz, T, e->ddc_taps.h);
         e->ddc_taps_fs = c.fs;
     }
-    const bool fresh = c.restart || e->ddc_fresh;
-    const uint64_t g0 = c.restart ? 0 : e->ddc_g0;
     DdcParams p{};
     p.n = c.n;
     p.decim = D;
     p.taps = T;
-    p.first = (int)(((uint64_t)D - g0 % (uint64_t)D) % (uint64_t)D);
+    p.first = c.cur.first(D);
     p.n_out = c.n_out;
     p.cap = c.cap;
     p.inc = nco_increment(cfg.offset_hz, c.fs);
-    p.g0_lo = (uint32_t)g0;
+    p.g0_lo = (uint32_t)c.cur.g;
     p.nco_tab = e->d_nco_tab;
-    p.hist_old = fresh ? nullptr : e->d_ddc_hist + (size_t)e->ddc_half * half;
-    p.hist_new = e->d_ddc_hist + (size_t)(e->ddc_half ^ 1) * half;
-    p.phasors = e->d_ddc_w;
+    p.hist_old = e->ddc_hist.old(c.cur, half);
+    p.hist_new = e->ddc_hist.next(c.cur, half);
+    p.phasors = e->ddc_w.p;
     HIP_TRY(launch_ddc(iq, fmt, e->n_streams, p, e->ddc_taps, out, e->s_main));
-    e->ddc_g0 = g0 + (uint64_t)c.n;
-    e->ddc_fresh = false;
-    e->ddc_half ^= 1;
+    e->ddc_cur = c.cur;
+    e->ddc_cur.advance(c.n);
     e->ddc_fs = c.fs;
     e->display_unmarked = true;  // sdrg_engine_wait_outputs covers out as it covers display rows
     return SDRG_OK;
 }
 
-int32_t sdrg_engine_ddc_device(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+// sdrg_engine_ddc_device (iq, out in device memory) and sdrg_engine_ddc_host (in host memory)
+static int32_t ddc_call(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out, bool host) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
     DdcCall c;
@@ -2087,35 +2100,23 @@ int32_t sdrg_engine_ddc_device(sdrg_engine *e, const void *iq, int32_t fmt, void
     if (rc) return rc;
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
-    rc = ddc_enqueue(e, c, iq, fmt, static_cast<float *>(out));
+    const size_t B = (size_t)e->n_streams;
+    if (host)
+        rc = host_round_trip(e, &e->ddc_in, iq, B * (size_t)c.n * bytes_per_sample(fmt), &e->ddc_out, out, B * (size_t)c.cap * 2,
+                             [&](const char *d_iq, float *d_out) { return ddc_enqueue(e, c, d_iq, fmt, d_out); });
+    else
+        rc = ddc_enqueue(e, c, iq, fmt, static_cast<float *>(out));
     if (rc) return rc;
     *n_out = c.n_out;
     return SDRG_OK;
 }
 
+int32_t sdrg_engine_ddc_device(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    return ddc_call(e, iq, fmt, out, n_out, false);
+}
+
 int32_t sdrg_engine_ddc_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
-    DdcCall c;
-    int32_t rc = ddc_resolve(e, fmt, &c);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t in_bytes = (size_t)e->n_streams * (size_t)c.n * (size_t)bytes_per_sample(fmt);
-    const size_t out_elems = (size_t)e->n_streams * (size_t)c.cap * 2;
-    char *in = static_cast<char *>(e->d_ddc_in);
-    rc = ensure_device(&in, &e->ddc_in_bytes, in_bytes);
-    e->d_ddc_in = in;
-    if (rc) return rc;
-    rc = ensure_device(&e->d_ddc_out, &e->ddc_out_elems, out_elems);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(e->d_ddc_in, iq, in_bytes, hipMemcpyHostToDevice, e->s_main));
-    rc = ddc_enqueue(e, c, e->d_ddc_in, fmt, e->d_ddc_out);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->d_ddc_out, sizeof(float) * out_elems, hipMemcpyDeviceToHost, e->s_main));
-    HIP_TRY(hipStreamSynchronize(e->s_main));
-    *n_out = c.n_out;
-    return SDRG_OK;
+    return ddc_call(e, iq, fmt, out, n_out, true);
 }
 
 // ---- demodulator stage (demod.hip) --------------------------------------------------------------------------------
@@ -2137,11 +2138,6 @@ int32_t sdrg_demod_geometry(int32_t audio_decimation, int32_t audio_taps, int32_
     return SDRG_OK;
 }
 
-static void demod_restart(sdrg_engine *e) {
-    e->demod_g = 0;
-    e->demod_fresh = true;
-}
-
 int32_t sdrg_engine_set_demod(sdrg_engine *e, const sdrg_demod_config *cfg) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (cfg) {
@@ -2150,7 +2146,7 @@ int32_t sdrg_engine_set_demod(sdrg_engine *e, const sdrg_demod_config *cfg) {
         demod_design(*cfg, &e->demod_kf, &e->demod_alpha, &e->demod_a, e->demod_taps.h);
     }
     e->demod_set = cfg != nullptr;
-    demod_restart(e);
+    e->demod_cur.restart();
     return SDRG_OK;
 }
 
@@ -2163,19 +2159,17 @@ int32_t sdrg_engine_get_demod(const sdrg_engine *e, sdrg_demod_config *cfg, floa
     if (alpha) *alpha = e->demod_alpha;
     if (a) *a = e->demod_a;
     if (taps) std::copy(e->demod_taps.h, e->demod_taps.h + e->demod.audio_taps, taps);
-    if (samples_consumed) *samples_consumed = e->demod_g;
+    if (samples_consumed) *samples_consumed = e->demod_cur.g;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_demod_reset(sdrg_engine *e) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    demod_restart(e);
+    e->demod_cur.restart();
     return SDRG_OK;
 }
 
-static int demod_cap(const sdrg_engine *e) {
-    return (e->demod.max_in + e->demod.audio_decimation - 1) / e->demod.audio_decimation;
-}
+static int demod_cap(const sdrg_engine *e) { return DecimCursor::cap(e->demod.max_in, e->demod.audio_decimation); }
 
 int32_t sdrg_engine_demod_max_out(const sdrg_engine *e, int32_t *cap) {
     if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
@@ -2188,8 +2182,7 @@ int32_t sdrg_engine_demod_max_out(const sdrg_engine *e, int32_t *cap) {
 static int32_t demod_resolve(const sdrg_engine *e, int32_t n, int32_t *n_out) {
     if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set (sdrg_engine_set_demod)");
     if (n < 0 || n > e->demod.max_in) return fail(SDRG_E_INVALID, "demod: n %d outside [0, max_in = %d]", n, e->demod.max_in);
-    const uint64_t g = e->demod_g, R = (uint64_t)e->demod.audio_decimation;
-    *n_out = (int32_t)((g + (uint64_t)n + R - 1) / R - (g + R - 1) / R);
+    *n_out = e->demod_cur.n_out(n, e->demod.audio_decimation);
     return SDRG_OK;
 }
 
@@ -2203,25 +2196,25 @@ static int32_t demod_enqueue(sdrg_engine *e, const float *chan, int in_stride, i
     const sdrg_demod_config &cfg = e->demod;
     const int T = cfg.audio_taps, R = cfg.audio_decimation;
     const size_t B = (size_t)e->n_streams, half = B * 4 + B * (size_t)(T - 1);
-    // only another configuration asks for more, and set_demod restarted the streams: nothing to keep
-    int32_t rc = ensure_device(&e->d_demod_state, &e->demod_state_elems, 2 * half);
+    int32_t rc = ensure_device(&e->demod_state, half);
     if (rc) return rc;
-    rc = ensure_device(&e->d_demod_scratch, &e->demod_scratch_elems, B * (size_t)cfg.max_in);
+    rc = ensure_device(&e->demod_scratch, B * (size_t)cfg.max_in);
     if (rc) return rc;
-    float *old_half = e->d_demod_state + (size_t)e->demod_half * half;
-    float *new_half = e->d_demod_state + (size_t)(e->demod_half ^ 1) * half;
+    const DecimCursor &cur = e->demod_cur;
+    float *old_half = e->demod_state.half(cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    float *new_half = e->demod_state.next(cur, half);
     DemodParams p{};
     p.n = n;
     p.in_stride = in_stride;
     p.scratch_stride = cfg.max_in;
     p.decim = R;
     p.taps = T;
-    p.first = (int)(((uint64_t)R - e->demod_g % (uint64_t)R) % (uint64_t)R);
+    p.first = cur.first(R);
     p.n_out = n_out;
     p.cap = demod_cap(e);
     p.mode = cfg.mode;
     p.out_format = cfg.out_format;
-    p.fresh = e->demod_fresh ? 1 : 0;
+    p.fresh = cur.fresh ? 1 : 0;
     p.kf = e->demod_kf;
     p.alpha = e->demod_alpha;
     p.a = e->demod_a;
@@ -2230,18 +2223,15 @@ static int32_t demod_enqueue(sdrg_engine *e, const float *chan, int in_stride, i
     p.hist_old = old_half + B * 4;
     p.state_new = new_half;
     p.hist_new = new_half + B * 4;
-    p.scratch = e->d_demod_scratch;
+    p.scratch = e->demod_scratch.p;
     HIP_TRY(launch_demod(chan, e->n_streams, p, e->demod_taps, out, e->s_main));
-    if (n > 0) {  // a call without samples wrote out only: the state stays where it is
-        e->demod_g += (uint64_t)n;
-        e->demod_fresh = false;
-        e->demod_half ^= 1;
-    }
+    e->demod_cur.advance(n);  // a call without samples wrote out only: the state stays where it is
     e->display_unmarked = true;  // sdrg_engine_wait_outputs covers out as it covers display rows
     return SDRG_OK;
 }
 
-int32_t sdrg_engine_demod_device(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
+// sdrg_engine_demod_device (chan, out in device memory) and sdrg_engine_demod_host (in host memory)
+static int32_t demod_call(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out, bool host) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!chan || !out || !n_out) return fail(SDRG_E_INVALID, "null chan, out or n_out");
     int32_t count;
@@ -2249,32 +2239,24 @@ int32_t sdrg_engine_demod_device(sdrg_engine *e, const void *chan, int32_t n, vo
     if (rc) return rc;
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
-    rc = demod_enqueue(e, static_cast<const float *>(chan), e->demod.max_in, n, count, out);
+    const int stride = e->demod.max_in;
+    if (host)
+        rc = host_round_trip(
+            e, &e->demod_in, chan, (size_t)e->n_streams * (size_t)stride * 2, &e->demod_out, out, demod_out_size(e),
+            [&](const float *d_chan, char *d_out) { return demod_enqueue(e, d_chan, stride, n, count, d_out); });
+    else
+        rc = demod_enqueue(e, static_cast<const float *>(chan), stride, n, count, out);
     if (rc) return rc;
     *n_out = count;
     return SDRG_OK;
 }
 
+int32_t sdrg_engine_demod_device(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
+    return demod_call(e, chan, n, out, n_out, false);
+}
+
 int32_t sdrg_engine_demod_host(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
-    if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!chan || !out || !n_out) return fail(SDRG_E_INVALID, "null chan, out or n_out");
-    int32_t count;
-    int32_t rc = demod_resolve(e, n, &count);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t in_elems = (size_t)e->n_streams * (size_t)e->demod.max_in * 2, out_bytes = demod_out_size(e);
-    rc = ensure_device(&e->d_demod_in, &e->demod_in_elems, in_elems);
-    if (rc) return rc;
-    rc = ensure_device(&e->d_demod_out, &e->demod_out_bytes, out_bytes);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(e->d_demod_in, chan, sizeof(float) * in_elems, hipMemcpyHostToDevice, e->s_main));
-    rc = demod_enqueue(e, e->d_demod_in, e->demod.max_in, n, count, e->d_demod_out);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->d_demod_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
-    HIP_TRY(hipStreamSynchronize(e->s_main));
-    *n_out = count;
-    return SDRG_OK;
+    return demod_call(e, chan, n, out, n_out, true);
 }
 
 int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
@@ -2291,23 +2273,15 @@ int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, 
     if (rc) return rc;
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
-    const size_t in_bytes = (size_t)e->n_streams * (size_t)c.n * (size_t)bytes_per_sample(fmt);
-    const size_t chan_elems = (size_t)e->n_streams * (size_t)c.cap * 2, out_bytes = demod_out_size(e);
-    char *in = static_cast<char *>(e->d_ddc_in);
-    rc = ensure_device(&in, &e->ddc_in_bytes, in_bytes);
-    e->d_ddc_in = in;
+    const size_t B = (size_t)e->n_streams;
+    rc = ensure_device(&e->ddc_out, B * (size_t)c.cap * 2);  // the channel between the two stages
     if (rc) return rc;
-    rc = ensure_device(&e->d_ddc_out, &e->ddc_out_elems, chan_elems);
+    rc = host_round_trip(e, &e->ddc_in, iq, B * (size_t)c.n * bytes_per_sample(fmt), &e->demod_out, out, demod_out_size(e),
+                         [&](const char *d_iq, char *d_out) {
+                             int32_t r = ddc_enqueue(e, c, d_iq, fmt, e->ddc_out.p);
+                             return r ? r : demod_enqueue(e, e->ddc_out.p, c.cap, c.n_out, count, d_out);
+                         });
     if (rc) return rc;
-    rc = ensure_device(&e->d_demod_out, &e->demod_out_bytes, out_bytes);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(e->d_ddc_in, iq, in_bytes, hipMemcpyHostToDevice, e->s_main));
-    rc = ddc_enqueue(e, c, e->d_ddc_in, fmt, e->d_ddc_out);
-    if (rc) return rc;
-    rc = demod_enqueue(e, e->d_ddc_out, c.cap, c.n_out, count, e->d_demod_out);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->d_demod_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
-    HIP_TRY(hipStreamSynchronize(e->s_main));
     *n_out = count;
     return SDRG_OK;
 }
@@ -2326,11 +2300,6 @@ int32_t sdrg_channelizer_tile_outputs(const sdrg_channelizer_config *cfg, int32_
     if (const char *bad = chan_check(*cfg)) return fail(SDRG_E_INVALID, "channelizer: %s", bad);
     *tile = chan_tile_outputs(cfg->channels);
     return SDRG_OK;
-}
-
-static void chan_restart(sdrg_engine *e) {
-    e->chan_g0 = 0;
-    e->chan_fresh = true;
 }
 
 int32_t sdrg_engine_set_channelizer(sdrg_engine *e, const sdrg_channelizer_config *cfg) {
@@ -2361,7 +2330,7 @@ int32_t sdrg_engine_set_channelizer(sdrg_engine *e, const sdrg_channelizer_confi
         e->chan = *cfg;
     }
     e->chan_set = cfg != nullptr;
-    chan_restart(e);
+    e->chan_cur.restart();
     return SDRG_OK;
 }
 
@@ -2369,21 +2338,20 @@ int32_t sdrg_engine_get_channelizer(const sdrg_engine *e, sdrg_channelizer_confi
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!e->chan_set) return fail(SDRG_E_INVALID, "no channelizer configuration set");
     if (cfg) *cfg = e->chan;
-    if (samples_consumed) *samples_consumed = e->chan_g0;
+    if (samples_consumed) *samples_consumed = e->chan_cur.g;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_channelizer_reset(sdrg_engine *e) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    chan_restart(e);
+    e->chan_cur.restart();
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_channelizer_max_out(const sdrg_engine *e, int32_t *cap) {
     if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
     if (!e->chan_set) return fail(SDRG_E_INVALID, "no channelizer configuration set (sdrg_engine_set_channelizer)");
-    const int D = e->chan.channels / e->chan.oversample;
-    *cap = (e->cfg.samples_per_reading + D - 1) / D;
+    *cap = DecimCursor::cap(e->cfg.samples_per_reading, e->chan.channels / e->chan.oversample);
     return SDRG_OK;
 }
 
@@ -2397,9 +2365,8 @@ static int32_t chan_resolve(const sdrg_engine *e, int32_t fmt, ChanCall *c) {
     if (bytes_per_sample(fmt) == 0) return fail(SDRG_E_INVALID, "unknown iq format %d", fmt);
     c->n = e->cfg.samples_per_reading;
     c->decim = e->chan.channels / e->chan.oversample;
-    const uint64_t g0 = e->chan_g0, D = (uint64_t)c->decim;
-    c->cap = (c->n + c->decim - 1) / c->decim;
-    c->n_out = (int)((g0 + (uint64_t)c->n + D - 1) / D - (g0 + D - 1) / D);
+    c->cap = DecimCursor::cap(c->n, c->decim);
+    c->n_out = e->chan_cur.n_out(c->n, c->decim);
     return SDRG_OK;
 }
 
@@ -2408,36 +2375,32 @@ static int32_t chan_enqueue(sdrg_engine *e, const ChanCall &c, const void *iq, i
     const sdrg_channelizer_config &cfg = e->chan;
     const size_t L = (size_t)cfg.channels * (size_t)cfg.taps_per_channel;
     const size_t half = (size_t)e->n_streams * (L - 1) * 2;
-    if (e->chan_hist_elems < 2 * half || !e->d_chan_hist) {
-        // only a larger L asks for more, and set_channelizer restarted the streams: nothing to keep
-        int32_t rc = ensure_device(&e->d_chan_hist, &e->chan_hist_elems, 2 * half);
-        if (rc) return rc;
-    }
-    const uint64_t g0 = e->chan_g0, D = (uint64_t)c.decim;
+    int32_t rc = ensure_device(&e->chan_hist, half);
+    if (rc) return rc;
+    const DecimCursor &cur = e->chan_cur;
     ChanParams p{};
     p.n = c.n;
     p.channels = cfg.channels;
     p.taps_per_channel = cfg.taps_per_channel;
     p.oversample = cfg.oversample;
     p.decim = c.decim;
-    p.first = (int)((D - g0 % D) % D);
+    p.first = cur.first(c.decim);
     p.n_out = c.n_out;
     p.cap = c.cap;
     p.first_channel = cfg.first_channel;
     p.n_channels = cfg.n_channels;
-    p.m_parity = (int)(((g0 + D - 1) / D) & 1);  // the global time of the call's first output
+    p.m_parity = (int)(cur.first_output(c.decim) & 1);
     p.taps = e->d_chan_taps;
-    p.hist_old = e->chan_fresh ? nullptr : e->d_chan_hist + (size_t)e->chan_half * half;
-    p.hist_new = e->d_chan_hist + (size_t)(e->chan_half ^ 1) * half;
+    p.hist_old = e->chan_hist.old(cur, half);
+    p.hist_new = e->chan_hist.next(cur, half);
     HIP_TRY(launch_channelizer(iq, fmt, e->n_streams, p, out, e->s_main));
-    e->chan_g0 = g0 + (uint64_t)c.n;
-    e->chan_fresh = false;
-    e->chan_half ^= 1;
+    e->chan_cur.advance(c.n);
     e->display_unmarked = true;  // sdrg_engine_wait_outputs covers out as it covers display rows
     return SDRG_OK;
 }
 
-int32_t sdrg_engine_channelizer_device(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+// sdrg_engine_channelizer_device (iq, out in device memory) and sdrg_engine_channelizer_host (in host memory)
+static int32_t chan_call(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out, bool host) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
     ChanCall c;
@@ -2445,35 +2408,24 @@ int32_t sdrg_engine_channelizer_device(sdrg_engine *e, const void *iq, int32_t f
     if (rc) return rc;
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
-    rc = chan_enqueue(e, c, iq, fmt, static_cast<float *>(out));
+    const size_t B = (size_t)e->n_streams;
+    if (host)
+        rc = host_round_trip(e, &e->chan_in, iq, B * (size_t)c.n * bytes_per_sample(fmt), &e->chan_out, out,
+                             B * (size_t)e->chan.n_channels * (size_t)c.cap * 2,
+                             [&](const char *d_iq, float *d_out) { return chan_enqueue(e, c, d_iq, fmt, d_out); });
+    else
+        rc = chan_enqueue(e, c, iq, fmt, static_cast<float *>(out));
     if (rc) return rc;
     *n_out = c.n_out;
     return SDRG_OK;
 }
 
+int32_t sdrg_engine_channelizer_device(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    return chan_call(e, iq, fmt, out, n_out, false);
+}
+
 int32_t sdrg_engine_channelizer_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
-    ChanCall c;
-    int32_t rc = chan_resolve(e, fmt, &c);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t in_bytes = (size_t)e->n_streams * (size_t)c.n * (size_t)bytes_per_sample(fmt);
-    const size_t out_elems = (size_t)e->n_streams * (size_t)e->chan.n_channels * (size_t)c.cap * 2;
-    char *in = static_cast<char *>(e->d_chan_in);
-    rc = ensure_device(&in, &e->chan_in_bytes, in_bytes);
-    e->d_chan_in = in;
-    if (rc) return rc;
-    rc = ensure_device(&e->d_chan_out, &e->chan_out_elems, out_elems);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(e->d_chan_in, iq, in_bytes, hipMemcpyHostToDevice, e->s_main));
-    rc = chan_enqueue(e, c, e->d_chan_in, fmt, e->d_chan_out);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->d_chan_out, sizeof(float) * out_elems, hipMemcpyDeviceToHost, e->s_main));
-    HIP_TRY(hipStreamSynchronize(e->s_main));
-    *n_out = c.n_out;
-    return SDRG_OK;
+    return chan_call(e, iq, fmt, out, n_out, true);
 }
 
 int32_t sdrg_engine_set_callbacks(sdrg_engine *e, const sdrg_callbacks *cbs) {

@@ -1,6 +1,6 @@
 // ssb_common.h — raw-IQ unpack, the NCO mix and LDS helpers shared by the SSB kernels (ssb.hip: the 16-stream
-// pipeline and the lane-per-stream kernels).  Unpack conventions as
-// include/sdrg.h: CS8 v/128, CU8 (v - 127.4)/128, CS16 v/32768, CF32 as is.
+// pipeline and the lane-per-stream kernels); the unpack also serves the decimating stages (fir_tile.h).  Unpack
+// conventions as include/sdrg.h: CS8 v/128, CU8 (v - 127.4)/128, CS16 v/32768, CF32 as is.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -139,6 +139,26 @@ __device__ __forceinline__ float load_q1(const char *frame, int n) {
     else if constexpr (FMT == SDRG_IQ_CS16)
         return (float)reinterpret_cast<const int16_t *>(frame)[2 * (size_t)n + 1] * (1.0f / 32768.0f);
     else return reinterpret_cast<const float *>(frame)[2 * (size_t)n + 1];
+}
+
+// sample s of a 16-byte chunk held in w (8, 4 or 2 samples by format), the expressions of load_i1 / load_q1
+template <int FMT>
+__device__ __forceinline__ void iq_chunk_unpack(const uint32_t (&w)[4], int s, float &xr, float &xi) {
+    if constexpr (FMT == SDRG_IQ_CS8) {
+        const uint32_t h = w[s >> 1] >> (16 * (s & 1));
+        xr = (float)(int8_t)(h & 0xff) * (1.0f / 128.0f);
+        xi = (float)(int8_t)((h >> 8) & 0xff) * (1.0f / 128.0f);
+    } else if constexpr (FMT == SDRG_IQ_CU8) {
+        const uint32_t h = w[s >> 1] >> (16 * (s & 1));
+        xr = ((float)(h & 0xff) - 127.4f) * (1.0f / 128.0f);
+        xi = ((float)((h >> 8) & 0xff) - 127.4f) * (1.0f / 128.0f);
+    } else if constexpr (FMT == SDRG_IQ_CS16) {
+        xr = (float)(int16_t)(w[s] & 0xffff) * (1.0f / 32768.0f);
+        xi = (float)(int16_t)(w[s] >> 16) * (1.0f / 32768.0f);
+    } else {
+        xr = __uint_as_float(w[2 * s]);
+        xi = __uint_as_float(w[2 * s + 1]);
+    }
 }
 
 // NCO variant: Re((xr + j xi) * w), w = e^{-j 2 pi ph / 2^32} = hi[ph >> 22] * lo[(ph >> 12) & 1023] with the
