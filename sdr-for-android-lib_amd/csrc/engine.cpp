@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <set>
@@ -129,7 +130,7 @@ struct EvSet {
     bool stats_marked = false;  // `stats` recorded after the statistics (joined calls, whose `end` follows the join)
 };
 
-// a device allocation of n values that only grows (ensure_device)
+// a device allocation of n values that only grows (ensure_device, ensure_device_keeping)
 template <typename T>
 struct DeviceBuf {
     T *p = nullptr;
@@ -228,8 +229,12 @@ struct sdrg_engine {
     size_t iq_stage_bytes = 0;
     float *d_spec_stage = nullptr;
     size_t spec_stage_elems = 0;
-    float *d_ss_stage = nullptr;  // signal_strength_host's copy of the caller's spectra
-    size_t ss_stage_elems = 0;
+    // The caller's spectra, [n_streams][N], of signal_strength_host, display_host, integrate_host and peaks_host.
+    // Not d_spec_stage: that one carries each stream's never-written bin N-1 of an odd N from one process_host call
+    // to the next (fft_process.cpp:92-97), which a caller's spectra must not replace.  One buffer serves the four:
+    // each of them waits on s_main before it returns, so no two uses overlap, and a call that fails after its copy
+    // was enqueued leaves that copy ordered on s_main before whatever the next call enqueues there.
+    DeviceBuf<float> spec_in;
     sdrg_frame_record *d_rec_stage = nullptr;
     int16_t *d_pcm_stage = nullptr;
     size_t pcm_stage_elems = 0;
@@ -280,13 +285,13 @@ struct sdrg_engine {
     // display stage (sdrg_engine_set_display / display_device / display_host; display.hip)
     sdrg_display_config disp{};
     bool disp_set = false;
-    float *d_disp_in = nullptr;   // display_host's copy of the caller's spectra (d_spec_stage keeps the odd-N bin N-1)
-    size_t disp_in_elems = 0;
-    unsigned char *d_disp_out = nullptr;  // display_host's rows
-    size_t disp_out_bytes = 0;
+    DeviceBuf<unsigned char> disp_out;  // the host calls' rows
     int host_spec_n = 0;          // N of the spectra the last process_host call with SPECTRUM left in d_spec_stage
-    hipEvent_t ev_display = nullptr;  // recorded by wait_outputs after a display call the waiting stream must follow
-    bool display_unmarked = false;    // a display kernel was enqueued on s_main after the last marker
+    // The device calls of the stages below (display, integration, peaks, DDC, demodulator, channelizer) write their
+    // outputs on s_main after the last process call's end marker, which is all a stream other than s_main follows.
+    // Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs on s_main for that stream to wait on.
+    hipEvent_t ev_outputs = nullptr;
+    bool outputs_unmarked = false;
     // integration stage (sdrg_engine_set_integration / integrate_device / integrate_host; integrate.hip)
     sdrg_integrate_config integ{};
     bool integ_set = false;
@@ -295,22 +300,14 @@ struct sdrg_engine {
     bool integ_seen = false;   // integ_n / _fs / _fc hold the configuration at the previous integrate call
     int integ_n = 0;
     int64_t integ_fs = 0, integ_fc = 0;
-    float *d_integ_ring = nullptr;  // MEAN / MAX: [period][integrate_slot_stride(n_streams * N)]
-    size_t integ_ring_elems = 0;
-    float *d_integ_ema = nullptr;   // EMA: y [n_streams][N]
-    size_t integ_ema_elems = 0;
-    float *d_integ_in = nullptr;    // integrate_host's copy of the caller's spectra
-    size_t integ_in_elems = 0;
-    float *d_integ_out = nullptr;   // integrate_host's rows
-    size_t integ_out_elems = 0;
-    int integ_out_n = 0;            // N of the rows the last integrate_host call left in d_integ_out
+    DeviceBuf<float> integ_ring;  // MEAN / MAX: [period][integrate_slot_stride(n_streams * N)]
+    DeviceBuf<float> integ_ema;   // EMA: y [n_streams][N]
+    DeviceBuf<float> integ_out;   // integrate_host's rows (history, as the two above: ensure_device_keeping)
+    int integ_out_n = 0;          // N of the rows the last integrate_host call left in integ_out
     // peak table stage (sdrg_engine_set_peaks / peaks_device / peaks_host; peaks.hip)
     sdrg_peaks_config peaks{};
     bool peaks_set = false;
-    float *d_peaks_in = nullptr;         // peaks_host's copy of the caller's spectra
-    size_t peaks_in_elems = 0;
-    unsigned char *d_peaks_out = nullptr;  // the host calls' tables: [n_streams][max_peaks] sdrg_peak, then the summaries
-    size_t peaks_out_bytes = 0;
+    DeviceBuf<unsigned char> peaks_out;  // the host calls' tables: [n_streams][max_peaks] sdrg_peak, then the summaries
     // DDC stage (sdrg_engine_set_ddc / ddc_device / ddc_host; ddc.hip)
     sdrg_ddc_config ddc{};
     bool ddc_set = false;
@@ -378,6 +375,8 @@ hipError_t memset_sync(void *p, int v, size_t bytes) {
     return e;
 }
 
+// Growth of a buffer that holds nothing across calls (staging, outputs, scratch): the old allocation is freed first,
+// so the two never exist together, and a call that cannot have the new one leaves the buffer empty
 template <typename T>
 int32_t ensure_device(T **p, size_t *have, size_t need, bool zero = false) {
     if (*have >= need && *p) return SDRG_OK;
@@ -385,7 +384,12 @@ int32_t ensure_device(T **p, size_t *have, size_t need, bool zero = false) {
     *p = nullptr;
     *have = 0;
     if (need == 0) return SDRG_OK;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), need * sizeof(T)));
+    const hipError_t er = hipMalloc(reinterpret_cast<void **>(p), need * sizeof(T));
+    if (er == hipErrorOutOfMemory) {  // for every growth policy: each allocates here
+        (void)hipGetLastError();
+        return fail(SDRG_E_NOMEM, "hipMalloc of %zu bytes failed", need * sizeof(T));
+    }
+    HIP_TRY(er);
     if (zero) HIP_TRY(memset_sync(*p, 0, need * sizeof(T)));
     *have = need;
     return SDRG_OK;
@@ -394,6 +398,19 @@ int32_t ensure_device(T **p, size_t *have, size_t need, bool zero = false) {
 template <typename T>
 int32_t ensure_device(DeviceBuf<T> *b, size_t need) {
     return ensure_device(&b->p, &b->n, need);
+}
+
+// Growth of a buffer that holds history (the integration stage's ring, EMA rows and output rows): the new buffer
+// first, so a call that cannot have it leaves the old one (and the history in it) as it was
+template <typename T>
+int32_t ensure_device_keeping(DeviceBuf<T> *b, size_t need) {
+    if (b->n >= need && b->p) return SDRG_OK;
+    DeviceBuf<T> grown;
+    const int32_t rc = ensure_device(&grown, need);
+    if (rc) return rc;
+    if (b->p) (void)hipFree(b->p);  // synchronises with the kernels that use it
+    *b = grown;
+    return SDRG_OK;
 }
 
 // Both halves of a decimating stage's ping-pong buffer.  Only another configuration asks for more, and setting one
@@ -416,6 +433,53 @@ int32_t host_round_trip(sdrg_engine *e, DeviceBuf<TI> *d_in, const void *in, siz
     rc = enqueue(d_in->p, d_out->p);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, d_out->p, sizeof(TO) * out_elems, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipStreamSynchronize(e->s_main));
+    return SDRG_OK;
+}
+
+// The device rows a display, integrate or peaks host call reads when its caller passes no spectra: those the last
+// process_host call left in d_spec_stage, if they are N = n bins wide.  With spectra, *d_rows stays null: a copy-in
+// to spec_in is owed, which spectra_round_trip makes.
+int32_t resolve_spectra(const sdrg_engine *e, const float *spectra, int n, const float **d_rows) {
+    if (spectra) return SDRG_OK;
+    if (!e->d_spec_stage || e->host_spec_n == 0)
+        return fail(SDRG_E_INVALID, "no spectra on the device: no sdrg_engine_process_host call with SDRG_STAGE_SPECTRUM yet");
+    if (e->host_spec_n != n)
+        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the spectra on the device were computed",
+                    e->host_spec_n, n);
+    *d_rows = e->d_spec_stage;
+    return SDRG_OK;
+}
+
+// The rows the last integrate_host call left on the device, if they are N = n bins wide
+int32_t resolve_integrated(const sdrg_engine *e, int n, const float **d_rows) {
+    if (!e->integ_out.p || e->integ_out_n == 0)
+        return fail(SDRG_E_INVALID, "no integrated rows on the device: no sdrg_engine_integrate_host call yet");
+    if (e->integ_out_n != n)
+        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the rows on the device were integrated",
+                    e->integ_out_n, n);
+    *d_rows = e->integ_out.p;
+    return SDRG_OK;
+}
+
+struct CopyOut { void *to; const void *from; size_t bytes; };  // device -> host; to == nullptr: the caller wants none
+
+// host_round_trip for the stages that read spectra, [n_streams][N] = count floats, on the main stream: the caller's
+// `spectra` to spec_in unless the source is d_rows (resolve_spectra, resolve_integrated), enqueue(source), the copies
+// out, and the wait.  Every refusal has come before, and the caller has allocated what `outs` reads from.
+template <typename Enqueue>
+int32_t spectra_round_trip(sdrg_engine *e, const float *spectra, const float *d_rows, size_t count, Enqueue enqueue,
+                           std::initializer_list<CopyOut> outs) {
+    if (!d_rows) {
+        const int32_t rc = ensure_device(&e->spec_in, count);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(e->spec_in.p, spectra, sizeof(float) * count, hipMemcpyHostToDevice, e->s_main));
+        d_rows = e->spec_in.p;
+    }
+    const int32_t rc = enqueue(d_rows);
+    if (rc) return rc;
+    for (const CopyOut &o : outs)
+        if (o.to) HIP_TRY(hipMemcpyAsync(o.to, o.from, o.bytes, hipMemcpyDeviceToHost, e->s_main));
     HIP_TRY(hipStreamSynchronize(e->s_main));
     return SDRG_OK;
 }
@@ -1118,10 +1182,10 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     e->spec_bank.detect_stream = e->audio_bank.detect_stream = nullptr;
     void *bufs[] = {e->d_stats, e->d_ssb, e->d_twiddles, e->d_taps, e->d_nco_tab, e->d_chunk_table, e->d_ssb_scratch,
                     e->d_spec_scratch, e->d_fft_scratch, e->d_pool, e->d_rec_scratch, e->d_iq_stage, e->d_spec_stage,
-                    e->d_ss_stage, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->d_disp_in, e->d_disp_out,
-                    e->d_integ_ring, e->d_integ_ema, e->d_integ_in, e->d_integ_out, e->d_peaks_in, e->d_peaks_out, e->ddc_hist.p,
-                    e->ddc_w.p, e->ddc_in.p, e->ddc_out.p, e->demod_state.p, e->demod_scratch.p, e->demod_in.p,
-                    e->demod_out.p, e->chan_hist.p, e->d_chan_taps, e->chan_in.p, e->chan_out.p};
+                    e->spec_in.p, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->disp_out.p, e->integ_ring.p,
+                    e->integ_ema.p, e->integ_out.p, e->peaks_out.p, e->ddc_hist.p, e->ddc_w.p, e->ddc_in.p, e->ddc_out.p,
+                    e->demod_state.p, e->demod_scratch.p, e->demod_in.p, e->demod_out.p, e->chan_hist.p, e->d_chan_taps,
+                    e->chan_in.p, e->chan_out.p};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
@@ -1129,7 +1193,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
         if (ev) (void)hipEventDestroy(ev);
     if (e->s_gather) (void)hipStreamSynchronize(e->s_gather);
     hipEvent_t evs[] = {e->ev_fork, e->ev_join, e->ev_in_main, e->ev_in_ssb, e->ev_fork_spec, e->ev_join_spec,
-                        e->ev_spec_done, e->ev_ap_end[0], e->ev_ap_end[1], e->ev_ap_end[2], e->ev_display};
+                        e->ev_spec_done, e->ev_ap_end[0], e->ev_ap_end[1], e->ev_ap_end[2], e->ev_outputs};
     for (hipEvent_t ev : evs)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ev_g)  // ev_gather is one of these
@@ -1220,14 +1284,14 @@ int32_t sdrg_engine_wait_outputs(sdrg_engine *e, void *hip_stream) {
     if (e->last_ap_end) HIP_TRY(hipStreamWaitEvent(s, e->last_ap_end, 0));                    // audio pulse
     if (e->stats_async && e->last_stats_end) HIP_TRY(hipStreamWaitEvent(s, e->last_stats_end, 0));  // records
     if (e->ev_gather) HIP_TRY(hipStreamWaitEvent(s, e->ev_gather, 0));  // the gathered outputs on the root
-    if (s != e->s_main) {  // display rows: enqueued on the main stream after the call's own end marker
-        if (e->display_unmarked) {
-            if (!e->ev_display)
-                HIP_TRY(hipEventCreateWithFlags(&e->ev_display, hipEventDisableTiming | hipEventDisableSystemFence));
-            HIP_TRY(hipEventRecord(e->ev_display, e->s_main));
-            e->display_unmarked = false;
+    if (s != e->s_main) {  // the later stages' outputs: enqueued on the main stream after the call's own end marker
+        if (e->outputs_unmarked) {
+            if (!e->ev_outputs)
+                HIP_TRY(hipEventCreateWithFlags(&e->ev_outputs, hipEventDisableTiming | hipEventDisableSystemFence));
+            HIP_TRY(hipEventRecord(e->ev_outputs, e->s_main));
+            e->outputs_unmarked = false;
         }
-        if (e->ev_display) HIP_TRY(hipStreamWaitEvent(s, e->ev_display, 0));
+        if (e->ev_outputs) HIP_TRY(hipStreamWaitEvent(s, e->ev_outputs, 0));
     }
     return SDRG_OK;
 }
@@ -1433,22 +1497,16 @@ int32_t sdrg_engine_signal_strength_host(sdrg_engine *e, const float *spectra, s
                                          int64_t now_ms) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!spectra || !records) return fail(SDRG_E_INVALID, "null spectra or records");
+    if (e->fft_fs == 0) return fail(SDRG_E_INVALID, "the statistics' sample rate is 0");  // signal_strength's, up front
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
-    const int n = e->cfg.samples_per_reading, B = e->n_streams;
-    // a staging buffer of its own: process_host's d_spec_stage carries each stream's never-written bin N-1 for odd N
-    // (fft_process.cpp:92-97), which the caller's spectra must not replace
-    int32_t rc = ensure_device(&e->d_ss_stage, &e->ss_stage_elems, (size_t)B * n);
-    if (rc) return rc;
+    const size_t B = (size_t)e->n_streams;
     if (!e->d_rec_stage)
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_rec_stage), sizeof(sdrg_frame_record) * (size_t)B));
-    HIP_TRY(hipMemcpyAsync(e->d_ss_stage, spectra, sizeof(float) * (size_t)B * n, hipMemcpyHostToDevice, e->s_main));
-    rc = signal_strength(e, e->d_ss_stage, e->d_rec_stage, now_ms);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(records, e->d_rec_stage, sizeof(sdrg_frame_record) * (size_t)B, hipMemcpyDeviceToHost,
-                           e->s_main));
-    HIP_TRY(hipStreamSynchronize(e->s_main));
-    return SDRG_OK;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_rec_stage), sizeof(sdrg_frame_record) * B));
+    return spectra_round_trip(
+        e, spectra, nullptr, B * (size_t)e->cfg.samples_per_reading,
+        [&](const float *src) { return signal_strength(e, src, e->d_rec_stage, now_ms); },
+        {{records, e->d_rec_stage, sizeof(sdrg_frame_record) * B}});
 }
 
 int32_t sdrg_engine_synchronize(sdrg_engine *e) {
@@ -1663,39 +1721,34 @@ int32_t sdrg_engine_display_device(sdrg_engine *e, const float *spectra, void *o
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     HIP_TRY(launch_display(spectra, e->n_streams, p, out, e->s_main));
-    e->display_unmarked = true;
+    e->outputs_unmarked = true;
     return SDRG_OK;
+}
+
+// the caller's spectra, or the device rows d_rows, -> the caller's host rows, synchronous
+static int32_t display_to_host(sdrg_engine *e, const DisplayParams &p, const float *spectra, const float *d_rows, void *out) {
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const size_t B = (size_t)e->n_streams, out_bytes = B * display_row_bytes(p);
+    const int32_t rc = ensure_device(&e->disp_out, out_bytes);
+    if (rc) return rc;
+    return spectra_round_trip(
+        e, spectra, d_rows, B * (size_t)p.n,
+        [&](const float *src) -> int32_t {
+            HIP_TRY(launch_display(src, e->n_streams, p, e->disp_out.p, e->s_main));
+            return SDRG_OK;
+        },
+        {{out, e->disp_out.p, out_bytes}});
 }
 
 int32_t sdrg_engine_display_host(sdrg_engine *e, const float *spectra, void *out) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!out) return fail(SDRG_E_INVALID, "null out");
     DisplayParams p;
+    const float *d_rows = nullptr;
     int32_t rc = display_params(e, &p);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t B = (size_t)e->n_streams, out_bytes = B * display_row_bytes(p);
-    const float *src = e->d_spec_stage;
-    if (spectra) {
-        // a staging buffer of its own, as sdrg_engine_signal_strength_host: d_spec_stage carries the odd-N bin N-1
-        rc = ensure_device(&e->d_disp_in, &e->disp_in_elems, B * (size_t)p.n);
-        if (rc) return rc;
-        src = e->d_disp_in;
-    } else if (!e->d_spec_stage || e->host_spec_n == 0) {
-        return fail(SDRG_E_INVALID, "no spectra on the device: no sdrg_engine_process_host call with SDRG_STAGE_SPECTRUM yet");
-    } else if (e->host_spec_n != p.n) {
-        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the spectra on the device were computed",
-                    e->host_spec_n, p.n);
-    }
-    rc = ensure_device(&e->d_disp_out, &e->disp_out_bytes, out_bytes);
-    if (rc) return rc;
-    if (spectra)
-        HIP_TRY(hipMemcpyAsync(e->d_disp_in, spectra, sizeof(float) * B * (size_t)p.n, hipMemcpyHostToDevice, e->s_main));
-    HIP_TRY(launch_display(src, e->n_streams, p, e->d_disp_out, e->s_main));
-    HIP_TRY(hipMemcpyAsync(out, e->d_disp_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
-    HIP_TRY(hipStreamSynchronize(e->s_main));
-    return SDRG_OK;
+    if (!rc) rc = resolve_spectra(e, spectra, p.n, &d_rows);
+    return rc ? rc : display_to_host(e, p, spectra, d_rows, out);
 }
 
 // ---- integration stage (integrate.hip) ----------------------------------------------------------------------------
@@ -1734,22 +1787,6 @@ int32_t sdrg_engine_integrate_reset(sdrg_engine *e) {
     return SDRG_OK;
 }
 
-// the new buffer first, so a call that cannot have it leaves the old one (and the history in it) as it was
-static int32_t integrate_buffer(float **p, size_t *have, size_t need) {
-    if (*have >= need && *p) return SDRG_OK;
-    float *q = nullptr;
-    const hipError_t er = hipMalloc(reinterpret_cast<void **>(&q), need * sizeof(float));
-    if (er == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        return fail(SDRG_E_NOMEM, "hipMalloc of %zu bytes for the integration stage failed", need * sizeof(float));
-    }
-    HIP_TRY(er);
-    if (*p) (void)hipFree(*p);  // synchronises with the kernels that use it
-    *p = q;
-    *have = need;
-    return SDRG_OK;
-}
-
 // one integrate call on the main stream: src, dst device [n_streams][N], dst may be src
 static int32_t integrate_enqueue(sdrg_engine *e, const float *src, float *dst) {
     const sdrg_integrate_config &c = e->integ;
@@ -1762,12 +1799,12 @@ static int32_t integrate_enqueue(sdrg_engine *e, const float *src, float *dst) {
     IntegrateParams p{c.mode, 1, 0, (int)std::min<int64_t>(t + 1, INT32_MAX), c.alpha};
     int32_t rc;
     if (c.mode == SDRG_INTEGRATE_EMA) {
-        rc = integrate_buffer(&e->d_integ_ema, &e->integ_ema_elems, count);
+        rc = ensure_device_keeping(&e->integ_ema, count);
     } else {
         p.period = c.period;
         p.slot = (int)(t % c.period);
         p.depth = (int)std::min<int64_t>(t + 1, c.period);
-        rc = integrate_buffer(&e->d_integ_ring, &e->integ_ring_elems, (size_t)c.period * stride);
+        rc = ensure_device_keeping(&e->integ_ring, (size_t)c.period * stride);
     }
     if (rc) return rc;
     // SDRG_PIPELINE_STATS_ASYNC: statistics of earlier calls may still read their spectra on s_stats; a dst that
@@ -1776,14 +1813,15 @@ static int32_t integrate_enqueue(sdrg_engine *e, const float *src, float *dst) {
         for (int k = 0; k < sdrg_engine::SA_RING; k++)
             if (e->sa_live[k] && e->sa_spec[k] < dst + count && dst < e->sa_spec[k] + count)
                 HIP_TRY(hipStreamWaitEvent(e->s_main, e->ev_stats_end[k], 0));
-    HIP_TRY(launch_integrate(src, count, p, e->d_integ_ring, stride, e->d_integ_ema, dst, e->s_main));
+    HIP_TRY(launch_integrate(src, count, p, e->integ_ring.p, stride, e->integ_ema.p, dst, e->s_main));
     e->integ_t = t + 1;
     e->integ_depth = p.depth;
     e->integ_seen = true;
     e->integ_n = n;
     e->integ_fs = e->cfg.sample_rate;
     e->integ_fc = e->cfg.center_frequency;
-    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers dst as it covers display rows
+    if (dst == e->integ_out.p) e->integ_out_n = n;  // integrate_host's rows: the _integrated_host calls read them
+    e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
@@ -1799,53 +1837,29 @@ int32_t sdrg_engine_integrate_device(sdrg_engine *e, const float *spectra, float
 int32_t sdrg_engine_integrate_host(sdrg_engine *e, const float *spectra, float *out) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!e->integ_set) return fail(SDRG_E_INVALID, "no integration configuration set (sdrg_engine_set_integration)");
+    const int n = e->cfg.samples_per_reading;
+    const float *d_rows = nullptr;
+    int32_t rc = resolve_spectra(e, spectra, n, &d_rows);
+    if (rc) return rc;
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
-    const int n = e->cfg.samples_per_reading;
     const size_t count = (size_t)e->n_streams * (size_t)n;
-    const float *src = e->d_spec_stage;
-    int32_t rc;
-    if (spectra) {  // a staging buffer of its own, as sdrg_engine_display_host
-        rc = integrate_buffer(&e->d_integ_in, &e->integ_in_elems, count);
-        if (rc) return rc;
-        src = e->d_integ_in;
-    } else if (!e->d_spec_stage || e->host_spec_n == 0) {
-        return fail(SDRG_E_INVALID, "no spectra on the device: no sdrg_engine_process_host call with SDRG_STAGE_SPECTRUM yet");
-    } else if (e->host_spec_n != n) {
-        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the spectra on the device were computed",
-                    e->host_spec_n, n);
-    }
-    rc = integrate_buffer(&e->d_integ_out, &e->integ_out_elems, count);
+    rc = ensure_device_keeping(&e->integ_out, count);
     if (rc) return rc;
-    if (spectra) HIP_TRY(hipMemcpyAsync(e->d_integ_in, spectra, sizeof(float) * count, hipMemcpyHostToDevice, e->s_main));
-    rc = integrate_enqueue(e, src, e->d_integ_out);
-    if (rc) return rc;
-    e->integ_out_n = n;  // sdrg_engine_display_integrated_host reads these rows
-    if (out) HIP_TRY(hipMemcpyAsync(out, e->d_integ_out, sizeof(float) * count, hipMemcpyDeviceToHost, e->s_main));
-    HIP_TRY(hipStreamSynchronize(e->s_main));
-    return SDRG_OK;
+    return spectra_round_trip(
+        e, spectra, d_rows, count,
+        [&](const float *src) { return integrate_enqueue(e, src, e->integ_out.p); },
+        {{out, e->integ_out.p, sizeof(float) * count}});
 }
 
 int32_t sdrg_engine_display_integrated_host(sdrg_engine *e, void *rows_out) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!rows_out) return fail(SDRG_E_INVALID, "null rows_out");
     DisplayParams p;
+    const float *d_rows = nullptr;
     int32_t rc = display_params(e, &p);
-    if (rc) return rc;
-    if (!e->d_integ_out || e->integ_out_n == 0)
-        return fail(SDRG_E_INVALID, "no integrated rows on the device: no sdrg_engine_integrate_host call yet");
-    if (e->integ_out_n != p.n)
-        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the rows on the device were integrated",
-                    e->integ_out_n, p.n);
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t out_bytes = (size_t)e->n_streams * display_row_bytes(p);
-    rc = ensure_device(&e->d_disp_out, &e->disp_out_bytes, out_bytes);
-    if (rc) return rc;
-    HIP_TRY(launch_display(e->d_integ_out, e->n_streams, p, e->d_disp_out, e->s_main));
-    HIP_TRY(hipMemcpyAsync(rows_out, e->d_disp_out, out_bytes, hipMemcpyDeviceToHost, e->s_main));
-    HIP_TRY(hipStreamSynchronize(e->s_main));
-    return SDRG_OK;
+    if (!rc) rc = resolve_integrated(e, p.n, &d_rows);
+    return rc ? rc : display_to_host(e, p, nullptr, d_rows, rows_out);
 }
 
 // ---- peak table stage (peaks.hip) ---------------------------------------------------------------------------------
@@ -1902,64 +1916,48 @@ int32_t sdrg_engine_peaks_device(sdrg_engine *e, const float *spectra, sdrg_peak
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     HIP_TRY(launch_peaks(spectra, e->n_streams, p, peaks, summary, e->s_main));
-    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers the tables as it covers display rows
+    e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
-// src (device, [n_streams][p.n]) -> the caller's host tables, synchronous
-static int32_t peaks_to_host(sdrg_engine *e, const float *src, const PeaksParams &p, sdrg_peak *peaks,
-                             sdrg_peaks_summary *summary) {
+// the caller's spectra, or the device rows d_rows, -> the caller's host tables, synchronous
+static int32_t peaks_to_host(sdrg_engine *e, const PeaksParams &p, const float *spectra, const float *d_rows,
+                             sdrg_peak *peaks, sdrg_peaks_summary *summary) {
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
     const size_t B = (size_t)e->n_streams, pk_bytes = B * (size_t)p.max_peaks * sizeof(sdrg_peak),
                  sm_bytes = B * sizeof(sdrg_peaks_summary);
-    int32_t rc = ensure_device(&e->d_peaks_out, &e->peaks_out_bytes, pk_bytes + sm_bytes);
+    const int32_t rc = ensure_device(&e->peaks_out, pk_bytes + sm_bytes);
     if (rc) return rc;
-    sdrg_peak *d_pk = reinterpret_cast<sdrg_peak *>(e->d_peaks_out);
-    sdrg_peaks_summary *d_sm = reinterpret_cast<sdrg_peaks_summary *>(e->d_peaks_out + pk_bytes);
-    HIP_TRY(launch_peaks(src, e->n_streams, p, d_pk, d_sm, e->s_main));
-    HIP_TRY(hipMemcpyAsync(peaks, d_pk, pk_bytes, hipMemcpyDeviceToHost, e->s_main));
-    HIP_TRY(hipMemcpyAsync(summary, d_sm, sm_bytes, hipMemcpyDeviceToHost, e->s_main));
-    HIP_TRY(hipStreamSynchronize(e->s_main));
-    return SDRG_OK;
+    sdrg_peak *d_pk = reinterpret_cast<sdrg_peak *>(e->peaks_out.p);
+    sdrg_peaks_summary *d_sm = reinterpret_cast<sdrg_peaks_summary *>(e->peaks_out.p + pk_bytes);
+    return spectra_round_trip(
+        e, spectra, d_rows, B * (size_t)p.n,
+        [&](const float *src) -> int32_t {
+            HIP_TRY(launch_peaks(src, e->n_streams, p, d_pk, d_sm, e->s_main));
+            return SDRG_OK;
+        },
+        {{peaks, d_pk, pk_bytes}, {summary, d_sm, sm_bytes}});
 }
 
 int32_t sdrg_engine_peaks_host(sdrg_engine *e, const float *spectra, sdrg_peak *peaks, sdrg_peaks_summary *summary) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!peaks || !summary) return fail(SDRG_E_INVALID, "null peaks or summary");
     PeaksParams p;
+    const float *d_rows = nullptr;
     int32_t rc = peaks_params(e, &p);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t count = (size_t)e->n_streams * (size_t)p.n;
-    const float *src = e->d_spec_stage;
-    if (spectra) {  // a staging buffer of its own, as sdrg_engine_display_host
-        rc = ensure_device(&e->d_peaks_in, &e->peaks_in_elems, count);
-        if (rc) return rc;
-        src = e->d_peaks_in;
-        HIP_TRY(hipMemcpyAsync(e->d_peaks_in, spectra, sizeof(float) * count, hipMemcpyHostToDevice, e->s_main));
-    } else if (!e->d_spec_stage || e->host_spec_n == 0) {
-        return fail(SDRG_E_INVALID, "no spectra on the device: no sdrg_engine_process_host call with SDRG_STAGE_SPECTRUM yet");
-    } else if (e->host_spec_n != p.n) {
-        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the spectra on the device were computed",
-                    e->host_spec_n, p.n);
-    }
-    return peaks_to_host(e, src, p, peaks, summary);
+    if (!rc) rc = resolve_spectra(e, spectra, p.n, &d_rows);
+    return rc ? rc : peaks_to_host(e, p, spectra, d_rows, peaks, summary);
 }
 
 int32_t sdrg_engine_peaks_integrated_host(sdrg_engine *e, sdrg_peak *peaks, sdrg_peaks_summary *summary) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!peaks || !summary) return fail(SDRG_E_INVALID, "null peaks or summary");
     PeaksParams p;
+    const float *d_rows = nullptr;
     int32_t rc = peaks_params(e, &p);
-    if (rc) return rc;
-    if (!e->d_integ_out || e->integ_out_n == 0)
-        return fail(SDRG_E_INVALID, "no integrated rows on the device: no sdrg_engine_integrate_host call yet");
-    if (e->integ_out_n != p.n)
-        return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the rows on the device were integrated",
-                    e->integ_out_n, p.n);
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    return peaks_to_host(e, e->d_integ_out, p, peaks, summary);
+    if (!rc) rc = resolve_integrated(e, p.n, &d_rows);
+    return rc ? rc : peaks_to_host(e, p, nullptr, d_rows, peaks, summary);
 }
 
 // ---- DDC stage (ddc.hip) ------------------------------------------------------------------------------------------
@@ -2087,7 +2085,7 @@ static int32_t ddc_enqueue(sdrg_engine *e, const DdcCall &c, const void *iq, int
     e->ddc_cur = c.cur;
     e->ddc_cur.advance(c.n);
     e->ddc_fs = c.fs;
-    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers out as it covers display rows
+    e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
@@ -2226,7 +2224,7 @@ static int32_t demod_enqueue(sdrg_engine *e, const float *chan, int in_stride, i
     p.scratch = e->demod_scratch.p;
     HIP_TRY(launch_demod(chan, e->n_streams, p, e->demod_taps, out, e->s_main));
     e->demod_cur.advance(n);  // a call without samples wrote out only: the state stays where it is
-    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers out as it covers display rows
+    e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
@@ -2395,7 +2393,7 @@ static int32_t chan_enqueue(sdrg_engine *e, const ChanCall &c, const void *iq, i
     p.hist_new = e->chan_hist.next(cur, half);
     HIP_TRY(launch_channelizer(iq, fmt, e->n_streams, p, out, e->s_main));
     e->chan_cur.advance(c.n);
-    e->display_unmarked = true;  // sdrg_engine_wait_outputs covers out as it covers display rows
+    e->outputs_unmarked = true;
     return SDRG_OK;
 }
 

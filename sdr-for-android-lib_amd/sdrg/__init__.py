@@ -212,22 +212,22 @@ class ChannelizerConfig(ctypes.Structure):
                 ("oversample", ctypes.c_int32), ("first_channel", ctypes.c_int32), ("n_channels", ctypes.c_int32)]
 
 
-def _channelizer_config(fields: dict) -> ChannelizerConfig:
-    c = ChannelizerConfig()
+def _filled(cls, what: str, fields: dict):
+    """A cls() (one of the configuration structures above) with `fields` set and the rest 0; `what` names the stage."""
+    c = cls()
     for k, v in fields.items():
-        if k not in dict(ChannelizerConfig._fields_):
-            raise TypeError(f"unknown channelizer field {k!r}")
+        if k not in dict(cls._fields_):
+            raise TypeError(f"unknown {what} field {k!r}")
         setattr(c, k, v)
     return c
 
 
-def _demod_config(fields: dict) -> DemodConfig:
-    c = DemodConfig()
-    for k, v in fields.items():
-        if k not in dict(DemodConfig._fields_):
-            raise TypeError(f"unknown demod field {k!r}")
-        setattr(c, k, v)
-    return c
+def _as_dict(c: ctypes.Structure) -> dict:
+    return {k: getattr(c, k) for k, _ in c._fields_}
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 class _Timings(ctypes.Structure):
@@ -620,7 +620,7 @@ def ddc_tile_outputs(decimation: int, taps: int) -> int:
 def demod_design(**fields) -> dict:
     """The demodulator stage's design for a configuration (host-side, no device): kf, alpha, a as np.float32 and
     taps float32 [audio_taps].  The fields are sdrg_demod_config's (fields left out are 0)."""
-    c = _demod_config(fields)
+    c = _filled(DemodConfig, "demod", fields)
     kf, alpha, a = _F(), _F(), _F()
     h = np.zeros(c.audio_taps if 0 < c.audio_taps <= DEMOD_MAX_TAPS else 1, np.float32)
     _check(load().sdrg_demod_design(ctypes.byref(c), ctypes.byref(kf), ctypes.byref(alpha), ctypes.byref(a),
@@ -639,7 +639,7 @@ def demod_geometry(audio_decimation: int, audio_taps: int) -> tuple:
 def channelizer_design(**fields) -> np.ndarray:
     """The channelizer stage's prototype for a configuration (host-side, no device): float32 [channels *
     taps_per_channel].  The fields are sdrg_channelizer_config's (fields left out are 0)."""
-    c = _channelizer_config(fields)
+    c = _filled(ChannelizerConfig, "channelizer", fields)
     L = c.channels * c.taps_per_channel
     h = np.zeros(L if 0 < L <= CHANNELIZER_MAX_TAPS else 1, np.float32)
     _check(load().sdrg_channelizer_design(ctypes.byref(c), h.ctypes.data_as(ctypes.c_void_p)), "channelizer_design")
@@ -648,7 +648,7 @@ def channelizer_design(**fields) -> np.ndarray:
 
 def channelizer_tile_outputs(**fields) -> int:
     """Consecutive output times per workgroup of the channelizer kernel for a configuration."""
-    c, t = _channelizer_config(fields), _I32()
+    c, t = _filled(ChannelizerConfig, "channelizer", fields), _I32()
     _check(load().sdrg_channelizer_tile_outputs(ctypes.byref(c), ctypes.byref(t)), "channelizer_tile_outputs")
     return t.value
 
@@ -807,9 +807,7 @@ class Engine:
         out: optional (spectra, records, pcm) arrays to write into (e.g. HostBuffer arrays, page-locked, for the
         full PCIe rate); entries for stages not run may be None.  By default fresh arrays are allocated."""
         n = self.cfg.samplesPerReading
-        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
-        if iq.size != self.n_streams * n * 2:
-            raise SdrgError(f"iq has {iq.size} values, expected {self.n_streams}x{n}x2")
+        iq = self._iq(iq, fmt)
         plen = self.pcm_len
         if out is not None:
             spec, recs, pcm = out
@@ -824,40 +822,60 @@ class Engine:
             spec = np.empty((self.n_streams, n), np.float32) if stages & STAGE_SPECTRUM else None
             recs = np.zeros(self.n_streams, RECORD_DTYPE) if stages & STAGE_STATS else None
             pcm = np.empty((self.n_streams, max(plen, 0)), np.int16) if stages & STAGE_SSB else None
-        ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-        _check(load().sdrg_engine_process_host(self._h, ptr(iq), fmt, stages, ptr(spec), ptr(recs),
-                                               ptr(pcm) if (pcm is not None and plen > 0) else None, now_ms),
-               "process_host")
+        _check(load().sdrg_engine_process_host(self._h, _ptr(iq), fmt, stages, _ptr(spec), _ptr(recs),
+                                               _ptr(pcm) if plen > 0 else None, now_ms), "process_host")
         return spec, recs, pcm
 
-    def signal_strength(self, spectra: np.ndarray, now_ms: int = 0) -> np.ndarray:
-        """evaluateSignalStrength alone on caller spectra ([n_streams][samplesPerReading] fftshifted linear power,
-        fft_process.cpp:122-379): returns the records; each stream's statistics state advances as in process()."""
+    def _iq(self, iq: np.ndarray, fmt: int) -> np.ndarray:
+        """A frame per stream, [n_streams][samplesPerReading * 2] raw samples: contiguous, in the type of fmt."""
+        n = self.cfg.samplesPerReading
+        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
+        if iq.size != self.n_streams * n * 2:
+            raise SdrgError(f"iq has {iq.size} values, expected {self.n_streams}x{n}x2")
+        return iq
+
+    def _spectra(self, spectra: np.ndarray | None):
+        """(array, its pointer) of caller spectra as contiguous float32 [n_streams][samplesPerReading], the array to be
+        kept alive over the call; (None, None) for None."""
+        if spectra is None:
+            return None, None
         n = self.cfg.samplesPerReading
         spectra = np.ascontiguousarray(spectra, dtype=np.float32)
         if spectra.shape != (self.n_streams, n):
             raise SdrgError(f"spectra {spectra.shape}: expected ({self.n_streams}, {n})")
+        return spectra, _ptr(spectra)
+
+    def _set_stage(self, cls, what: str, fields: dict) -> None:
+        """sdrg_engine_set_<what> with a cls of `fields`, or for off=True with a null configuration: the stage off."""
+        off = fields.pop("off", False)
+        if off and fields:
+            raise TypeError("off=True takes no other field")
+        c = None if off else ctypes.byref(_filled(cls, what, fields))
+        _check(getattr(load(), "sdrg_engine_set_" + what)(self._h, c), "set_" + what)
+
+    def signal_strength(self, spectra: np.ndarray, now_ms: int = 0) -> np.ndarray:
+        """evaluateSignalStrength alone on caller spectra ([n_streams][samplesPerReading] fftshifted linear power,
+        fft_process.cpp:122-379): returns the records; each stream's statistics state advances as in process()."""
+        spectra, ptr = self._spectra(np.asarray(spectra))  # no spectra are no source here: a wrong shape
         recs = np.zeros(self.n_streams, RECORD_DTYPE)
-        _check(load().sdrg_engine_signal_strength_host(self._h, spectra.ctypes.data_as(ctypes.c_void_p),
-                                                       recs.ctypes.data_as(ctypes.c_void_p), now_ms),
-               "signal_strength_host")
+        _check(load().sdrg_engine_signal_strength_host(self._h, ptr, _ptr(recs), now_ms), "signal_strength_host")
         return recs
 
     # ---- display stage ----------------------------------------------------------------------------
     def set_display(self, **fields) -> None:
         """sdrg_engine_set_display: span, first_bin, n_bins, width, reduce, format, db_min, db_max (fields left out
         are 0: the full span, MAX, float dB).  A rejected configuration leaves the previous one in force."""
-        c = DisplayConfig()
-        for k, v in fields.items():
-            if k not in dict(DisplayConfig._fields_):
-                raise TypeError(f"unknown display field {k!r}")
-            setattr(c, k, v)
+        c = _filled(DisplayConfig, "display", fields)
         _check(load().sdrg_engine_set_display(self._h, ctypes.byref(c)), "set_display")
 
     def display_config(self) -> dict:
         c = DisplayConfig()
         _check(load().sdrg_engine_get_display(self._h, ctypes.byref(c)), "get_display")
-        return {k: getattr(c, k) for k, _ in DisplayConfig._fields_}
+        return _as_dict(c)
+
+    def _display_rows(self) -> np.ndarray:
+        cfg = self.display_config()
+        return np.empty((self.n_streams, cfg["width"]), np.uint8 if cfg["format"] == DISPLAY_U8 else np.float32)
 
     def display_geometry(self) -> tuple[int, int, int]:
         """(first_bin, n_bins, row_bytes) the next display call would use."""
@@ -875,16 +893,9 @@ class Engine:
         """Host path: the display rows [n_streams][width], float32 dB or uint8 codes, of caller spectra
         ([n_streams][samplesPerReading] float32) or, with None, of the spectra the last process() call with
         STAGE_SPECTRUM left on the device."""
-        cfg = self.display_config()
-        ptr = None
-        if spectra is not None:
-            n = self.cfg.samplesPerReading
-            spectra = np.ascontiguousarray(spectra, dtype=np.float32)
-            if spectra.shape != (self.n_streams, n):
-                raise SdrgError(f"spectra {spectra.shape}: expected ({self.n_streams}, {n})")
-            ptr = spectra.ctypes.data_as(ctypes.c_void_p)
-        out = np.empty((self.n_streams, cfg["width"]), np.uint8 if cfg["format"] == DISPLAY_U8 else np.float32)
-        _check(load().sdrg_engine_display_host(self._h, ptr, out.ctypes.data_as(ctypes.c_void_p)), "display_host")
+        out = self._display_rows()
+        spectra, ptr = self._spectra(spectra)
+        _check(load().sdrg_engine_display_host(self._h, ptr, _ptr(out)), "display_host")
         return out
 
     # ---- integration stage ------------------------------------------------------------------------
@@ -918,42 +929,29 @@ class Engine:
         """Host path: feeds caller spectra ([n_streams][samplesPerReading] float32) or, with None, the spectra the
         last process() call with STAGE_SPECTRUM left on the device, and returns the integrated rows; with
         want_output=False they stay on the device (display_integrated() shows them) and None is returned."""
-        n = self.cfg.samplesPerReading
-        ptr = None
-        if spectra is not None:
-            spectra = np.ascontiguousarray(spectra, dtype=np.float32)
-            if spectra.shape != (self.n_streams, n):
-                raise SdrgError(f"spectra {spectra.shape}: expected ({self.n_streams}, {n})")
-            ptr = spectra.ctypes.data_as(ctypes.c_void_p)
-        out = np.empty((self.n_streams, n), np.float32) if want_output else None
-        _check(load().sdrg_engine_integrate_host(self._h, ptr, out.ctypes.data_as(ctypes.c_void_p) if want_output else None),
-               "integrate_host")
+        spectra, ptr = self._spectra(spectra)
+        out = np.empty((self.n_streams, self.cfg.samplesPerReading), np.float32) if want_output else None
+        _check(load().sdrg_engine_integrate_host(self._h, ptr, _ptr(out)), "integrate_host")
         return out
 
     def display_integrated(self) -> np.ndarray:
         """The display rows [n_streams][width] (current display configuration) of the rows the last integrate() call
         left on the device."""
-        cfg = self.display_config()
-        out = np.empty((self.n_streams, cfg["width"]), np.uint8 if cfg["format"] == DISPLAY_U8 else np.float32)
-        _check(load().sdrg_engine_display_integrated_host(self._h, out.ctypes.data_as(ctypes.c_void_p)),
-               "display_integrated_host")
+        out = self._display_rows()
+        _check(load().sdrg_engine_display_integrated_host(self._h, _ptr(out)), "display_integrated_host")
         return out
 
     # ---- peak table stage ------------------------------------------------------------------------
     def set_peaks(self, **fields) -> None:
         """sdrg_engine_set_peaks: span, first_bin, n_bins, max_peaks, min_separation, threshold_db (fields left out
         are 0)."""
-        c = PeaksConfig()
-        for k, v in fields.items():
-            if k not in dict(PeaksConfig._fields_):
-                raise TypeError(f"unknown peaks field {k!r}")
-            setattr(c, k, v)
+        c = _filled(PeaksConfig, "peaks", fields)
         _check(load().sdrg_engine_set_peaks(self._h, ctypes.byref(c)), "set_peaks")
 
     def peaks_config(self) -> dict:
         c = PeaksConfig()
         _check(load().sdrg_engine_get_peaks(self._h, ctypes.byref(c)), "get_peaks")
-        return {k: getattr(c, k) for k, _ in PeaksConfig._fields_}
+        return _as_dict(c)
 
     def peaks_device(self, spectra_ptr: int, peaks_ptr: int, summary_ptr: int) -> None:
         """Device path: spectra [n_streams][N] float32 in, peaks [n_streams][max_peaks] PEAK_DTYPE and summary
@@ -968,46 +966,27 @@ class Engine:
         """Host path: (peaks [n_streams][max_peaks], summary [n_streams]) of caller spectra [n_streams][N], or, with
         spectra=None, of the spectra the last process() call with STAGE_SPECTRUM left on the device."""
         pk, sm = self._peaks_out()
-        ptr = None
-        if spectra is not None:
-            spectra = np.ascontiguousarray(spectra, dtype=np.float32)
-            if spectra.shape != (self.n_streams, self.cfg.samplesPerReading):
-                raise SdrgError(f"spectra {spectra.shape}: expected ({self.n_streams}, {self.cfg.samplesPerReading})")
-            ptr = spectra.ctypes.data_as(ctypes.c_void_p)
-        _check(load().sdrg_engine_peaks_host(self._h, ptr, pk.ctypes.data_as(ctypes.c_void_p),
-                                             sm.ctypes.data_as(ctypes.c_void_p)), "peaks_host")
+        spectra, ptr = self._spectra(spectra)
+        _check(load().sdrg_engine_peaks_host(self._h, ptr, _ptr(pk), _ptr(sm)), "peaks_host")
         return pk, sm
 
     def peaks_integrated(self):
         """(peaks, summary) of the rows the last integrate() call left on the device."""
         pk, sm = self._peaks_out()
-        _check(load().sdrg_engine_peaks_integrated_host(self._h, pk.ctypes.data_as(ctypes.c_void_p),
-                                                        sm.ctypes.data_as(ctypes.c_void_p)), "peaks_integrated_host")
+        _check(load().sdrg_engine_peaks_integrated_host(self._h, _ptr(pk), _ptr(sm)), "peaks_integrated_host")
         return pk, sm
 
     # ---- DDC stage -------------------------------------------------------------------------------
     def set_ddc(self, **fields) -> None:
         """sdrg_engine_set_ddc: offset_hz, cutoff_hz, decimation, taps (fields left out are 0); set_ddc(off=True)
         switches the stage off."""
-        if fields.pop("off", False):
-            if fields:
-                raise TypeError("off=True takes no other field")
-            _check(load().sdrg_engine_set_ddc(self._h, None), "set_ddc")
-            return
-        c = DdcConfig()
-        for k, v in fields.items():
-            if k not in dict(DdcConfig._fields_):
-                raise TypeError(f"unknown ddc field {k!r}")
-            setattr(c, k, v)
-        _check(load().sdrg_engine_set_ddc(self._h, ctypes.byref(c)), "set_ddc")
+        self._set_stage(DdcConfig, "ddc", fields)
 
     def ddc_config(self) -> dict:
         """The configuration in force, plus nco_increment (at the current sample rate) and samples_consumed."""
         c, inc, g0 = DdcConfig(), ctypes.c_uint32(), ctypes.c_uint64()
         _check(load().sdrg_engine_get_ddc(self._h, ctypes.byref(c), ctypes.byref(inc), ctypes.byref(g0)), "get_ddc")
-        d = {k: getattr(c, k) for k, _ in DdcConfig._fields_}
-        d.update(nco_increment=inc.value, samples_consumed=g0.value)
-        return d
+        return dict(_as_dict(c), nco_increment=inc.value, samples_consumed=g0.value)
 
     def ddc_reset(self) -> None:
         _check(load().sdrg_engine_ddc_reset(self._h), "ddc_reset")
@@ -1027,27 +1006,17 @@ class Engine:
 
     def ddc(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
         """Host path: iq is [n_streams][samplesPerReading * 2] raw samples; returns complex64 [n_streams][n_out]."""
-        n = self.cfg.samplesPerReading
-        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
-        if iq.size != self.n_streams * n * 2:
-            raise SdrgError(f"iq has {iq.size} values, expected {self.n_streams}x{n}x2")
+        iq = self._iq(iq, fmt)
         out = np.empty((self.n_streams, self.ddc_max_out()), np.complex64)
         n_out = _I32()
-        _check(load().sdrg_engine_ddc_host(self._h, iq.ctypes.data_as(ctypes.c_void_p), fmt,
-                                           out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_out)), "ddc_host")
+        _check(load().sdrg_engine_ddc_host(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out)), "ddc_host")
         return out[:, :n_out.value]
 
     # ---- demodulator stage -----------------------------------------------------------------------
     def set_demod(self, **fields) -> None:
         """sdrg_engine_set_demod: the fields of sdrg_demod_config (fields left out are 0); set_demod(off=True) switches
         the stage off."""
-        if fields.pop("off", False):
-            if fields:
-                raise TypeError("off=True takes no other field")
-            _check(load().sdrg_engine_set_demod(self._h, None), "set_demod")
-            return
-        c = _demod_config(fields)
-        _check(load().sdrg_engine_set_demod(self._h, ctypes.byref(c)), "set_demod")
+        self._set_stage(DemodConfig, "demod", fields)
 
     def demod_config(self) -> dict:
         """The configuration in force, plus its design (kf, alpha, a as np.float32, taps) and samples_consumed."""
@@ -1056,10 +1025,8 @@ class Engine:
         _check(load().sdrg_engine_get_demod(self._h, ctypes.byref(c), ctypes.byref(kf), ctypes.byref(alpha),
                                             ctypes.byref(a), h.ctypes.data_as(ctypes.c_void_p), ctypes.byref(g)),
                "get_demod")
-        d = {k: getattr(c, k) for k, _ in DemodConfig._fields_}
-        d.update(kf=np.float32(kf.value), alpha=np.float32(alpha.value), a=np.float32(a.value),
-                 taps=h[:c.audio_taps].copy(), samples_consumed=g.value)
-        return d
+        return dict(_as_dict(c), kf=np.float32(kf.value), alpha=np.float32(alpha.value), a=np.float32(a.value),
+                    taps=h[:c.audio_taps].copy(), samples_consumed=g.value)
 
     def demod_reset(self) -> None:
         _check(load().sdrg_engine_demod_reset(self._h), "demod_reset")
@@ -1098,14 +1065,10 @@ class Engine:
     def ddc_demod(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
         """Tune and listen: iq [n_streams][samplesPerReading * 2] raw samples through the DDC and the demodulator, the
         channel left on the device; returns the audio, int16 or float32 [n_streams][n_out]."""
-        n = self.cfg.samplesPerReading
-        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
-        if iq.size != self.n_streams * n * 2:
-            raise SdrgError(f"iq has {iq.size} values, expected {self.n_streams}x{n}x2")
+        iq = self._iq(iq, fmt)
         out = self._demod_out()
         n_out = _I32()
-        _check(load().sdrg_engine_ddc_demod_host(self._h, iq.ctypes.data_as(ctypes.c_void_p), fmt,
-                                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_out)),
+        _check(load().sdrg_engine_ddc_demod_host(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out)),
                "ddc_demod_host")
         return out[:, :n_out.value]
 
@@ -1113,21 +1076,13 @@ class Engine:
     def set_channelizer(self, **fields) -> None:
         """sdrg_engine_set_channelizer: cutoff_rel, channels, taps_per_channel, oversample, first_channel, n_channels
         (fields left out are 0); set_channelizer(off=True) switches the stage off."""
-        if fields.pop("off", False):
-            if fields:
-                raise TypeError("off=True takes no other field")
-            _check(load().sdrg_engine_set_channelizer(self._h, None), "set_channelizer")
-            return
-        c = _channelizer_config(fields)
-        _check(load().sdrg_engine_set_channelizer(self._h, ctypes.byref(c)), "set_channelizer")
+        self._set_stage(ChannelizerConfig, "channelizer", fields)
 
     def channelizer_config(self) -> dict:
         """The configuration in force, plus samples_consumed."""
         c, g0 = ChannelizerConfig(), ctypes.c_uint64()
         _check(load().sdrg_engine_get_channelizer(self._h, ctypes.byref(c), ctypes.byref(g0)), "get_channelizer")
-        d = {k: getattr(c, k) for k, _ in ChannelizerConfig._fields_}
-        d.update(samples_consumed=g0.value)
-        return d
+        return dict(_as_dict(c), samples_consumed=g0.value)
 
     def channelizer_reset(self) -> None:
         _check(load().sdrg_engine_channelizer_reset(self._h), "channelizer_reset")
@@ -1150,15 +1105,11 @@ class Engine:
     def channelizer(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
         """Host path: iq is [n_streams][samplesPerReading * 2] raw samples; returns complex64
         [n_streams][n_channels][n_out]."""
-        n = self.cfg.samplesPerReading
-        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
-        if iq.size != self.n_streams * n * 2:
-            raise SdrgError(f"iq has {iq.size} values, expected {self.n_streams}x{n}x2")
+        iq = self._iq(iq, fmt)
         rows = self.channelizer_config()["n_channels"]
         out = np.empty((self.n_streams, rows, self.channelizer_max_out()), np.complex64)
         n_out = _I32()
-        _check(load().sdrg_engine_channelizer_host(self._h, iq.ctypes.data_as(ctypes.c_void_p), fmt,
-                                                   out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_out)),
+        _check(load().sdrg_engine_channelizer_host(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out)),
                "channelizer_host")
         return out[:, :, :n_out.value]
 
