@@ -887,6 +887,96 @@ int32_t sdrg_engine_channelizer_device(sdrg_engine *eng, const void *iq, int32_t
 /* Host buffers, synchronous. */
 int32_t sdrg_engine_channelizer_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the resampler stage, a polyphase rational resampler.  Per stream, the n
+ * values of a call (the demodulator's float audio, the DDC's or the channelizer's CF32 channel, or any rows in device
+ * memory) come out at exactly L / M times their rate: fs = 2 000 000 / 41 Hz audio through 123 / 125 is 48 000 Hz.
+ * Nothing depends on a rate in Hz.  Over the whole life of a stream (the calls' values concatenated, whatever their
+ * lengths) the result is that of one call; each call writes the outputs its values complete.  All arithmetic is float,
+ * every product and sum rounded on its own, unless "double" is stated; denormals are kept.  A non-finite input value
+ * makes that stream's output unspecified from then on (the history carries it).
+ *   config     interp L and decim M in [1, SDRG_RESAMPLE_MAX_FACTOR] with gcd(L, M) = 1 (a reducible pair is refused;
+ *              sdrg_resample_ratio reduces one) and 1/8 <= L / M <= 8 (larger decimations belong to the DDC and the
+ *              demodulator); taps_per_phase P in [1, SDRG_RESAMPLE_MAX_TAPS_PER_PHASE] with L P <=
+ *              SDRG_RESAMPLE_MAX_TAPS; 0 < cutoff_rel <= 1, the prototype's cutoff in units of the narrower Nyquist
+ *              band, min(in, out) rate / 2; components 1 (real float rows [n_streams][max_in]) or 2 (CF32 rows
+ *              [n_streams][max_in][2], each component resampled on its own); out_format SDRG_RESAMPLE_OUT_S16 or
+ *              SDRG_RESAMPLE_OUT_F32, applied to each component; gain finite; max_in in [1, 2^20]: the row length of
+ *              the input, every call's n <= max_in.  A rejected set_resample leaves the previous configuration and
+ *              state in force; an accepted one, and sdrg_engine_resample_reset, restart every stream: g = 0, history +0.
+ *   prototype  sdrg_resample_design, in double: with n = L P and T = n if n is odd, else n - 1, h[0 .. T - 1] is the
+ *              formula of sdrg_ddc_design with f = cutoff_rel / (2 max(L, M)) cycles per upsampled sample, scaled to
+ *              the DC gain L before its single rounding: h[k] = (float)((double)L v[k] / sum).  h[T .. n - 1] = +0.
+ *   filter     x[i] is the stream's input since the restart, x[i] = +0 for i < 0.  Output m has q = floor(m M / L) and
+ *              phi = (m M) mod L: acc = +0.0f, then for k = 0 .. P - 1 in this order
+ *              acc = acc + h[phi + k L] * x[q - k] (a rounded multiply, then a rounded add), per component.  With g
+ *              values consumed before it, a call of n writes the outputs with g <= q < g + n, the m in
+ *              [ceil(g L / M), ceil((g + n) L / M)): n_out of them, the same for every stream, possibly 0 when M > L
+ *              (the call still advances the history).  The group delay of (T - 1) / 2 upsampled samples is not
+ *              compensated.
+ *   output     o = y * gain.  SDRG_RESAMPLE_OUT_F32 writes o; SDRG_RESAMPLE_OUT_S16 writes the demodulator's
+ *              (int16_t) rintf(fminf(fmaxf(o, -1.0f), 1.0f) * 32767.0f), ties to even.  out [n_streams][cap] of float
+ *              or int16, or of pairs of them at components = 2; cap = ceil(max_in L / M).  Every byte is written by
+ *              every call, zero from n_out on.  n = 0 is a valid call: no outputs, the state unchanged.  *n_out is set
+ *              on the host before the call returns.
+ *   state      per stream the last P - 1 input values, in device memory (allocated at the first resample call), in two
+ *              halves a call reads and writes in turn; per engine g, advanced by n once the call's launch has been
+ *              issued: a failed call commits nothing.  The taps live in a device buffer, in the order [phi][k], written
+ *              by set_resample, never by a call.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_RESAMPLE_OUT_S16 0
+#define SDRG_RESAMPLE_OUT_F32 1
+#define SDRG_RESAMPLE_MAX_FACTOR 512
+#define SDRG_RESAMPLE_MAX_TAPS_PER_PHASE 64
+#define SDRG_RESAMPLE_MAX_TAPS 8192
+#define SDRG_RESAMPLE_MAX_IN 1048576
+typedef struct sdrg_resample_config {
+    double cutoff_rel;
+    int32_t interp;
+    int32_t decim;
+    int32_t taps_per_phase;
+    int32_t components;
+    int32_t out_format;
+    int32_t max_in;
+    float gain;
+} sdrg_resample_config;
+
+/* Host-only, no device.  The prototype of cfg (interp * taps_per_phase floats), after the checks of set_resample. */
+int32_t sdrg_resample_design(const sdrg_resample_config *cfg, float *taps);
+/* Host-only: how many consecutive outputs one workgroup of the resampler kernel computes for cfg: an output index of a
+ * call that is a multiple of it starts a new tile (for tests that want windows across every tile seam). */
+int32_t sdrg_resample_tile_outputs(const sdrg_resample_config *cfg, int32_t *tile);
+/* Host-only: *interp / *decim = out_hz * in_den / in_num in lowest terms, the ratio that takes the rate in_num / in_den
+ * Hz to out_hz Hz: (2 000 000, 41, 48 000) gives 123 / 125.  SDRG_E_INVALID, and nothing written, if an argument is 0
+ * or the reduced pair is outside the limits of the configuration. */
+int32_t sdrg_resample_ratio(uint64_t in_num, uint64_t in_den, uint64_t out_hz, int32_t *interp, int32_t *decim);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the resampler.  A resample call while it is off returns SDRG_E_INVALID
+ * and writes nothing. */
+int32_t sdrg_engine_set_resample(sdrg_engine *eng, const sdrg_resample_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its prototype (taps: interp * taps_per_phase floats) and g, the
+ * values every stream has consumed since the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_resample(const sdrg_engine *eng, sdrg_resample_config *cfg, float *taps,
+                                 uint64_t *samples_consumed);
+int32_t sdrg_engine_resample_reset(sdrg_engine *eng);
+/* cap = ceil(max_in L / M): the row length of `out`, in floats or int16, or pairs of them, by the configuration. */
+int32_t sdrg_engine_resample_max_out(const sdrg_engine *eng, int32_t *cap);
+/* in: n_streams rows in_stride values apart (a value is a float, or a float pair at components = 2), of which the
+ * first n of every row are this call's (0 <= n <= max_in, in_stride >= n), and out [n_streams][cap], in device memory.
+ * Reads `in` only.  Stream rules and waiting as sdrg_engine_ddc_device: runs on the main stream (the caller's after
+ * sdrg_engine_set_stream); complete after sdrg_engine_synchronize, or on a stream after sdrg_engine_wait_outputs. */
+int32_t sdrg_engine_resample_device(sdrg_engine *eng, const void *in, int32_t in_stride, int32_t n, void *out,
+                                    int32_t *n_out);
+/* Host buffers of the same shapes, synchronous; all n_streams * in_stride values of `in` are copied. */
+int32_t sdrg_engine_resample_host(sdrg_engine *eng, const void *in, int32_t in_stride, int32_t n, void *out,
+                                  int32_t *n_out);
+/* Tune and listen at the sound device's rate: sdrg_engine_ddc_demod_host's iq through the DDC, the demodulator and the
+ * resampler, the channel and the audio left on the device (the resampler's n is the demodulator's n_out); only the
+ * resampled rows out [n_streams][cap] come back.  SDRG_E_INVALID if a stage is off, the demodulator's max_in is smaller
+ * than the DDC's cap, the demodulator does not write SDRG_DEMOD_OUT_F32, or the resampler has components != 1 or a
+ * max_in smaller than the demodulator's cap; a refused call commits nothing in any stage. */
+int32_t sdrg_engine_ddc_demod_resample_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

@@ -10,6 +10,8 @@
 #include <cmath>
 #include <stdint.h>
 
+#include <algorithm>
+#include <numeric>
 #include <vector>
 
 #include "design.h"
@@ -238,8 +240,11 @@ void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h) {
     lowpass_design(cutoff_hz / (double)sample_rate, taps, h);
 }
 
-void lowpass_design(double f, int taps, float *h) {
-    std::vector<double> v((size_t)taps);  // the channelizer's prototype has up to 4095 coefficients
+void lowpass_design(double f, int taps, float *h) { lowpass_design_scaled(f, taps, 1.0, h); }
+
+// scale = 1 multiplies exactly: lowpass_design's floats are what they were as v[k] / sum
+void lowpass_design_scaled(double f, int taps, double scale, float *h) {
+    std::vector<double> v((size_t)taps);  // the resampler's prototype has up to 8192 coefficients
     double sum = 0.0;
     for (int k = 0; k < taps; k++) {
         const int c = k - (taps - 1) / 2;
@@ -248,7 +253,7 @@ void lowpass_design(double f, int taps, float *h) {
         v[k] = ideal * w;
         sum += v[k];
     }
-    for (int k = 0; k < taps; k++) h[k] = (float)(v[k] / sum);
+    for (int k = 0; k < taps; k++) h[k] = (float)(scale * v[k] / sum);
 }
 
 // The channelizer stage's configuration rules (sdrg.h): nullptr, or what is wrong
@@ -301,6 +306,52 @@ void demod_design(const sdrg_demod_config &c, float *kf, float *alpha, float *a,
     if (alpha) *alpha = (float)(1.0 - std::exp(-2.0 * M_PI * c.dc_cutoff_hz / fc));
     if (a) *a = c.deemphasis_us > 0.0 ? (float)(1.0 - std::exp(-1.0 / (fc * c.deemphasis_us * 1e-6))) : 0.0f;
     if (h) lowpass_design(c.audio_cutoff_hz / fc, c.audio_taps, h);
+}
+
+// The resampler stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *resample_check(const sdrg_resample_config &c) {
+    const int L = c.interp, M = c.decim, P = c.taps_per_phase;
+    if (L < 1 || L > SDRG_RESAMPLE_MAX_FACTOR) return "interp outside [1, 512]";
+    if (M < 1 || M > SDRG_RESAMPLE_MAX_FACTOR) return "decim outside [1, 512]";
+    if (std::gcd(L, M) != 1) return "interp and decim have a common factor (sdrg_resample_ratio reduces a ratio)";
+    if (L > 8 * M || M > 8 * L) return "interp / decim outside [1/8, 8]";
+    if (P < 1 || P > SDRG_RESAMPLE_MAX_TAPS_PER_PHASE) return "taps_per_phase outside [1, 64]";
+    if (L * P > SDRG_RESAMPLE_MAX_TAPS) return "interp * taps_per_phase above 8192";
+    if (!(c.cutoff_rel > 0.0 && c.cutoff_rel <= 1.0)) return "cutoff_rel outside (0, 1]";
+    if (c.components != 1 && c.components != 2) return "components must be 1 (real) or 2 (CF32)";
+    if (c.out_format != SDRG_RESAMPLE_OUT_S16 && c.out_format != SDRG_RESAMPLE_OUT_F32)
+        return "out_format must be SDRG_RESAMPLE_OUT_S16 or SDRG_RESAMPLE_OUT_F32";
+    if (!std::isfinite(c.gain)) return "gain must be finite";
+    if (c.max_in < 1 || c.max_in > SDRG_RESAMPLE_MAX_IN) return "max_in outside [1, 2^20]";
+    return nullptr;
+}
+
+// The resampler's prototype (sdrg.h): the DDC's low-pass of T coefficients (T = L P, less one if that is even) at
+// f = cutoff_rel / (2 max(L, M)) cycles per upsampled sample with the DC gain L, then +0
+void resample_design(const sdrg_resample_config &c, float *h) {
+    const int n = c.interp * c.taps_per_phase, T = (n & 1) ? n : n - 1;
+    lowpass_design_scaled(c.cutoff_rel / (2.0 * (double)std::max(c.interp, c.decim)), T, (double)c.interp, h);
+    for (int k = T; k < n; k++) h[k] = 0.0f;
+}
+
+// L / M = out_hz in_den / in_num in lowest terms, inside the resampler's limits
+bool resample_ratio(uint64_t in_num, uint64_t in_den, uint64_t out_hz, int *interp, int *decim) {
+    if (in_num == 0 || in_den == 0 || out_hz == 0) return false;
+    unsigned __int128 num = (unsigned __int128)out_hz * in_den, den = in_num;
+    unsigned __int128 a = num, b = den;
+    while (b != 0) {
+        const unsigned __int128 t = a % b;
+        a = b;
+        b = t;
+    }
+    num /= a;
+    den /= a;
+    if (num > SDRG_RESAMPLE_MAX_FACTOR || den > SDRG_RESAMPLE_MAX_FACTOR) return false;
+    const int L = (int)num, M = (int)den;
+    if (L > 8 * M || M > 8 * L) return false;
+    *interp = L;
+    *decim = M;
+    return true;
 }
 
 }  // namespace sdrg

@@ -21,12 +21,19 @@ const char *ddc_check(uint32_t sample_rate, double offset_hz, double cutoff_hz, 
 void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h);
 // the same low-pass at the relative cutoff f = cutoff / rate (cycles per sample)
 void lowpass_design(double f, int taps, float *h);
+// the same with the DC gain `scale`: h[k] = (float)(scale v[k] / sum), one rounding
+void lowpass_design_scaled(double f, int taps, double scale, float *h);
 // Channelizer stage: the configuration rules (nullptr = valid) and the prototype, channels * taps_per_channel floats
 const char *chan_check(const sdrg_channelizer_config &cfg);
 void chan_design(const sdrg_channelizer_config &cfg, float *h);
 // Demodulator stage: the configuration rules (nullptr = valid) and kf, alpha, a and the taps (any pointer may be null)
 const char *demod_check(const sdrg_demod_config &cfg);
 void demod_design(const sdrg_demod_config &cfg, float *kf, float *alpha, float *a, float *h);
+// Resampler stage: the configuration rules (nullptr = valid), the prototype, interp * taps_per_phase floats, and the
+// reduced ratio out_hz in_den / in_num (false: zero arguments, or outside the stage's limits)
+const char *resample_check(const sdrg_resample_config &cfg);
+void resample_design(const sdrg_resample_config &cfg, float *h);
+bool resample_ratio(uint64_t in_num, uint64_t in_den, uint64_t out_hz, int *interp, int *decim);
 // AudioPulseDetector::makeLP2 / makeHP2 (audio_pulse_detector.cpp:29-55), Q = 0.7071: {b0, b1, b2, a1, a2}
 void design_pulse_sos(float fs, float fc, bool highpass, float c[5]);
 StatsGeometry stats_geometry(uint32_t sample_rate, uint32_t center_frequency, int n, int focus_khz);

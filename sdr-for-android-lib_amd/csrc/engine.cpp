@@ -287,9 +287,10 @@ struct sdrg_engine {
     bool disp_set = false;
     DeviceBuf<unsigned char> disp_out;  // the host calls' rows
     int host_spec_n = 0;          // N of the spectra the last process_host call with SPECTRUM left in d_spec_stage
-    // The device calls of the stages below (display, integration, peaks, DDC, demodulator, channelizer) write their
-    // outputs on s_main after the last process call's end marker, which is all a stream other than s_main follows.
-    // Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs on s_main for that stream to wait on.
+    // The device calls of the stages below (display, integration, peaks, DDC, demodulator, channelizer, resampler) write
+    // their outputs on s_main after the last process call's end marker, which is all a stream other than s_main
+    // follows.  Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs on s_main for that stream
+    // to wait on.
     hipEvent_t ev_outputs = nullptr;
     bool outputs_unmarked = false;
     // integration stage (sdrg_engine_set_integration / integrate_device / integrate_host; integrate.hip)
@@ -337,6 +338,16 @@ struct sdrg_engine {
     float *d_chan_taps = nullptr;  // [L] taps, then [CHAN_TWIDDLES][2]: written by set_channelizer
     DeviceBuf<char> chan_in;       // channelizer_host's copy of the caller's iq
     DeviceBuf<float> chan_out;     // channelizer_host's rows
+    // resampler stage (sdrg_engine_set_resample / resample_device / resample_host / ddc_demod_resample_host;
+    // resample.hip)
+    sdrg_resample_config rs{};
+    bool rs_set = false;
+    ResampleCursor rs_cur;
+    std::vector<float> rs_taps;  // resample_design of `rs`: the prototype, [L P]
+    PingPong<float> rs_hist;     // halves of [n_streams][P - 1][components]: the values before the next call's
+    float *d_rs_taps = nullptr;  // the prototype in polyphase order [L][P]: written by set_resample
+    DeviceBuf<float> rs_in;      // resample_host's copy of the caller's rows
+    DeviceBuf<char> rs_out;      // resample_host's and ddc_demod_resample_host's rows
 };
 
 namespace {
@@ -1185,7 +1196,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
                     e->spec_in.p, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->disp_out.p, e->integ_ring.p,
                     e->integ_ema.p, e->integ_out.p, e->peaks_out.p, e->ddc_hist.p, e->ddc_w.p, e->ddc_in.p, e->ddc_out.p,
                     e->demod_state.p, e->demod_scratch.p, e->demod_in.p, e->demod_out.p, e->chan_hist.p, e->d_chan_taps,
-                    e->chan_in.p, e->chan_out.p};
+                    e->chan_in.p, e->chan_out.p, e->rs_hist.p, e->d_rs_taps, e->rs_in.p, e->rs_out.p};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
@@ -2424,6 +2435,201 @@ int32_t sdrg_engine_channelizer_device(sdrg_engine *e, const void *iq, int32_t f
 
 int32_t sdrg_engine_channelizer_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
     return chan_call(e, iq, fmt, out, n_out, true);
+}
+
+// ---- resampler stage (resample.hip) --------------------------------------------------------------------------------
+
+int32_t sdrg_resample_design(const sdrg_resample_config *cfg, float *taps) {
+    if (!cfg || !taps) return fail(SDRG_E_INVALID, "null resample config or taps");
+    if (const char *bad = resample_check(*cfg)) return fail(SDRG_E_INVALID, "resample: %s", bad);
+    resample_design(*cfg, taps);
+    return SDRG_OK;
+}
+
+int32_t sdrg_resample_tile_outputs(const sdrg_resample_config *cfg, int32_t *tile) {
+    if (!cfg || !tile) return fail(SDRG_E_INVALID, "null resample config or tile");
+    if (const char *bad = resample_check(*cfg)) return fail(SDRG_E_INVALID, "resample: %s", bad);
+    *tile = RESAMPLE_TILE;
+    return SDRG_OK;
+}
+
+int32_t sdrg_resample_ratio(uint64_t in_num, uint64_t in_den, uint64_t out_hz, int32_t *interp, int32_t *decim) {
+    if (!interp || !decim) return fail(SDRG_E_INVALID, "null interp or decim");
+    int L, M;
+    if (!resample_ratio(in_num, in_den, out_hz, &L, &M))
+        return fail(SDRG_E_INVALID,
+                    "resample: %llu Hz from %llu / %llu Hz is no ratio of integers in [1, 512] inside [1/8, 8]",
+                    (unsigned long long)out_hz, (unsigned long long)in_num, (unsigned long long)in_den);
+    *interp = L;
+    *decim = M;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_resample(sdrg_engine *e, const sdrg_resample_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (cfg) {
+        if (const char *bad = resample_check(*cfg)) return fail(SDRG_E_INVALID, "resample: %s", bad);
+        // the taps go into a buffer of their own, transposed to the polyphase order [phi][k] = h[phi + k L]; the old one
+        // is freed afterwards, which waits for the calls that still read it
+        const int L = cfg->interp, P = cfg->taps_per_phase;
+        std::vector<float> h((size_t)L * (size_t)P), poly(h.size());
+        resample_design(*cfg, h.data());
+        for (int phi = 0; phi < L; phi++)
+            for (int k = 0; k < P; k++) poly[(size_t)phi * (size_t)P + (size_t)k] = h[(size_t)phi + (size_t)k * (size_t)L];
+        DeviceScope dscope(e->device);
+        HIP_TRY(dscope.error());
+        float *fresh = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&fresh), sizeof(float) * poly.size()));
+        hipError_t er = hipMemcpy(fresh, poly.data(), sizeof(float) * poly.size(), hipMemcpyHostToDevice);
+        if (er != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(SDRG_E_HIP, "resample taps upload: %s", hipGetErrorString(er));
+        }
+        if (e->d_rs_taps) (void)hipFree(e->d_rs_taps);
+        e->d_rs_taps = fresh;
+        e->rs_taps.swap(h);
+        e->rs = *cfg;
+    }
+    e->rs_set = cfg != nullptr;
+    e->rs_cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_resample(const sdrg_engine *e, sdrg_resample_config *cfg, float *taps, uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!e->rs_set) return fail(SDRG_E_INVALID, "no resample configuration set");
+    if (cfg) *cfg = e->rs;
+    if (taps) std::copy(e->rs_taps.begin(), e->rs_taps.end(), taps);
+    if (samples_consumed) *samples_consumed = e->rs_cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_resample_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->rs_cur.restart();
+    return SDRG_OK;
+}
+
+static int rs_cap(const sdrg_engine *e) { return ResampleCursor::cap(e->rs.max_in, e->rs.interp, e->rs.decim); }
+
+int32_t sdrg_engine_resample_max_out(const sdrg_engine *e, int32_t *cap) {
+    if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
+    if (!e->rs_set) return fail(SDRG_E_INVALID, "no resample configuration set (sdrg_engine_set_resample)");
+    *cap = rs_cap(e);
+    return SDRG_OK;
+}
+
+// the checks of one resample call, and its n_out, before anything is touched
+static int32_t rs_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, int32_t *n_out) {
+    if (!e->rs_set) return fail(SDRG_E_INVALID, "no resample configuration set (sdrg_engine_set_resample)");
+    if (n < 0 || n > e->rs.max_in) return fail(SDRG_E_INVALID, "resample: n %d outside [0, max_in = %d]", n, e->rs.max_in);
+    if (in_stride < n) return fail(SDRG_E_INVALID, "resample: in_stride %d smaller than n %d", in_stride, n);
+    *n_out = e->rs_cur.n_out(n, e->rs.interp, e->rs.decim);
+    return SDRG_OK;
+}
+
+static size_t rs_out_size(const sdrg_engine *e) {
+    return (size_t)e->n_streams * (size_t)rs_cap(e) * (size_t)e->rs.components *
+           (e->rs.out_format == SDRG_RESAMPLE_OUT_F32 ? sizeof(float) : sizeof(int16_t));
+}
+
+// one resample call on the main stream: in (rows of in_stride values), out in device memory
+static int32_t rs_enqueue(sdrg_engine *e, const void *in, int in_stride, int n, int n_out, void *out) {
+    const sdrg_resample_config &cfg = e->rs;
+    const size_t half = (size_t)e->n_streams * (size_t)(cfg.taps_per_phase - 1) * (size_t)cfg.components;
+    int32_t rc = ensure_device(&e->rs_hist, half);
+    if (rc) return rc;
+    const ResampleCursor &cur = e->rs_cur;
+    ResampleParams p{};
+    p.n = n;
+    p.in_stride = in_stride;
+    p.interp = cfg.interp;
+    p.decim = cfg.decim;
+    p.taps_per_phase = cfg.taps_per_phase;
+    p.q0 = cur.q0(cfg.interp, cfg.decim);
+    p.phi0 = cur.phi0(cfg.interp, cfg.decim);
+    p.n_out = n_out;
+    p.cap = rs_cap(e);
+    p.components = cfg.components;
+    p.out_format = cfg.out_format;
+    p.fresh = cur.fresh ? 1 : 0;
+    p.gain = cfg.gain;
+    p.taps = e->d_rs_taps;
+    p.hist_old = e->rs_hist.old(cur, half);
+    p.hist_new = e->rs_hist.next(cur, half);
+    HIP_TRY(launch_resample(in, e->n_streams, p, out, e->s_main));
+    e->rs_cur.advance(n);  // a call without samples wrote out only: the state stays where it is
+    e->outputs_unmarked = true;
+    return SDRG_OK;
+}
+
+// sdrg_engine_resample_device (in, out in device memory) and sdrg_engine_resample_host (in host memory)
+static int32_t rs_call(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *out, int32_t *n_out, bool host) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!in || !out || !n_out) return fail(SDRG_E_INVALID, "null in, out or n_out");
+    int32_t count;
+    int32_t rc = rs_resolve(e, in_stride, n, &count);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    if (host)
+        rc = host_round_trip(e, &e->rs_in, in, (size_t)e->n_streams * (size_t)in_stride * (size_t)e->rs.components,
+                             &e->rs_out, out, rs_out_size(e),
+                             [&](const float *d_in, char *d_out) { return rs_enqueue(e, d_in, in_stride, n, count, d_out); });
+    else
+        rc = rs_enqueue(e, in, in_stride, n, count, out);
+    if (rc) return rc;
+    *n_out = count;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_resample_device(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *out,
+                                    int32_t *n_out) {
+    return rs_call(e, in, in_stride, n, out, n_out, false);
+}
+
+int32_t sdrg_engine_resample_host(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *out,
+                                  int32_t *n_out) {
+    return rs_call(e, in, in_stride, n, out, n_out, true);
+}
+
+int32_t sdrg_engine_ddc_demod_resample_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set (sdrg_engine_set_demod)");
+    if (!e->rs_set) return fail(SDRG_E_INVALID, "no resample configuration set (sdrg_engine_set_resample)");
+    DdcCall c;
+    int32_t rc = ddc_resolve(e, fmt, &c);
+    if (rc) return rc;
+    if (e->demod.max_in < c.cap)
+        return fail(SDRG_E_INVALID, "demod max_in %d smaller than the ddc's row length %d", e->demod.max_in, c.cap);
+    if (e->demod.out_format != SDRG_DEMOD_OUT_F32)
+        return fail(SDRG_E_INVALID, "the resampler reads float audio: demod out_format must be SDRG_DEMOD_OUT_F32");
+    if (e->rs.components != 1) return fail(SDRG_E_INVALID, "the resampler reads real audio: resample components must be 1");
+    const int audio_cap = demod_cap(e);
+    if (e->rs.max_in < audio_cap)
+        return fail(SDRG_E_INVALID, "resample max_in %d smaller than the demod's row length %d", e->rs.max_in, audio_cap);
+    int32_t audio, count;
+    rc = demod_resolve(e, c.n_out, &audio);
+    if (rc) return rc;
+    rc = rs_resolve(e, audio_cap, audio, &count);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    const size_t B = (size_t)e->n_streams;
+    rc = ensure_device(&e->ddc_out, B * (size_t)c.cap * 2);  // the channel between the first two stages
+    if (rc) return rc;
+    rc = ensure_device(&e->demod_out, demod_out_size(e));  // the audio between the last two
+    if (rc) return rc;
+    rc = host_round_trip(e, &e->ddc_in, iq, B * (size_t)c.n * bytes_per_sample(fmt), &e->rs_out, out, rs_out_size(e),
+                         [&](const char *d_iq, char *d_out) {
+                             int32_t r = ddc_enqueue(e, c, d_iq, fmt, e->ddc_out.p);
+                             if (!r) r = demod_enqueue(e, e->ddc_out.p, c.cap, c.n_out, audio, e->demod_out.p);
+                             return r ? r : rs_enqueue(e, e->demod_out.p, audio_cap, audio, count, d_out);
+                         });
+    if (rc) return rc;
+    *n_out = count;
+    return SDRG_OK;
 }
 
 int32_t sdrg_engine_set_callbacks(sdrg_engine *e, const sdrg_callbacks *cbs) {

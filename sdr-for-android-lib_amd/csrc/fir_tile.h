@@ -1,4 +1,5 @@
-// fir_tile.h — the tile form the decimating stages share (ddc.hip, demod.hip's FIR kernel, channelizer.hip).
+// fir_tile.h — the tile form the decimating stages share (ddc.hip, demod.hip's FIR kernel, channelizer.hip; resample.hip
+// takes its grid and carry_history, and has a filter phase per output in place of the polyphase layout below).
 //
 // A stage filters each stream with a window of H + 1 values and decimates by D.  A call's outputs j in [0, n_out) read
 // the values at the local indices t = first + j D - k, k in [0, H]; t in [0, N) is this call's frame, t in [-H, 0) the

@@ -232,4 +232,23 @@ int chan_tile_outputs(int channels);  // output times per workgroup
 hipError_t launch_channelizer(const void *iq, int fmt, int n_streams, const ChanParams &p, float *out,
                               hipStream_t stream);
 
+// Resampler stage (resample.hip): per stream and output j in [0, n_out), t = phi0 + j decim, q = q0 + t / interp,
+// phi = t mod interp, out[j] = gain * sum_k taps[phi][k] x[q - k], k in [0, taps_per_phase): x the n values at
+// in + stream * in_stride (floats, or float pairs at components 2) and, at indices in [-(taps_per_phase - 1), 0),
+// hist_old [n_streams][taps_per_phase - 1] values (fresh: zeros, not read).  Writes out [n_streams][cap] whole (zeros
+// from n_out on; float or int16 by out_format, pairs at components 2) and, if n > 0, the values at
+// [n - (taps_per_phase - 1), n) to hist_new.  taps: [interp][taps_per_phase] floats in device memory.  n_tiles is the
+// launcher's.
+struct ResampleParams {
+    int n, in_stride, interp, decim, taps_per_phase, q0, phi0, n_out, cap;
+    int components, out_format, fresh;
+    float gain;
+    const float *taps;
+    const float *hist_old;
+    float *hist_new;
+    int n_tiles;
+};
+constexpr int RESAMPLE_TILE = 256;  // outputs per workgroup, one per lane
+hipError_t launch_resample(const void *in, int n_streams, const ResampleParams &p, void *out, hipStream_t stream);
+
 }  // namespace sdrg

@@ -44,6 +44,9 @@ DEMOD_OUT_S16, DEMOD_OUT_F32 = 0, 1                                 # SDRG_DEMOD
 DEMOD_MAX_TAPS, DEMOD_MAX_DECIMATION, DEMOD_MAX_IN = 255, 64, 1 << 20  # SDRG_DEMOD_MAX_*
 CHANNELIZER_MAX_CHANNELS, CHANNELIZER_MAX_TAPS_PER_CHANNEL, CHANNELIZER_MAX_TAPS = 256, 32, 4096  # SDRG_CHANNELIZER_*
 DEMOD_OUT_DTYPE = {DEMOD_OUT_S16: np.int16, DEMOD_OUT_F32: np.float32}
+RESAMPLE_OUT_S16, RESAMPLE_OUT_F32 = 0, 1                           # SDRG_RESAMPLE_OUT_*
+RESAMPLE_MAX_FACTOR, RESAMPLE_MAX_TAPS_PER_PHASE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_IN = 512, 64, 8192, 1 << 20
+RESAMPLE_OUT_DTYPE = {RESAMPLE_OUT_S16: np.int16, RESAMPLE_OUT_F32: np.float32}
 STATUS = {0: "SDRG_OK", -1: "SDRG_E_INVALID", -2: "SDRG_E_UNSUPPORTED", -3: "SDRG_E_NOMEM", -4: "SDRG_E_HIP",
           -5: "SDRG_E_NODEVICE"}
 BYTES_PER_SAMPLE = {CF32: 8, CS8: 2, CU8: 2, CS16: 4}
@@ -132,6 +135,9 @@ EXPORTS = [
     "sdrg_channelizer_design", "sdrg_channelizer_tile_outputs", "sdrg_engine_set_channelizer",
     "sdrg_engine_get_channelizer", "sdrg_engine_channelizer_reset", "sdrg_engine_channelizer_max_out",
     "sdrg_engine_channelizer_device", "sdrg_engine_channelizer_host",
+    "sdrg_resample_design", "sdrg_resample_tile_outputs", "sdrg_resample_ratio", "sdrg_engine_set_resample",
+    "sdrg_engine_get_resample", "sdrg_engine_resample_reset", "sdrg_engine_resample_max_out",
+    "sdrg_engine_resample_device", "sdrg_engine_resample_host", "sdrg_engine_ddc_demod_resample_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -210,6 +216,14 @@ class ChannelizerConfig(ctypes.Structure):
     and the span of rows written (include/sdrg.h)."""
     _fields_ = [("cutoff_rel", ctypes.c_double), ("channels", ctypes.c_int32), ("taps_per_channel", ctypes.c_int32),
                 ("oversample", ctypes.c_int32), ("first_channel", ctypes.c_int32), ("n_channels", ctypes.c_int32)]
+
+
+class ResampleConfig(ctypes.Structure):
+    """sdrg_resample_config: the resampler stage's prototype cutoff, ratio interp / decim, taps per phase, row type,
+    output format, row length and gain (include/sdrg.h)."""
+    _fields_ = [("cutoff_rel", ctypes.c_double), ("interp", ctypes.c_int32), ("decim", ctypes.c_int32),
+                ("taps_per_phase", ctypes.c_int32), ("components", ctypes.c_int32), ("out_format", ctypes.c_int32),
+                ("max_in", ctypes.c_int32), ("gain", ctypes.c_float)]
 
 
 def _filled(cls, what: str, fields: dict):
@@ -432,6 +446,17 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_channelizer_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
         "sdrg_engine_channelizer_device": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_channelizer_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_resample_design": (_I32, [ctypes.POINTER(ResampleConfig), P]),
+        "sdrg_resample_tile_outputs": (_I32, [ctypes.POINTER(ResampleConfig), ctypes.POINTER(_I32)]),
+        "sdrg_resample_ratio": (_I32, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(_I32),
+                                       ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_resample": (_I32, [P, ctypes.POINTER(ResampleConfig)]),
+        "sdrg_engine_get_resample": (_I32, [P, ctypes.POINTER(ResampleConfig), P, ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_resample_reset": (_I32, [P]),
+        "sdrg_engine_resample_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_resample_device": (_I32, [P, P, _I32, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_resample_host": (_I32, [P, P, _I32, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_ddc_demod_resample_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -651,6 +676,35 @@ def channelizer_tile_outputs(**fields) -> int:
     c, t = _filled(ChannelizerConfig, "channelizer", fields), _I32()
     _check(load().sdrg_channelizer_tile_outputs(ctypes.byref(c), ctypes.byref(t)), "channelizer_tile_outputs")
     return t.value
+
+
+def resample_design(**fields) -> np.ndarray:
+    """The resampler stage's prototype for a configuration (host-side, no device): float32 [interp * taps_per_phase].
+    The fields are sdrg_resample_config's (fields left out are 0)."""
+    c = _filled(ResampleConfig, "resample", fields)
+    n = c.interp * c.taps_per_phase
+    h = np.zeros(n if 0 < n <= RESAMPLE_MAX_TAPS else 1, np.float32)
+    _check(load().sdrg_resample_design(ctypes.byref(c), h.ctypes.data_as(ctypes.c_void_p)), "resample_design")
+    return h
+
+
+def resample_tile_outputs(**fields) -> int:
+    """Consecutive outputs per workgroup of the resampler kernel for a configuration."""
+    c, t = _filled(ResampleConfig, "resample", fields), _I32()
+    _check(load().sdrg_resample_tile_outputs(ctypes.byref(c), ctypes.byref(t)), "resample_tile_outputs")
+    return t.value
+
+
+def resample_ratio(in_num: int, in_den: int, out_hz: int) -> tuple[int, int]:
+    """(interp, decim): out_hz * in_den / in_num in lowest terms, the ratio that takes in_num / in_den Hz to out_hz Hz;
+    SdrgError if it is outside the resampler's limits.  (2_000_000, 41, 48_000) -> (123, 125)."""
+    for v in (in_num, in_den, out_hz):
+        if not 0 <= int(v) < 1 << 64:
+            raise SdrgError(f"resample_ratio: {v} is not an unsigned 64-bit integer")
+    L, M = _I32(), _I32()
+    _check(load().sdrg_resample_ratio(int(in_num), int(in_den), int(out_hz), ctypes.byref(L), ctypes.byref(M)),
+           "resample_ratio")
+    return L.value, M.value
 
 
 def ssb_design(samp_count: int, sample_rate: int, sound_mode: int = 1) -> dict:
@@ -1112,6 +1166,70 @@ class Engine:
         _check(load().sdrg_engine_channelizer_host(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out)),
                "channelizer_host")
         return out[:, :, :n_out.value]
+
+    # ---- resampler stage --------------------------------------------------------------------------
+    def set_resample(self, **fields) -> None:
+        """sdrg_engine_set_resample: the fields of sdrg_resample_config (fields left out are 0); set_resample(off=True)
+        switches the stage off."""
+        self._set_stage(ResampleConfig, "resample", fields)
+
+    def resample_config(self) -> dict:
+        """The configuration in force, plus its prototype (taps) and samples_consumed."""
+        c, g = ResampleConfig(), ctypes.c_uint64()
+        h = np.zeros(RESAMPLE_MAX_TAPS, np.float32)
+        _check(load().sdrg_engine_get_resample(self._h, ctypes.byref(c), h.ctypes.data_as(ctypes.c_void_p),
+                                               ctypes.byref(g)), "get_resample")
+        return dict(_as_dict(c), taps=h[:c.interp * c.taps_per_phase].copy(), samples_consumed=g.value)
+
+    def resample_reset(self) -> None:
+        _check(load().sdrg_engine_resample_reset(self._h), "resample_reset")
+
+    def resample_max_out(self) -> int:
+        """ceil(max_in * interp / decim): the row length of a resample call's output."""
+        cap = _I32()
+        _check(load().sdrg_engine_resample_max_out(self._h, ctypes.byref(cap)), "resample_max_out")
+        return cap.value
+
+    def resample_device(self, in_ptr: int, in_stride: int, n: int, out_ptr: int) -> int:
+        """Device path: n_streams rows in_stride values apart in (float32, or complex64 at components = 2; the first n
+        of every row are the call's), out [n_streams][resample_max_out()] float32, int16 or pairs of them out;
+        asynchronous on the main stream.  Returns n_out."""
+        n_out = _I32()
+        _check(load().sdrg_engine_resample_device(self._h, in_ptr, in_stride, n, out_ptr, ctypes.byref(n_out)),
+               "resample_device")
+        return n_out.value
+
+    def _resample_out(self) -> np.ndarray:
+        c = self.resample_config()
+        shape = (self.n_streams, self.resample_max_out()) + ((2,) if c["components"] == 2 else ())
+        return np.empty(shape, RESAMPLE_OUT_DTYPE[c["out_format"]])
+
+    def resample_host(self, rows: np.ndarray) -> np.ndarray:
+        """Host path: rows is float32 [n_streams][n], or complex64 [n_streams][n] at components = 2, n <= max_in.
+        Returns [n_streams][n_out] float32 or int16, with a last axis of 2 (re, im) at components = 2."""
+        comps = self.resample_config()["components"]
+        rows = np.ascontiguousarray(rows, np.complex64 if comps == 2 else np.float32)
+        if rows.size % self.n_streams:
+            raise SdrgError(f"rows has {rows.size} values, no multiple of {self.n_streams} streams")
+        n = rows.size // self.n_streams
+        if n == 0:  # a call without samples still wants a pointer
+            rows = np.zeros((self.n_streams, 1), rows.dtype)
+        out = self._resample_out()
+        n_out = _I32()
+        _check(load().sdrg_engine_resample_host(self._h, _ptr(rows), max(n, 1), n, _ptr(out), ctypes.byref(n_out)),
+               "resample_host")
+        return out[:, :n_out.value]
+
+    def ddc_demod_resample_host(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
+        """Tune and listen at the sound device's rate: iq [n_streams][samplesPerReading * 2] raw samples through the
+        DDC, the demodulator (float32 out) and the resampler (components = 1), the channel and the audio left on the
+        device; returns the resampled audio, int16 or float32 [n_streams][n_out]."""
+        iq = self._iq(iq, fmt)
+        out = self._resample_out()
+        n_out = _I32()
+        _check(load().sdrg_engine_ddc_demod_resample_host(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out)),
+               "ddc_demod_resample_host")
+        return out[:, :n_out.value]
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
                        pcm_ptr: int | None, now_ms: int = 0) -> None:
