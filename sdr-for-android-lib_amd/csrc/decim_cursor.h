@@ -9,11 +9,25 @@
 
 namespace sdrg {
 
-struct DecimCursor {
+// What every stage's position holds, whatever its rate: the arithmetic is the derived cursors'.
+struct StreamCursor {
     uint64_t g = 0;     // samples every stream has consumed since the last restart
     bool fresh = true;  // the next call starts from a history of zeros
     int half = 0;       // the half of the stage's ping-pong buffer the next call reads
 
+    int old_half() const { return half; }
+    int new_half() const { return half ^ 1; }
+    // after a call of n samples; one without samples wrote no history: the state stays where it is
+    void advance(int n) {
+        if (n == 0) return;
+        g += (uint64_t)n;
+        fresh = false;
+        half ^= 1;
+    }
+    void restart() { *this = StreamCursor{}; }
+};
+
+struct DecimCursor : StreamCursor {
     // outputs before global sample x: the multiples of D in [0, x)
     static uint64_t outputs_before(uint64_t x, int D) { return (x + (uint64_t)D - 1) / (uint64_t)D; }
     // global time of the next call's first output
@@ -24,16 +38,6 @@ struct DecimCursor {
     int n_out(int n, int D) const { return (int)(outputs_before(g + (uint64_t)n, D) - outputs_before(g, D)); }
     // the most outputs any call of n samples has: the row length of `out`
     static int cap(int n, int D) { return (n + D - 1) / D; }
-    int old_half() const { return half; }
-    int new_half() const { return half ^ 1; }
-    // after a call of n samples; one without samples wrote no history: the state stays where it is
-    void advance(int n) {
-        if (n == 0) return;
-        g += (uint64_t)n;
-        fresh = false;
-        half ^= 1;
-    }
-    void restart() { *this = DecimCursor{}; }
 };
 
 // The resampler's position (resample.hip): the rate changes by L / M, gcd(L, M) = 1, both in [1, 512].  Output m reads
@@ -41,11 +45,7 @@ struct DecimCursor {
 // m with m M < x L: ceil(x L / M) of them.  With d = (M - (g L) mod M) mod M the next output m0 = ceil(g L / M) has
 // m0 M = g L + d, hence q = g + d / L and phi = d mod L: everything a call needs follows from g mod M, in 64 bits and
 // exactly for every g < 2^63; only m0 itself needs more (g L / M passes 2^64 at L / M = 8).
-struct ResampleCursor {
-    uint64_t g = 0;     // samples every stream has consumed since the last restart
-    bool fresh = true;  // the next call starts from a history of zeros
-    int half = 0;       // the half of the stage's ping-pong buffer the next call reads
-
+struct ResampleCursor : StreamCursor {
     // m0 M - g L of the next call's first output m0, in [0, M)
     int ahead(int L, int M) const {
         const uint64_t r = (g % (uint64_t)M) * (uint64_t)L % (uint64_t)M;
@@ -64,16 +64,6 @@ struct ResampleCursor {
     }
     // the most outputs any call of n samples has (d = 0): the row length of `out`
     static int cap(int n, int L, int M) { return (int)(((int64_t)n * L + M - 1) / M); }
-    int old_half() const { return half; }
-    int new_half() const { return half ^ 1; }
-    // after a call of n samples; one without samples wrote no history: the state stays where it is
-    void advance(int n) {
-        if (n == 0) return;
-        g += (uint64_t)n;
-        fresh = false;
-        half ^= 1;
-    }
-    void restart() { *this = ResampleCursor{}; }
 };
 
 // A device buffer of two halves of half_elems values each: a call reads what the previous one wrote into one half and

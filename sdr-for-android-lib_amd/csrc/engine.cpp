@@ -137,6 +137,72 @@ struct DeviceBuf {
     size_t n = 0;
 };
 
+template <typename... Buf>  // DeviceBufs and PingPongs: freed (hipFree takes a null pointer) and empty again
+void release(Buf *...b) {
+    (((void)hipFree(b->p), *b = Buf{}), ...);
+}
+
+// The streaming stages' records: the configuration and whether one is set, the stream position, what the configuration
+// designs, and the device buffers, all of which free_buffers() releases (sdrg_engine_destroy calls the four).
+
+// DDC stage (sdrg_engine_set_ddc / ddc_device / ddc_host; ddc.hip)
+struct DdcStage {
+    sdrg_ddc_config cfg{};
+    bool set = false;
+    DecimCursor cur;
+    uint32_t fs = 0;        // the sample rate of the previous ddc call (0: none since set_ddc)
+    PingPong<float> hist;   // halves of [n_streams][taps - 1][2]: the mixed samples before the next frame
+    DeviceBuf<float> w;     // [N][2]: the phasors of the frame in flight, shared by the streams
+    uint32_t taps_fs = 0;   // the sample rate taps was designed for (0: not designed)
+    DdcTaps taps{};
+    size_t half(int B) const { return (size_t)B * (size_t)(cfg.taps - 1) * 2; }
+    void restart() {
+        cur.restart();
+        fs = 0;
+    }
+    void free_buffers() { release(&hist, &w); }
+};
+
+// demodulator stage (sdrg_engine_set_demod / demod_device / demod_host / ddc_demod_host; demod.hip)
+struct DemodStage {
+    sdrg_demod_config cfg{};
+    bool set = false;
+    DecimCursor cur;
+    float kf = 0.0f, alpha = 0.0f, a = 0.0f;  // demod_design of cfg
+    DemodTaps taps{};
+    PingPong<float> state;     // halves of {[n_streams][4]: wr, wi, m, s; [n_streams][T2 - 1]: v}
+    DeviceBuf<float> scratch;  // [n_streams][max_in]: e, then v, of the call in flight
+    int cap() const { return DecimCursor::cap(cfg.max_in, cfg.audio_decimation); }
+    size_t half(int B) const { return (size_t)B * 4 + (size_t)B * (size_t)(cfg.audio_taps - 1); }
+    void free_buffers() { release(&state, &scratch); }
+};
+
+// channelizer stage (sdrg_engine_set_channelizer / channelizer_device / channelizer_host; channelizer.hip)
+struct ChanStage {
+    sdrg_channelizer_config cfg{};
+    bool set = false;
+    DecimCursor cur;
+    PingPong<float> hist;     // halves of [n_streams][L - 1][2]: the unpacked samples before the next frame
+    DeviceBuf<float> d_taps;  // [L] taps, then [CHAN_TWIDDLES][2]: written by set_channelizer
+    int decim() const { return cfg.channels / cfg.oversample; }
+    size_t half(int B) const { return (size_t)B * ((size_t)cfg.channels * (size_t)cfg.taps_per_channel - 1) * 2; }
+    void free_buffers() { release(&hist, &d_taps); }
+};
+
+// resampler stage (sdrg_engine_set_resample / resample_device / resample_host / ddc_demod_resample_host;
+// resample.hip)
+struct ResampleStage {
+    sdrg_resample_config cfg{};
+    bool set = false;
+    ResampleCursor cur;
+    std::vector<float> taps;  // resample_design of cfg: the prototype, [L P]
+    PingPong<float> hist;     // halves of [n_streams][P - 1][components]: the values before the next call's
+    DeviceBuf<float> d_taps;  // the prototype in polyphase order [L][P]: written by set_resample
+    int cap() const { return ResampleCursor::cap(cfg.max_in, cfg.interp, cfg.decim); }
+    size_t half(int B) const { return (size_t)B * (size_t)(cfg.taps_per_phase - 1) * (size_t)cfg.components; }
+    void free_buffers() { release(&hist, &d_taps); }
+};
+
 }  // namespace
 
 struct sdrg_engine {
@@ -309,45 +375,20 @@ struct sdrg_engine {
     sdrg_peaks_config peaks{};
     bool peaks_set = false;
     DeviceBuf<unsigned char> peaks_out;  // the host calls' tables: [n_streams][max_peaks] sdrg_peak, then the summaries
-    // DDC stage (sdrg_engine_set_ddc / ddc_device / ddc_host; ddc.hip)
-    sdrg_ddc_config ddc{};
-    bool ddc_set = false;
-    DecimCursor ddc_cur;
-    uint32_t ddc_fs = 0;        // the sample rate of the previous ddc call (0: none since set_ddc)
-    PingPong<float> ddc_hist;   // halves of [n_streams][taps - 1][2]: the mixed samples before the next frame
-    DeviceBuf<float> ddc_w;     // [N][2]: the phasors of the frame in flight, shared by the streams
-    uint32_t ddc_taps_fs = 0;   // the sample rate ddc_taps was designed for (0: not designed)
-    DdcTaps ddc_taps{};
-    DeviceBuf<char> ddc_in;     // ddc_host's copy of the caller's iq
-    DeviceBuf<float> ddc_out;   // ddc_host's rows
-    // demodulator stage (sdrg_engine_set_demod / demod_device / demod_host / ddc_demod_host; demod.hip)
-    sdrg_demod_config demod{};
-    bool demod_set = false;
-    DecimCursor demod_cur;
-    float demod_kf = 0.0f, demod_alpha = 0.0f, demod_a = 0.0f;  // demod_design of `demod`
-    DemodTaps demod_taps{};
-    PingPong<float> demod_state;     // halves of {[n_streams][4]: wr, wi, m, s; [n_streams][T2 - 1]: v}
-    DeviceBuf<float> demod_scratch;  // [n_streams][max_in]: e, then v, of the call in flight
-    DeviceBuf<float> demod_in;       // demod_host's copy of the caller's rows
-    DeviceBuf<char> demod_out;       // demod_host's and ddc_demod_host's audio rows
-    // channelizer stage (sdrg_engine_set_channelizer / channelizer_device / channelizer_host; channelizer.hip)
-    sdrg_channelizer_config chan{};
-    bool chan_set = false;
-    DecimCursor chan_cur;
-    PingPong<float> chan_hist;     // halves of [n_streams][L - 1][2]: the unpacked samples before the next frame
-    float *d_chan_taps = nullptr;  // [L] taps, then [CHAN_TWIDDLES][2]: written by set_channelizer
-    DeviceBuf<char> chan_in;       // channelizer_host's copy of the caller's iq
-    DeviceBuf<float> chan_out;     // channelizer_host's rows
-    // resampler stage (sdrg_engine_set_resample / resample_device / resample_host / ddc_demod_resample_host;
-    // resample.hip)
-    sdrg_resample_config rs{};
-    bool rs_set = false;
-    ResampleCursor rs_cur;
-    std::vector<float> rs_taps;  // resample_design of `rs`: the prototype, [L P]
-    PingPong<float> rs_hist;     // halves of [n_streams][P - 1][components]: the values before the next call's
-    float *d_rs_taps = nullptr;  // the prototype in polyphase order [L][P]: written by set_resample
-    DeviceBuf<float> rs_in;      // resample_host's copy of the caller's rows
-    DeviceBuf<char> rs_out;      // resample_host's and ddc_demod_resample_host's rows
+    // the streaming stages (DdcStage ... ResampleStage above)
+    DdcStage ddc;
+    DemodStage demod;
+    ChanStage chan;
+    ResampleStage rs;
+    // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host and the two
+    // chains), as bytes: the caller's input, and the rows it gets back.  One pair serves them all, as spec_in does its
+    // four: each of them waits on s_main before it returns, so no two uses overlap, and a call that fails after its
+    // copy was enqueued leaves that copy ordered on s_main before whatever the next call enqueues there.
+    DeviceBuf<char> stream_in, stream_out;
+    // what a chain call leaves on the device, for the same reason one of each: the channel between the DDC and the
+    // demodulator, [n_streams][the DDC's cap][2], and the float audio between the demodulator and the resampler,
+    // [n_streams][the demodulator's cap]
+    DeviceBuf<float> chain_chan, chain_audio;
 };
 
 namespace {
@@ -431,20 +472,85 @@ int32_t ensure_device(PingPong<T> *b, size_t half_elems) {
     return ensure_device(&b->p, &b->n, std::max<size_t>(2 * half_elems, 2));
 }
 
-// One host call of a stage on the main stream: the caller's `in` to the staging buffer, enqueue(staged input, device
-// rows), the rows to the caller's `out`, and the wait.  Every refusal has come before: this allocates and copies.
-template <typename TI, typename TO, typename Enqueue>
-int32_t host_round_trip(sdrg_engine *e, DeviceBuf<TI> *d_in, const void *in, size_t in_elems, DeviceBuf<TO> *d_out,
-                        void *out, size_t out_elems, Enqueue enqueue) {
-    int32_t rc = ensure_device(d_in, in_elems);
+// The two ends of a streaming stage's or a chain's host call on the main stream: the caller's `in` into stream_in, with
+// stream_out made ready for the rows; and those rows to the caller's `out`, and the wait.  Between the two the launches
+// read stream_in.p and write stream_out.p.
+int32_t host_begin(sdrg_engine *e, const void *in, size_t in_bytes, size_t out_bytes) {
+    int32_t rc = ensure_device(&e->stream_in, in_bytes);
     if (rc) return rc;
-    rc = ensure_device(d_out, out_elems);
+    rc = ensure_device(&e->stream_out, out_bytes);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(d_in->p, in, sizeof(TI) * in_elems, hipMemcpyHostToDevice, e->s_main));
-    rc = enqueue(d_in->p, d_out->p);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out->p, sizeof(TO) * out_elems, hipMemcpyDeviceToHost, e->s_main));
+    HIP_TRY(hipMemcpyAsync(e->stream_in.p, in, in_bytes, hipMemcpyHostToDevice, e->s_main));
+    return SDRG_OK;
+}
+
+int32_t host_end(sdrg_engine *e, void *out, size_t out_bytes) {
+    HIP_TRY(hipMemcpyAsync(out, e->stream_out.p, out_bytes, hipMemcpyDeviceToHost, e->s_main));
     HIP_TRY(hipStreamSynchronize(e->s_main));
+    return SDRG_OK;
+}
+
+// These host floats become the device buffer *d (`what` taps: a stage's name, for the message).  They go into a buffer
+// of their own, so a failed copy leaves the old one in force; the old one is freed afterwards, which waits for the
+// calls that still read it.
+int32_t upload_floats(DeviceBuf<float> *d, const std::vector<float> &host, const char *what) {
+    DeviceBuf<float> fresh;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&fresh.p), sizeof(float) * host.size()));
+    const hipError_t er = hipMemcpy(fresh.p, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
+    if (er != hipSuccess) {
+        (void)hipFree(fresh.p);
+        return fail(SDRG_E_HIP, "%s taps upload: %s", what, hipGetErrorString(er));
+    }
+    fresh.n = host.size();
+    release(d);
+    *d = fresh;
+    return SDRG_OK;
+}
+
+// nco_tables() on the device, uploaded once: the SSB variant's mixer and the DDC's read the same table
+int32_t ensure_nco_table(sdrg_engine *e) {
+    if (e->d_nco_tab) return SDRG_OK;
+    std::vector<float> tab(4096);
+    nco_tables(tab.data());
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_nco_tab), sizeof(float) * tab.size()));
+    HIP_TRY(hipMemcpy(e->d_nco_tab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    return SDRG_OK;
+}
+
+// ---- the streaming stages: DDC, demodulator, channelizer, resampler -------------------------------------------------
+//
+// A call of a stage goes through three steps.  x_resolve makes every refusal and touches nothing; what it finds goes
+// into the stage's XCall.  x_reserve does everything that can fail without a launch (the stage's device buffers, the
+// NCO table, the DDC's taps) and commits no cursor.  x_launch fills the kernel's parameters, launches, and only then
+// advances the cursor.  stage_call runs the three for one stage, chain_host for several.
+
+// what every resolved call has; a stage's XCall adds what its own launch needs
+struct StageCall {
+    int n = 0, n_out = 0, cap = 0;       // samples per stream in, outputs per row, the row length of `out`
+    size_t in_bytes = 0, out_bytes = 0;  // a host call's input and output
+};
+
+int32_t require_set(bool set, const char *stage) {
+    return set ? SDRG_OK : fail(SDRG_E_INVALID, "no %s configuration set (sdrg_engine_set_%s)", stage, stage);
+}
+
+// sdrg_engine_<stage>_device (in, out in device memory) and sdrg_engine_<stage>_host (in host memory) of the stage
+// with these three steps; `args` are what its resolve takes between the engine and the call
+template <typename Call, auto resolve, auto reserve, auto launch, typename... A>
+int32_t stage_call(sdrg_engine *e, const char *in_name, const void *in, void *out, int32_t *n_out, bool host, A... args) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!in || !out || !n_out) return fail(SDRG_E_INVALID, "null %s, out or n_out", in_name);
+    Call c;
+    int32_t rc = resolve(e, args..., &c);
+    if (rc) return rc;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    rc = reserve(e, c);
+    if (!rc && host) rc = host_begin(e, in, c.in_bytes, c.out_bytes);
+    if (!rc) rc = host ? launch(e, c, e->stream_in.p, e->stream_out.p) : launch(e, c, in, out);
+    if (!rc && host) rc = host_end(e, out, c.out_bytes);
+    if (rc) return rc;
+    *n_out = c.n_out;
     return SDRG_OK;
 }
 
@@ -475,7 +581,7 @@ int32_t resolve_integrated(const sdrg_engine *e, int n, const float **d_rows) {
 
 struct CopyOut { void *to; const void *from; size_t bytes; };  // device -> host; to == nullptr: the caller wants none
 
-// host_round_trip for the stages that read spectra, [n_streams][N] = count floats, on the main stream: the caller's
+// The host call of the stages that read spectra, [n_streams][N] = count floats, on the main stream: the caller's
 // `spectra` to spec_in unless the source is d_rows (resolve_spectra, resolve_integrated), enqueue(source), the copies
 // out, and the wait.  Every refusal has come before, and the caller has allocated what `outs` reads from.
 template <typename Enqueue>
@@ -650,12 +756,8 @@ int32_t prepare_ssb(sdrg_engine *e, SsbControl &c, uint32_t &nco_phase, SsbParam
     memcpy(p->hp, c.hp, sizeof(p->hp));
     memcpy(p->bp, c.bp, sizeof(p->bp));
     if (e->nco_hz != 0.0) {
-        if (!e->d_nco_tab) {
-            std::vector<float> tab(4096);
-            nco_tables(tab.data());
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_nco_tab), sizeof(float) * tab.size()));
-            HIP_TRY(hipMemcpy(e->d_nco_tab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-        }
+        const int32_t rc = ensure_nco_table(e);
+        if (rc) return rc;
         p->nco_on = 1;
         p->nco_inc = nco_increment(e->nco_hz, fs);
         p->nco_phase = nco_phase;
@@ -1194,11 +1296,14 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     void *bufs[] = {e->d_stats, e->d_ssb, e->d_twiddles, e->d_taps, e->d_nco_tab, e->d_chunk_table, e->d_ssb_scratch,
                     e->d_spec_scratch, e->d_fft_scratch, e->d_pool, e->d_rec_scratch, e->d_iq_stage, e->d_spec_stage,
                     e->spec_in.p, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->disp_out.p, e->integ_ring.p,
-                    e->integ_ema.p, e->integ_out.p, e->peaks_out.p, e->ddc_hist.p, e->ddc_w.p, e->ddc_in.p, e->ddc_out.p,
-                    e->demod_state.p, e->demod_scratch.p, e->demod_in.p, e->demod_out.p, e->chan_hist.p, e->d_chan_taps,
-                    e->chan_in.p, e->chan_out.p, e->rs_hist.p, e->d_rs_taps, e->rs_in.p, e->rs_out.p};
+                    e->integ_ema.p, e->integ_out.p, e->peaks_out.p, e->stream_in.p, e->stream_out.p,
+                    e->chain_chan.p, e->chain_audio.p};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
+    e->ddc.free_buffers();
+    e->demod.free_buffers();
+    e->chan.free_buffers();
+    e->rs.free_buffers();
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
     for (hipEvent_t ev : e->ev_stats_end)
         if (ev) (void)hipEventDestroy(ev);
@@ -1996,136 +2101,117 @@ int32_t sdrg_ddc_tile_outputs(int32_t decimation, int32_t taps, int32_t *tile) {
     return SDRG_OK;
 }
 
-static void ddc_restart(sdrg_engine *e) {
-    e->ddc_cur.restart();
-    e->ddc_fs = 0;
-}
-
 int32_t sdrg_engine_set_ddc(sdrg_engine *e, const sdrg_ddc_config *cfg) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (cfg) {
         if (const char *bad = ddc_check((uint32_t)e->cfg.sample_rate, cfg->offset_hz, cfg->cutoff_hz, cfg->decimation,
                                         cfg->taps))
             return fail(SDRG_E_INVALID, "ddc: %s", bad);
-        e->ddc = *cfg;
+        e->ddc.cfg = *cfg;
     }
-    e->ddc_set = cfg != nullptr;
-    e->ddc_taps_fs = 0;
-    ddc_restart(e);
+    e->ddc.set = cfg != nullptr;
+    e->ddc.taps_fs = 0;
+    e->ddc.restart();
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_get_ddc(const sdrg_engine *e, sdrg_ddc_config *cfg, uint32_t *nco_increment_out,
                             uint64_t *samples_consumed) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!e->ddc_set) return fail(SDRG_E_INVALID, "no ddc configuration set");
-    if (cfg) *cfg = e->ddc;
-    if (nco_increment_out) *nco_increment_out = nco_increment(e->ddc.offset_hz, (uint32_t)e->cfg.sample_rate);
-    if (samples_consumed) *samples_consumed = e->ddc_cur.g;
+    if (!e->ddc.set) return fail(SDRG_E_INVALID, "no ddc configuration set");
+    if (cfg) *cfg = e->ddc.cfg;
+    if (nco_increment_out) *nco_increment_out = nco_increment(e->ddc.cfg.offset_hz, (uint32_t)e->cfg.sample_rate);
+    if (samples_consumed) *samples_consumed = e->ddc.cur.g;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_ddc_reset(sdrg_engine *e) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    ddc_restart(e);
+    e->ddc.restart();
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_ddc_max_out(const sdrg_engine *e, int32_t *cap) {
     if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
-    if (!e->ddc_set) return fail(SDRG_E_INVALID, "no ddc configuration set (sdrg_engine_set_ddc)");
-    *cap = DecimCursor::cap(e->cfg.samples_per_reading, e->ddc.decimation);
+    if (int32_t rc = require_set(e->ddc.set, "ddc")) return rc;
+    *cap = DecimCursor::cap(e->cfg.samples_per_reading, e->ddc.cfg.decimation);
     return SDRG_OK;
 }
 
-// what one ddc call needs beside its buffers, resolved before anything is touched
-struct DdcCall {
+struct DdcCall : StageCall {
+    int32_t fmt;
     uint32_t fs;
     DecimCursor cur;  // where the call starts: the engine's, restarted if the sample rate changed since the previous call
-    int n, cap, n_out;
 };
 
 static int32_t ddc_resolve(const sdrg_engine *e, int32_t fmt, DdcCall *c) {
-    if (!e->ddc_set) return fail(SDRG_E_INVALID, "no ddc configuration set (sdrg_engine_set_ddc)");
+    const DdcStage &s = e->ddc;
+    if (int32_t rc = require_set(s.set, "ddc")) return rc;
     if (bytes_per_sample(fmt) == 0) return fail(SDRG_E_INVALID, "unknown iq format %d", fmt);
+    c->fmt = fmt;
     c->fs = (uint32_t)e->cfg.sample_rate;
-    if (e->ddc.cutoff_hz > (double)c->fs / 2.0)
-        return fail(SDRG_E_INVALID, "ddc cutoff %g Hz above half the sample rate %u", e->ddc.cutoff_hz, c->fs);
-    c->cur = e->ddc_cur;
-    if (e->ddc_fs != 0 && e->ddc_fs != c->fs) c->cur.restart();
+    if (s.cfg.cutoff_hz > (double)c->fs / 2.0)
+        return fail(SDRG_E_INVALID, "ddc cutoff %g Hz above half the sample rate %u", s.cfg.cutoff_hz, c->fs);
+    c->cur = s.cur;
+    if (s.fs != 0 && s.fs != c->fs) c->cur.restart();
     c->n = e->cfg.samples_per_reading;
-    c->cap = DecimCursor::cap(c->n, e->ddc.decimation);
-    c->n_out = c->cur.n_out(c->n, e->ddc.decimation);
+    c->cap = DecimCursor::cap(c->n, s.cfg.decimation);
+    c->n_out = c->cur.n_out(c->n, s.cfg.decimation);
+    c->in_bytes = (size_t)e->n_streams * (size_t)c->n * (size_t)bytes_per_sample(fmt);
+    c->out_bytes = (size_t)e->n_streams * (size_t)c->cap * 2 * sizeof(float);
+    return SDRG_OK;
+}
+
+static int32_t ddc_reserve(sdrg_engine *e, const DdcCall &c) {
+    DdcStage &s = e->ddc;
+    int32_t rc = ensure_device(&s.hist, s.half(e->n_streams));
+    if (rc) return rc;
+    // a longer frame than any before: hipFree waits for the calls that read the old row
+    rc = ensure_device(&s.w, 2 * (size_t)c.n);
+    if (rc) return rc;
+    rc = ensure_nco_table(e);
+    if (rc) return rc;
+    if (s.taps_fs != c.fs) {  // the taps travel in the kernel arguments: nothing on the device to replace
+        ddc_design(c.fs, s.cfg.cutoff_hz, s.cfg.taps, s.taps.h);
+        s.taps_fs = c.fs;
+    }
     return SDRG_OK;
 }
 
 // one ddc call on the main stream: iq, out in device memory
-static int32_t ddc_enqueue(sdrg_engine *e, const DdcCall &c, const void *iq, int32_t fmt, float *out) {
-    const sdrg_ddc_config &cfg = e->ddc;
-    const int T = cfg.taps, D = cfg.decimation;
-    const size_t half = (size_t)e->n_streams * (size_t)(T - 1) * 2;
-    int32_t rc = ensure_device(&e->ddc_hist, half);
-    if (rc) return rc;
-    // a longer frame than any before: hipFree waits for the calls that read the old row
-    rc = ensure_device(&e->ddc_w, 2 * (size_t)c.n);
-    if (rc) return rc;
-    if (!e->d_nco_tab) {
-        std::vector<float> tab(4096);
-        nco_tables(tab.data());
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_nco_tab), sizeof(float) * tab.size()));
-        HIP_TRY(hipMemcpy(e->d_nco_tab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    }
-    if (e->ddc_taps_fs != c.fs) {  // the taps travel in the kernel arguments: nothing on the device to replace
-        ddc_design(c.fs, cfg.cutoff_hz, T, e->ddc_taps.h);
-        e->ddc_taps_fs = c.fs;
-    }
+static int32_t ddc_launch(sdrg_engine *e, const DdcCall &c, const void *iq, void *out) {
+    DdcStage &s = e->ddc;
+    const int D = s.cfg.decimation;
+    const size_t half = s.half(e->n_streams);
     DdcParams p{};
     p.n = c.n;
     p.decim = D;
-    p.taps = T;
+    p.taps = s.cfg.taps;
     p.first = c.cur.first(D);
     p.n_out = c.n_out;
     p.cap = c.cap;
-    p.inc = nco_increment(cfg.offset_hz, c.fs);
+    p.inc = nco_increment(s.cfg.offset_hz, c.fs);
     p.g0_lo = (uint32_t)c.cur.g;
     p.nco_tab = e->d_nco_tab;
-    p.hist_old = e->ddc_hist.old(c.cur, half);
-    p.hist_new = e->ddc_hist.next(c.cur, half);
-    p.phasors = e->ddc_w.p;
-    HIP_TRY(launch_ddc(iq, fmt, e->n_streams, p, e->ddc_taps, out, e->s_main));
-    e->ddc_cur = c.cur;
-    e->ddc_cur.advance(c.n);
-    e->ddc_fs = c.fs;
+    p.hist_old = s.hist.old(c.cur, half);
+    p.hist_new = s.hist.next(c.cur, half);
+    p.phasors = s.w.p;
+    HIP_TRY(launch_ddc(iq, c.fmt, e->n_streams, p, s.taps, static_cast<float *>(out), e->s_main));
+    s.cur = c.cur;
+    s.cur.advance(c.n);
+    s.fs = c.fs;
     e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
-// sdrg_engine_ddc_device (iq, out in device memory) and sdrg_engine_ddc_host (in host memory)
-static int32_t ddc_call(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out, bool host) {
-    if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
-    DdcCall c;
-    int32_t rc = ddc_resolve(e, fmt, &c);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t B = (size_t)e->n_streams;
-    if (host)
-        rc = host_round_trip(e, &e->ddc_in, iq, B * (size_t)c.n * bytes_per_sample(fmt), &e->ddc_out, out, B * (size_t)c.cap * 2,
-                             [&](const char *d_iq, float *d_out) { return ddc_enqueue(e, c, d_iq, fmt, d_out); });
-    else
-        rc = ddc_enqueue(e, c, iq, fmt, static_cast<float *>(out));
-    if (rc) return rc;
-    *n_out = c.n_out;
-    return SDRG_OK;
-}
+static constexpr auto ddc_stage = &stage_call<DdcCall, ddc_resolve, ddc_reserve, ddc_launch, int32_t>;
 
 int32_t sdrg_engine_ddc_device(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    return ddc_call(e, iq, fmt, out, n_out, false);
+    return ddc_stage(e, "iq", iq, out, n_out, false, fmt);
 }
 
 int32_t sdrg_engine_ddc_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    return ddc_call(e, iq, fmt, out, n_out, true);
+    return ddc_stage(e, "iq", iq, out, n_out, true, fmt);
 }
 
 // ---- demodulator stage (demod.hip) --------------------------------------------------------------------------------
@@ -2149,150 +2235,108 @@ int32_t sdrg_demod_geometry(int32_t audio_decimation, int32_t audio_taps, int32_
 
 int32_t sdrg_engine_set_demod(sdrg_engine *e, const sdrg_demod_config *cfg) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
+    DemodStage &s = e->demod;
     if (cfg) {
         if (const char *bad = demod_check(*cfg)) return fail(SDRG_E_INVALID, "demod: %s", bad);
-        e->demod = *cfg;
-        demod_design(*cfg, &e->demod_kf, &e->demod_alpha, &e->demod_a, e->demod_taps.h);
+        s.cfg = *cfg;
+        demod_design(*cfg, &s.kf, &s.alpha, &s.a, s.taps.h);
     }
-    e->demod_set = cfg != nullptr;
-    e->demod_cur.restart();
+    s.set = cfg != nullptr;
+    s.cur.restart();
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_get_demod(const sdrg_engine *e, sdrg_demod_config *cfg, float *kf, float *alpha, float *a,
                               float *taps, uint64_t *samples_consumed) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set");
-    if (cfg) *cfg = e->demod;
-    if (kf) *kf = e->demod_kf;
-    if (alpha) *alpha = e->demod_alpha;
-    if (a) *a = e->demod_a;
-    if (taps) std::copy(e->demod_taps.h, e->demod_taps.h + e->demod.audio_taps, taps);
-    if (samples_consumed) *samples_consumed = e->demod_cur.g;
+    const DemodStage &s = e->demod;
+    if (!s.set) return fail(SDRG_E_INVALID, "no demod configuration set");
+    if (cfg) *cfg = s.cfg;
+    if (kf) *kf = s.kf;
+    if (alpha) *alpha = s.alpha;
+    if (a) *a = s.a;
+    if (taps) std::copy(s.taps.h, s.taps.h + s.cfg.audio_taps, taps);
+    if (samples_consumed) *samples_consumed = s.cur.g;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_demod_reset(sdrg_engine *e) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    e->demod_cur.restart();
+    e->demod.cur.restart();
     return SDRG_OK;
 }
-
-static int demod_cap(const sdrg_engine *e) { return DecimCursor::cap(e->demod.max_in, e->demod.audio_decimation); }
 
 int32_t sdrg_engine_demod_max_out(const sdrg_engine *e, int32_t *cap) {
     if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
-    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set (sdrg_engine_set_demod)");
-    *cap = demod_cap(e);
+    if (int32_t rc = require_set(e->demod.set, "demod")) return rc;
+    *cap = e->demod.cap();
     return SDRG_OK;
 }
 
-// the checks of one demod call, and its n_out, before anything is touched
-static int32_t demod_resolve(const sdrg_engine *e, int32_t n, int32_t *n_out) {
-    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set (sdrg_engine_set_demod)");
-    if (n < 0 || n > e->demod.max_in) return fail(SDRG_E_INVALID, "demod: n %d outside [0, max_in = %d]", n, e->demod.max_in);
-    *n_out = e->demod_cur.n_out(n, e->demod.audio_decimation);
+struct DemodCall : StageCall {
+    int in_stride;  // complex samples between the rows of chan: max_in, or in a chain the DDC's cap
+};
+
+static int32_t demod_resolve(const sdrg_engine *e, int32_t n, DemodCall *c) {
+    const DemodStage &s = e->demod;
+    if (int32_t rc = require_set(s.set, "demod")) return rc;
+    if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "demod: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
+    c->n = n;
+    c->in_stride = s.cfg.max_in;
+    c->cap = s.cap();
+    c->n_out = s.cur.n_out(n, s.cfg.audio_decimation);
+    c->in_bytes = (size_t)e->n_streams * (size_t)c->in_stride * 2 * sizeof(float);
+    c->out_bytes = (size_t)e->n_streams * (size_t)c->cap *
+                   (s.cfg.out_format == SDRG_DEMOD_OUT_F32 ? sizeof(float) : sizeof(int16_t));
     return SDRG_OK;
 }
 
-static size_t demod_out_size(const sdrg_engine *e) {
-    return (size_t)e->n_streams * (size_t)demod_cap(e) *
-           (e->demod.out_format == SDRG_DEMOD_OUT_F32 ? sizeof(float) : sizeof(int16_t));
+static int32_t demod_reserve(sdrg_engine *e, const DemodCall &) {
+    const int32_t rc = ensure_device(&e->demod.state, e->demod.half(e->n_streams));
+    return rc ? rc : ensure_device(&e->demod.scratch, (size_t)e->n_streams * (size_t)e->demod.cfg.max_in);
 }
 
 // one demod call on the main stream: chan (rows of in_stride complex samples), out in device memory
-static int32_t demod_enqueue(sdrg_engine *e, const float *chan, int in_stride, int n, int n_out, void *out) {
-    const sdrg_demod_config &cfg = e->demod;
-    const int T = cfg.audio_taps, R = cfg.audio_decimation;
-    const size_t B = (size_t)e->n_streams, half = B * 4 + B * (size_t)(T - 1);
-    int32_t rc = ensure_device(&e->demod_state, half);
-    if (rc) return rc;
-    rc = ensure_device(&e->demod_scratch, B * (size_t)cfg.max_in);
-    if (rc) return rc;
-    const DecimCursor &cur = e->demod_cur;
-    float *old_half = e->demod_state.half(cur.old_half(), half);  // not read by a fresh call: p.fresh says so
-    float *new_half = e->demod_state.next(cur, half);
+static int32_t demod_launch(sdrg_engine *e, const DemodCall &c, const void *chan, void *out) {
+    DemodStage &s = e->demod;
+    const size_t B = (size_t)e->n_streams, half = s.half(e->n_streams);
+    float *old_half = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    float *new_half = s.state.next(s.cur, half);
     DemodParams p{};
-    p.n = n;
-    p.in_stride = in_stride;
-    p.scratch_stride = cfg.max_in;
-    p.decim = R;
-    p.taps = T;
-    p.first = cur.first(R);
-    p.n_out = n_out;
-    p.cap = demod_cap(e);
-    p.mode = cfg.mode;
-    p.out_format = cfg.out_format;
-    p.fresh = cur.fresh ? 1 : 0;
-    p.kf = e->demod_kf;
-    p.alpha = e->demod_alpha;
-    p.a = e->demod_a;
-    p.gain = cfg.gain;
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.scratch_stride = s.cfg.max_in;
+    p.decim = s.cfg.audio_decimation;
+    p.taps = s.cfg.audio_taps;
+    p.first = s.cur.first(s.cfg.audio_decimation);
+    p.n_out = c.n_out;
+    p.cap = c.cap;
+    p.mode = s.cfg.mode;
+    p.out_format = s.cfg.out_format;
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.kf = s.kf;
+    p.alpha = s.alpha;
+    p.a = s.a;
+    p.gain = s.cfg.gain;
     p.state_old = old_half;
     p.hist_old = old_half + B * 4;
     p.state_new = new_half;
     p.hist_new = new_half + B * 4;
-    p.scratch = e->demod_scratch.p;
-    HIP_TRY(launch_demod(chan, e->n_streams, p, e->demod_taps, out, e->s_main));
-    e->demod_cur.advance(n);  // a call without samples wrote out only: the state stays where it is
+    p.scratch = s.scratch.p;
+    HIP_TRY(launch_demod(static_cast<const float *>(chan), e->n_streams, p, s.taps, out, e->s_main));
+    s.cur.advance(c.n);  // a call without samples wrote out only: the state stays where it is
     e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
-// sdrg_engine_demod_device (chan, out in device memory) and sdrg_engine_demod_host (in host memory)
-static int32_t demod_call(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out, bool host) {
-    if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!chan || !out || !n_out) return fail(SDRG_E_INVALID, "null chan, out or n_out");
-    int32_t count;
-    int32_t rc = demod_resolve(e, n, &count);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const int stride = e->demod.max_in;
-    if (host)
-        rc = host_round_trip(
-            e, &e->demod_in, chan, (size_t)e->n_streams * (size_t)stride * 2, &e->demod_out, out, demod_out_size(e),
-            [&](const float *d_chan, char *d_out) { return demod_enqueue(e, d_chan, stride, n, count, d_out); });
-    else
-        rc = demod_enqueue(e, static_cast<const float *>(chan), stride, n, count, out);
-    if (rc) return rc;
-    *n_out = count;
-    return SDRG_OK;
-}
+static constexpr auto demod_stage = &stage_call<DemodCall, demod_resolve, demod_reserve, demod_launch, int32_t>;
 
 int32_t sdrg_engine_demod_device(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
-    return demod_call(e, chan, n, out, n_out, false);
+    return demod_stage(e, "chan", chan, out, n_out, false, n);
 }
 
 int32_t sdrg_engine_demod_host(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
-    return demod_call(e, chan, n, out, n_out, true);
-}
-
-int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
-    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set (sdrg_engine_set_demod)");
-    DdcCall c;
-    int32_t rc = ddc_resolve(e, fmt, &c);
-    if (rc) return rc;
-    if (e->demod.max_in < c.cap)
-        return fail(SDRG_E_INVALID, "demod max_in %d smaller than the ddc's row length %d", e->demod.max_in, c.cap);
-    int32_t count;
-    rc = demod_resolve(e, c.n_out, &count);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t B = (size_t)e->n_streams;
-    rc = ensure_device(&e->ddc_out, B * (size_t)c.cap * 2);  // the channel between the two stages
-    if (rc) return rc;
-    rc = host_round_trip(e, &e->ddc_in, iq, B * (size_t)c.n * bytes_per_sample(fmt), &e->demod_out, out, demod_out_size(e),
-                         [&](const char *d_iq, char *d_out) {
-                             int32_t r = ddc_enqueue(e, c, d_iq, fmt, e->ddc_out.p);
-                             return r ? r : demod_enqueue(e, e->ddc_out.p, c.cap, c.n_out, count, d_out);
-                         });
-    if (rc) return rc;
-    *n_out = count;
-    return SDRG_OK;
+    return demod_stage(e, "chan", chan, out, n_out, true, n);
 }
 
 // ---- channelizer stage (channelizer.hip) ---------------------------------------------------------------------------
@@ -2315,8 +2359,7 @@ int32_t sdrg_engine_set_channelizer(sdrg_engine *e, const sdrg_channelizer_confi
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (cfg) {
         if (const char *bad = chan_check(*cfg)) return fail(SDRG_E_INVALID, "channelizer: %s", bad);
-        // the taps and the DFT's twiddles go into a buffer of their own; the old one is freed afterwards, which waits
-        // for the calls that still read it
+        // the taps, then the DFT's twiddles
         const size_t L = (size_t)cfg->channels * (size_t)cfg->taps_per_channel;
         std::vector<float> host(L + 2 * (size_t)CHAN_TWIDDLES);
         chan_design(*cfg, host.data());
@@ -2327,114 +2370,88 @@ int32_t sdrg_engine_set_channelizer(sdrg_engine *e, const sdrg_channelizer_confi
         }
         DeviceScope dscope(e->device);
         HIP_TRY(dscope.error());
-        float *fresh = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&fresh), sizeof(float) * host.size()));
-        hipError_t er = hipMemcpy(fresh, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
-        if (er != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(SDRG_E_HIP, "channelizer taps upload: %s", hipGetErrorString(er));
-        }
-        if (e->d_chan_taps) (void)hipFree(e->d_chan_taps);
-        e->d_chan_taps = fresh;
-        e->chan = *cfg;
+        const int32_t rc = upload_floats(&e->chan.d_taps, host, "channelizer");
+        if (rc) return rc;
+        e->chan.cfg = *cfg;
     }
-    e->chan_set = cfg != nullptr;
-    e->chan_cur.restart();
+    e->chan.set = cfg != nullptr;
+    e->chan.cur.restart();
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_get_channelizer(const sdrg_engine *e, sdrg_channelizer_config *cfg, uint64_t *samples_consumed) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!e->chan_set) return fail(SDRG_E_INVALID, "no channelizer configuration set");
-    if (cfg) *cfg = e->chan;
-    if (samples_consumed) *samples_consumed = e->chan_cur.g;
+    if (!e->chan.set) return fail(SDRG_E_INVALID, "no channelizer configuration set");
+    if (cfg) *cfg = e->chan.cfg;
+    if (samples_consumed) *samples_consumed = e->chan.cur.g;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_channelizer_reset(sdrg_engine *e) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    e->chan_cur.restart();
+    e->chan.cur.restart();
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_channelizer_max_out(const sdrg_engine *e, int32_t *cap) {
     if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
-    if (!e->chan_set) return fail(SDRG_E_INVALID, "no channelizer configuration set (sdrg_engine_set_channelizer)");
-    *cap = DecimCursor::cap(e->cfg.samples_per_reading, e->chan.channels / e->chan.oversample);
+    if (int32_t rc = require_set(e->chan.set, "channelizer")) return rc;
+    *cap = DecimCursor::cap(e->cfg.samples_per_reading, e->chan.decim());
     return SDRG_OK;
 }
 
-// what one channelizer call needs beside its buffers, resolved before anything is touched
-struct ChanCall {
-    int n, decim, cap, n_out;
+struct ChanCall : StageCall {
+    int32_t fmt;
 };
 
 static int32_t chan_resolve(const sdrg_engine *e, int32_t fmt, ChanCall *c) {
-    if (!e->chan_set) return fail(SDRG_E_INVALID, "no channelizer configuration set (sdrg_engine_set_channelizer)");
+    const ChanStage &s = e->chan;
+    if (int32_t rc = require_set(s.set, "channelizer")) return rc;
     if (bytes_per_sample(fmt) == 0) return fail(SDRG_E_INVALID, "unknown iq format %d", fmt);
+    c->fmt = fmt;
     c->n = e->cfg.samples_per_reading;
-    c->decim = e->chan.channels / e->chan.oversample;
-    c->cap = DecimCursor::cap(c->n, c->decim);
-    c->n_out = e->chan_cur.n_out(c->n, c->decim);
+    c->cap = DecimCursor::cap(c->n, s.decim());
+    c->n_out = s.cur.n_out(c->n, s.decim());
+    c->in_bytes = (size_t)e->n_streams * (size_t)c->n * (size_t)bytes_per_sample(fmt);
+    c->out_bytes = (size_t)e->n_streams * (size_t)s.cfg.n_channels * (size_t)c->cap * 2 * sizeof(float);
     return SDRG_OK;
 }
 
+static int32_t chan_reserve(sdrg_engine *e, const ChanCall &) { return ensure_device(&e->chan.hist, e->chan.half(e->n_streams)); }
+
 // one channelizer call on the main stream: iq, out in device memory
-static int32_t chan_enqueue(sdrg_engine *e, const ChanCall &c, const void *iq, int32_t fmt, float *out) {
-    const sdrg_channelizer_config &cfg = e->chan;
-    const size_t L = (size_t)cfg.channels * (size_t)cfg.taps_per_channel;
-    const size_t half = (size_t)e->n_streams * (L - 1) * 2;
-    int32_t rc = ensure_device(&e->chan_hist, half);
-    if (rc) return rc;
-    const DecimCursor &cur = e->chan_cur;
+static int32_t chan_launch(sdrg_engine *e, const ChanCall &c, const void *iq, void *out) {
+    ChanStage &s = e->chan;
+    const size_t half = s.half(e->n_streams);
     ChanParams p{};
     p.n = c.n;
-    p.channels = cfg.channels;
-    p.taps_per_channel = cfg.taps_per_channel;
-    p.oversample = cfg.oversample;
-    p.decim = c.decim;
-    p.first = cur.first(c.decim);
+    p.channels = s.cfg.channels;
+    p.taps_per_channel = s.cfg.taps_per_channel;
+    p.oversample = s.cfg.oversample;
+    p.decim = s.decim();
+    p.first = s.cur.first(p.decim);
     p.n_out = c.n_out;
     p.cap = c.cap;
-    p.first_channel = cfg.first_channel;
-    p.n_channels = cfg.n_channels;
-    p.m_parity = (int)(cur.first_output(c.decim) & 1);
-    p.taps = e->d_chan_taps;
-    p.hist_old = e->chan_hist.old(cur, half);
-    p.hist_new = e->chan_hist.next(cur, half);
-    HIP_TRY(launch_channelizer(iq, fmt, e->n_streams, p, out, e->s_main));
-    e->chan_cur.advance(c.n);
+    p.first_channel = s.cfg.first_channel;
+    p.n_channels = s.cfg.n_channels;
+    p.m_parity = (int)(s.cur.first_output(p.decim) & 1);
+    p.taps = s.d_taps.p;
+    p.hist_old = s.hist.old(s.cur, half);
+    p.hist_new = s.hist.next(s.cur, half);
+    HIP_TRY(launch_channelizer(iq, c.fmt, e->n_streams, p, static_cast<float *>(out), e->s_main));
+    s.cur.advance(c.n);
     e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
-// sdrg_engine_channelizer_device (iq, out in device memory) and sdrg_engine_channelizer_host (in host memory)
-static int32_t chan_call(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out, bool host) {
-    if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
-    ChanCall c;
-    int32_t rc = chan_resolve(e, fmt, &c);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t B = (size_t)e->n_streams;
-    if (host)
-        rc = host_round_trip(e, &e->chan_in, iq, B * (size_t)c.n * bytes_per_sample(fmt), &e->chan_out, out,
-                             B * (size_t)e->chan.n_channels * (size_t)c.cap * 2,
-                             [&](const char *d_iq, float *d_out) { return chan_enqueue(e, c, d_iq, fmt, d_out); });
-    else
-        rc = chan_enqueue(e, c, iq, fmt, static_cast<float *>(out));
-    if (rc) return rc;
-    *n_out = c.n_out;
-    return SDRG_OK;
-}
+static constexpr auto chan_stage = &stage_call<ChanCall, chan_resolve, chan_reserve, chan_launch, int32_t>;
 
 int32_t sdrg_engine_channelizer_device(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    return chan_call(e, iq, fmt, out, n_out, false);
+    return chan_stage(e, "iq", iq, out, n_out, false, fmt);
 }
 
 int32_t sdrg_engine_channelizer_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    return chan_call(e, iq, fmt, out, n_out, true);
+    return chan_stage(e, "iq", iq, out, n_out, true, fmt);
 }
 
 // ---- resampler stage (resample.hip) --------------------------------------------------------------------------------
@@ -2469,8 +2486,7 @@ int32_t sdrg_engine_set_resample(sdrg_engine *e, const sdrg_resample_config *cfg
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (cfg) {
         if (const char *bad = resample_check(*cfg)) return fail(SDRG_E_INVALID, "resample: %s", bad);
-        // the taps go into a buffer of their own, transposed to the polyphase order [phi][k] = h[phi + k L]; the old one
-        // is freed afterwards, which waits for the calls that still read it
+        // the device's copy is transposed to the polyphase order [phi][k] = h[phi + k L]
         const int L = cfg->interp, P = cfg->taps_per_phase;
         std::vector<float> h((size_t)L * (size_t)P), poly(h.size());
         resample_design(*cfg, h.data());
@@ -2478,158 +2494,154 @@ int32_t sdrg_engine_set_resample(sdrg_engine *e, const sdrg_resample_config *cfg
             for (int k = 0; k < P; k++) poly[(size_t)phi * (size_t)P + (size_t)k] = h[(size_t)phi + (size_t)k * (size_t)L];
         DeviceScope dscope(e->device);
         HIP_TRY(dscope.error());
-        float *fresh = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&fresh), sizeof(float) * poly.size()));
-        hipError_t er = hipMemcpy(fresh, poly.data(), sizeof(float) * poly.size(), hipMemcpyHostToDevice);
-        if (er != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(SDRG_E_HIP, "resample taps upload: %s", hipGetErrorString(er));
-        }
-        if (e->d_rs_taps) (void)hipFree(e->d_rs_taps);
-        e->d_rs_taps = fresh;
-        e->rs_taps.swap(h);
-        e->rs = *cfg;
+        const int32_t rc = upload_floats(&e->rs.d_taps, poly, "resample");
+        if (rc) return rc;
+        e->rs.taps.swap(h);
+        e->rs.cfg = *cfg;
     }
-    e->rs_set = cfg != nullptr;
-    e->rs_cur.restart();
+    e->rs.set = cfg != nullptr;
+    e->rs.cur.restart();
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_get_resample(const sdrg_engine *e, sdrg_resample_config *cfg, float *taps, uint64_t *samples_consumed) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!e->rs_set) return fail(SDRG_E_INVALID, "no resample configuration set");
-    if (cfg) *cfg = e->rs;
-    if (taps) std::copy(e->rs_taps.begin(), e->rs_taps.end(), taps);
-    if (samples_consumed) *samples_consumed = e->rs_cur.g;
+    if (!e->rs.set) return fail(SDRG_E_INVALID, "no resample configuration set");
+    if (cfg) *cfg = e->rs.cfg;
+    if (taps) std::copy(e->rs.taps.begin(), e->rs.taps.end(), taps);
+    if (samples_consumed) *samples_consumed = e->rs.cur.g;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_resample_reset(sdrg_engine *e) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    e->rs_cur.restart();
+    e->rs.cur.restart();
     return SDRG_OK;
 }
-
-static int rs_cap(const sdrg_engine *e) { return ResampleCursor::cap(e->rs.max_in, e->rs.interp, e->rs.decim); }
 
 int32_t sdrg_engine_resample_max_out(const sdrg_engine *e, int32_t *cap) {
     if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
-    if (!e->rs_set) return fail(SDRG_E_INVALID, "no resample configuration set (sdrg_engine_set_resample)");
-    *cap = rs_cap(e);
+    if (int32_t rc = require_set(e->rs.set, "resample")) return rc;
+    *cap = e->rs.cap();
     return SDRG_OK;
 }
 
-// the checks of one resample call, and its n_out, before anything is touched
-static int32_t rs_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, int32_t *n_out) {
-    if (!e->rs_set) return fail(SDRG_E_INVALID, "no resample configuration set (sdrg_engine_set_resample)");
-    if (n < 0 || n > e->rs.max_in) return fail(SDRG_E_INVALID, "resample: n %d outside [0, max_in = %d]", n, e->rs.max_in);
+struct RsCall : StageCall {
+    int in_stride;  // values between the rows of in
+};
+
+static int32_t rs_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, RsCall *c) {
+    const ResampleStage &s = e->rs;
+    if (int32_t rc = require_set(s.set, "resample")) return rc;
+    if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "resample: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
     if (in_stride < n) return fail(SDRG_E_INVALID, "resample: in_stride %d smaller than n %d", in_stride, n);
-    *n_out = e->rs_cur.n_out(n, e->rs.interp, e->rs.decim);
+    c->n = n;
+    c->in_stride = in_stride;
+    c->cap = s.cap();
+    c->n_out = s.cur.n_out(n, s.cfg.interp, s.cfg.decim);
+    c->in_bytes = (size_t)e->n_streams * (size_t)in_stride * (size_t)s.cfg.components * sizeof(float);
+    c->out_bytes = (size_t)e->n_streams * (size_t)c->cap * (size_t)s.cfg.components *
+                   (s.cfg.out_format == SDRG_RESAMPLE_OUT_F32 ? sizeof(float) : sizeof(int16_t));
     return SDRG_OK;
 }
 
-static size_t rs_out_size(const sdrg_engine *e) {
-    return (size_t)e->n_streams * (size_t)rs_cap(e) * (size_t)e->rs.components *
-           (e->rs.out_format == SDRG_RESAMPLE_OUT_F32 ? sizeof(float) : sizeof(int16_t));
-}
+static int32_t rs_reserve(sdrg_engine *e, const RsCall &) { return ensure_device(&e->rs.hist, e->rs.half(e->n_streams)); }
 
 // one resample call on the main stream: in (rows of in_stride values), out in device memory
-static int32_t rs_enqueue(sdrg_engine *e, const void *in, int in_stride, int n, int n_out, void *out) {
-    const sdrg_resample_config &cfg = e->rs;
-    const size_t half = (size_t)e->n_streams * (size_t)(cfg.taps_per_phase - 1) * (size_t)cfg.components;
-    int32_t rc = ensure_device(&e->rs_hist, half);
-    if (rc) return rc;
-    const ResampleCursor &cur = e->rs_cur;
+static int32_t rs_launch(sdrg_engine *e, const RsCall &c, const void *in, void *out) {
+    ResampleStage &s = e->rs;
+    const size_t half = s.half(e->n_streams);
     ResampleParams p{};
-    p.n = n;
-    p.in_stride = in_stride;
-    p.interp = cfg.interp;
-    p.decim = cfg.decim;
-    p.taps_per_phase = cfg.taps_per_phase;
-    p.q0 = cur.q0(cfg.interp, cfg.decim);
-    p.phi0 = cur.phi0(cfg.interp, cfg.decim);
-    p.n_out = n_out;
-    p.cap = rs_cap(e);
-    p.components = cfg.components;
-    p.out_format = cfg.out_format;
-    p.fresh = cur.fresh ? 1 : 0;
-    p.gain = cfg.gain;
-    p.taps = e->d_rs_taps;
-    p.hist_old = e->rs_hist.old(cur, half);
-    p.hist_new = e->rs_hist.next(cur, half);
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.interp = s.cfg.interp;
+    p.decim = s.cfg.decim;
+    p.taps_per_phase = s.cfg.taps_per_phase;
+    p.q0 = s.cur.q0(s.cfg.interp, s.cfg.decim);
+    p.phi0 = s.cur.phi0(s.cfg.interp, s.cfg.decim);
+    p.n_out = c.n_out;
+    p.cap = c.cap;
+    p.components = s.cfg.components;
+    p.out_format = s.cfg.out_format;
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.gain = s.cfg.gain;
+    p.taps = s.d_taps.p;
+    p.hist_old = s.hist.old(s.cur, half);
+    p.hist_new = s.hist.next(s.cur, half);
     HIP_TRY(launch_resample(in, e->n_streams, p, out, e->s_main));
-    e->rs_cur.advance(n);  // a call without samples wrote out only: the state stays where it is
+    s.cur.advance(c.n);  // a call without samples wrote out only: the state stays where it is
     e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
-// sdrg_engine_resample_device (in, out in device memory) and sdrg_engine_resample_host (in host memory)
-static int32_t rs_call(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *out, int32_t *n_out, bool host) {
-    if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!in || !out || !n_out) return fail(SDRG_E_INVALID, "null in, out or n_out");
-    int32_t count;
-    int32_t rc = rs_resolve(e, in_stride, n, &count);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    if (host)
-        rc = host_round_trip(e, &e->rs_in, in, (size_t)e->n_streams * (size_t)in_stride * (size_t)e->rs.components,
-                             &e->rs_out, out, rs_out_size(e),
-                             [&](const float *d_in, char *d_out) { return rs_enqueue(e, d_in, in_stride, n, count, d_out); });
-    else
-        rc = rs_enqueue(e, in, in_stride, n, count, out);
-    if (rc) return rc;
-    *n_out = count;
-    return SDRG_OK;
-}
+static constexpr auto rs_stage = &stage_call<RsCall, rs_resolve, rs_reserve, rs_launch, int32_t, int32_t>;
 
 int32_t sdrg_engine_resample_device(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *out,
                                     int32_t *n_out) {
-    return rs_call(e, in, in_stride, n, out, n_out, false);
+    return rs_stage(e, "in", in, out, n_out, false, in_stride, n);
 }
 
 int32_t sdrg_engine_resample_host(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *out,
                                   int32_t *n_out) {
-    return rs_call(e, in, in_stride, n, out, n_out, true);
+    return rs_stage(e, "in", in, out, n_out, true, in_stride, n);
+}
+
+// ---- the chains: DDC -> demodulator (-> resampler), host memory in and out ------------------------------------------
+
+// Every refusal comes first, in the order the header lists them; then every stage's reserve and the buffers between
+// the stages; then the copy in, the launches, the copy out and the wait.  No x_launch is reachable before every
+// x_reserve of the call has returned SDRG_OK, so a call that fails for want of memory has advanced no stage's cursor:
+// "commits nothing in any stage" (include/sdrg.h) holds for SDRG_E_NOMEM as for the refusals.
+static int32_t chain_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out, bool resample) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    int32_t rc = require_set(e->demod.set, "demod");
+    if (!rc && resample) rc = require_set(e->rs.set, "resample");
+    DdcCall d;
+    DemodCall a;
+    RsCall r;
+    if (!rc) rc = ddc_resolve(e, fmt, &d);
+    if (rc) return rc;
+    // the checks between the stages come before the later stages' own: after them those cannot refuse their n
+    if (e->demod.cfg.max_in < d.cap)
+        return fail(SDRG_E_INVALID, "demod max_in %d smaller than the ddc's row length %d", e->demod.cfg.max_in, d.cap);
+    if (resample) {
+        if (e->demod.cfg.out_format != SDRG_DEMOD_OUT_F32)
+            return fail(SDRG_E_INVALID, "the resampler reads float audio: demod out_format must be SDRG_DEMOD_OUT_F32");
+        if (e->rs.cfg.components != 1)
+            return fail(SDRG_E_INVALID, "the resampler reads real audio: resample components must be 1");
+        if (e->rs.cfg.max_in < e->demod.cap())
+            return fail(SDRG_E_INVALID, "resample max_in %d smaller than the demod's row length %d", e->rs.cfg.max_in,
+                        e->demod.cap());
+    }
+    rc = demod_resolve(e, d.n_out, &a);
+    a.in_stride = d.cap;  // the channel's rows are the DDC's
+    if (!rc && resample) rc = rs_resolve(e, a.cap, a.n_out, &r);
+    if (rc) return rc;
+    const StageCall &last = resample ? static_cast<const StageCall &>(r) : a;
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    rc = ddc_reserve(e, d);
+    if (!rc) rc = demod_reserve(e, a);
+    if (!rc && resample) rc = rs_reserve(e, r);
+    if (!rc) rc = ensure_device(&e->chain_chan, d.out_bytes / sizeof(float));
+    if (!rc && resample) rc = ensure_device(&e->chain_audio, a.out_bytes / sizeof(float));
+    if (!rc) rc = host_begin(e, iq, d.in_bytes, last.out_bytes);
+    if (!rc) rc = ddc_launch(e, d, e->stream_in.p, e->chain_chan.p);
+    if (!rc) rc = demod_launch(e, a, e->chain_chan.p, resample ? (void *)e->chain_audio.p : e->stream_out.p);
+    if (!rc && resample) rc = rs_launch(e, r, e->chain_audio.p, e->stream_out.p);
+    if (!rc) rc = host_end(e, out, last.out_bytes);
+    if (rc) return rc;
+    *n_out = last.n_out;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    return chain_host(e, iq, fmt, out, n_out, false);
 }
 
 int32_t sdrg_engine_ddc_demod_resample_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
-    if (!e->demod_set) return fail(SDRG_E_INVALID, "no demod configuration set (sdrg_engine_set_demod)");
-    if (!e->rs_set) return fail(SDRG_E_INVALID, "no resample configuration set (sdrg_engine_set_resample)");
-    DdcCall c;
-    int32_t rc = ddc_resolve(e, fmt, &c);
-    if (rc) return rc;
-    if (e->demod.max_in < c.cap)
-        return fail(SDRG_E_INVALID, "demod max_in %d smaller than the ddc's row length %d", e->demod.max_in, c.cap);
-    if (e->demod.out_format != SDRG_DEMOD_OUT_F32)
-        return fail(SDRG_E_INVALID, "the resampler reads float audio: demod out_format must be SDRG_DEMOD_OUT_F32");
-    if (e->rs.components != 1) return fail(SDRG_E_INVALID, "the resampler reads real audio: resample components must be 1");
-    const int audio_cap = demod_cap(e);
-    if (e->rs.max_in < audio_cap)
-        return fail(SDRG_E_INVALID, "resample max_in %d smaller than the demod's row length %d", e->rs.max_in, audio_cap);
-    int32_t audio, count;
-    rc = demod_resolve(e, c.n_out, &audio);
-    if (rc) return rc;
-    rc = rs_resolve(e, audio_cap, audio, &count);
-    if (rc) return rc;
-    DeviceScope dscope(e->device);
-    HIP_TRY(dscope.error());
-    const size_t B = (size_t)e->n_streams;
-    rc = ensure_device(&e->ddc_out, B * (size_t)c.cap * 2);  // the channel between the first two stages
-    if (rc) return rc;
-    rc = ensure_device(&e->demod_out, demod_out_size(e));  // the audio between the last two
-    if (rc) return rc;
-    rc = host_round_trip(e, &e->ddc_in, iq, B * (size_t)c.n * bytes_per_sample(fmt), &e->rs_out, out, rs_out_size(e),
-                         [&](const char *d_iq, char *d_out) {
-                             int32_t r = ddc_enqueue(e, c, d_iq, fmt, e->ddc_out.p);
-                             if (!r) r = demod_enqueue(e, e->ddc_out.p, c.cap, c.n_out, audio, e->demod_out.p);
-                             return r ? r : rs_enqueue(e, e->demod_out.p, audio_cap, audio, count, d_out);
-                         });
-    if (rc) return rc;
-    *n_out = count;
-    return SDRG_OK;
+    return chain_host(e, iq, fmt, out, n_out, true);
 }
 
 int32_t sdrg_engine_set_callbacks(sdrg_engine *e, const sdrg_callbacks *cbs) {

@@ -907,6 +907,18 @@ class Engine:
         c = None if off else ctypes.byref(_filled(cls, what, fields))
         _check(getattr(load(), "sdrg_engine_set_" + what)(self._h, c), "set_" + what)
 
+    def _i32_call(self, fn, what: str, *args) -> int:
+        """fn(h, *args, &value) of the library: the int32 it writes, a stage's max_out or a call's n_out."""
+        value = _I32()
+        _check(fn(self._h, *args, ctypes.byref(value)), what)
+        return value.value
+
+    def _iq_call(self, fn, what: str, iq: np.ndarray, fmt: int, make_out) -> np.ndarray:
+        """A host call fn of the library on a frame per stream: the rows make_out() allocates, cut to its n_out."""
+        iq = self._iq(iq, fmt)
+        out = make_out()
+        return out[..., :self._i32_call(fn, what, _ptr(iq), fmt, _ptr(out))]
+
     def signal_strength(self, spectra: np.ndarray, now_ms: int = 0) -> np.ndarray:
         """evaluateSignalStrength alone on caller spectra ([n_streams][samplesPerReading] fftshifted linear power,
         fft_process.cpp:122-379): returns the records; each stream's statistics state advances as in process()."""
@@ -1047,24 +1059,17 @@ class Engine:
 
     def ddc_max_out(self) -> int:
         """ceil(samplesPerReading / decimation): the row length of a ddc call's output, in complex samples."""
-        cap = _I32()
-        _check(load().sdrg_engine_ddc_max_out(self._h, ctypes.byref(cap)), "ddc_max_out")
-        return cap.value
+        return self._i32_call(load().sdrg_engine_ddc_max_out, "ddc_max_out")
 
     def ddc_device(self, iq_ptr: int, fmt: int, out_ptr: int) -> int:
         """Device path: iq [n_streams][N] raw samples in, out [n_streams][ddc_max_out()] complex64 out; asynchronous
         on the main stream.  Returns n_out, the outputs this call produced per stream (the rest of a row is zero)."""
-        n_out = _I32()
-        _check(load().sdrg_engine_ddc_device(self._h, iq_ptr, fmt, out_ptr, ctypes.byref(n_out)), "ddc_device")
-        return n_out.value
+        return self._i32_call(load().sdrg_engine_ddc_device, "ddc_device", iq_ptr, fmt, out_ptr)
 
     def ddc(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
         """Host path: iq is [n_streams][samplesPerReading * 2] raw samples; returns complex64 [n_streams][n_out]."""
-        iq = self._iq(iq, fmt)
-        out = np.empty((self.n_streams, self.ddc_max_out()), np.complex64)
-        n_out = _I32()
-        _check(load().sdrg_engine_ddc_host(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out)), "ddc_host")
-        return out[:, :n_out.value]
+        return self._iq_call(load().sdrg_engine_ddc_host, "ddc_host", iq, fmt,
+                             lambda: np.empty((self.n_streams, self.ddc_max_out()), np.complex64))
 
     # ---- demodulator stage -----------------------------------------------------------------------
     def set_demod(self, **fields) -> None:
@@ -1087,16 +1092,12 @@ class Engine:
 
     def demod_max_out(self) -> int:
         """ceil(max_in / audio_decimation): the row length of a demod call's output."""
-        cap = _I32()
-        _check(load().sdrg_engine_demod_max_out(self._h, ctypes.byref(cap)), "demod_max_out")
-        return cap.value
+        return self._i32_call(load().sdrg_engine_demod_max_out, "demod_max_out")
 
     def demod_device(self, chan_ptr: int, n: int, out_ptr: int) -> int:
         """Device path: chan [n_streams][max_in] complex64 in (the first n of every row are the call's), out
         [n_streams][demod_max_out()] int16 or float32 out; asynchronous on the main stream.  Returns n_out."""
-        n_out = _I32()
-        _check(load().sdrg_engine_demod_device(self._h, chan_ptr, n, out_ptr, ctypes.byref(n_out)), "demod_device")
-        return n_out.value
+        return self._i32_call(load().sdrg_engine_demod_device, "demod_device", chan_ptr, n, out_ptr)
 
     def _demod_out(self) -> np.ndarray:
         fmt = self.demod_config()["out_format"]
@@ -1119,12 +1120,7 @@ class Engine:
     def ddc_demod(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
         """Tune and listen: iq [n_streams][samplesPerReading * 2] raw samples through the DDC and the demodulator, the
         channel left on the device; returns the audio, int16 or float32 [n_streams][n_out]."""
-        iq = self._iq(iq, fmt)
-        out = self._demod_out()
-        n_out = _I32()
-        _check(load().sdrg_engine_ddc_demod_host(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out)),
-               "ddc_demod_host")
-        return out[:, :n_out.value]
+        return self._iq_call(load().sdrg_engine_ddc_demod_host, "ddc_demod_host", iq, fmt, self._demod_out)
 
     # ---- channelizer stage ------------------------------------------------------------------------
     def set_channelizer(self, **fields) -> None:
@@ -1143,29 +1139,21 @@ class Engine:
 
     def channelizer_max_out(self) -> int:
         """ceil(samplesPerReading / (channels / oversample)): the row length of a channelizer call's output."""
-        cap = _I32()
-        _check(load().sdrg_engine_channelizer_max_out(self._h, ctypes.byref(cap)), "channelizer_max_out")
-        return cap.value
+        return self._i32_call(load().sdrg_engine_channelizer_max_out, "channelizer_max_out")
 
     def channelizer_device(self, iq_ptr: int, fmt: int, out_ptr: int) -> int:
         """Device path: iq [n_streams][N] raw samples in, out [n_streams][n_channels][channelizer_max_out()] complex64
         out; asynchronous on the main stream.  Returns n_out, the outputs this call produced per row (the rest of a row
         is zero)."""
-        n_out = _I32()
-        _check(load().sdrg_engine_channelizer_device(self._h, iq_ptr, fmt, out_ptr, ctypes.byref(n_out)),
-               "channelizer_device")
-        return n_out.value
+        return self._i32_call(load().sdrg_engine_channelizer_device, "channelizer_device", iq_ptr, fmt, out_ptr)
 
     def channelizer(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
         """Host path: iq is [n_streams][samplesPerReading * 2] raw samples; returns complex64
         [n_streams][n_channels][n_out]."""
-        iq = self._iq(iq, fmt)
-        rows = self.channelizer_config()["n_channels"]
-        out = np.empty((self.n_streams, rows, self.channelizer_max_out()), np.complex64)
-        n_out = _I32()
-        _check(load().sdrg_engine_channelizer_host(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out)),
-               "channelizer_host")
-        return out[:, :, :n_out.value]
+        def rows():
+            n_rows = self.channelizer_config()["n_channels"]
+            return np.empty((self.n_streams, n_rows, self.channelizer_max_out()), np.complex64)
+        return self._iq_call(load().sdrg_engine_channelizer_host, "channelizer_host", iq, fmt, rows)
 
     # ---- resampler stage --------------------------------------------------------------------------
     def set_resample(self, **fields) -> None:
@@ -1186,18 +1174,13 @@ class Engine:
 
     def resample_max_out(self) -> int:
         """ceil(max_in * interp / decim): the row length of a resample call's output."""
-        cap = _I32()
-        _check(load().sdrg_engine_resample_max_out(self._h, ctypes.byref(cap)), "resample_max_out")
-        return cap.value
+        return self._i32_call(load().sdrg_engine_resample_max_out, "resample_max_out")
 
     def resample_device(self, in_ptr: int, in_stride: int, n: int, out_ptr: int) -> int:
         """Device path: n_streams rows in_stride values apart in (float32, or complex64 at components = 2; the first n
         of every row are the call's), out [n_streams][resample_max_out()] float32, int16 or pairs of them out;
         asynchronous on the main stream.  Returns n_out."""
-        n_out = _I32()
-        _check(load().sdrg_engine_resample_device(self._h, in_ptr, in_stride, n, out_ptr, ctypes.byref(n_out)),
-               "resample_device")
-        return n_out.value
+        return self._i32_call(load().sdrg_engine_resample_device, "resample_device", in_ptr, in_stride, n, out_ptr)
 
     def _resample_out(self) -> np.ndarray:
         c = self.resample_config()
@@ -1224,12 +1207,8 @@ class Engine:
         """Tune and listen at the sound device's rate: iq [n_streams][samplesPerReading * 2] raw samples through the
         DDC, the demodulator (float32 out) and the resampler (components = 1), the channel and the audio left on the
         device; returns the resampled audio, int16 or float32 [n_streams][n_out]."""
-        iq = self._iq(iq, fmt)
-        out = self._resample_out()
-        n_out = _I32()
-        _check(load().sdrg_engine_ddc_demod_resample_host(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out)),
-               "ddc_demod_resample_host")
-        return out[:, :n_out.value]
+        return self._iq_call(load().sdrg_engine_ddc_demod_resample_host, "ddc_demod_resample_host", iq, fmt,
+                             self._resample_out)
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
                        pcm_ptr: int | None, now_ms: int = 0) -> None:

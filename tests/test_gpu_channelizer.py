@@ -1,8 +1,9 @@
 """GPU tests of the channelizer stage (csrc/channelizer.hip, sdrg_engine_channelizer_*): every written row of every
 stream against the float64 model of tests/channelizer_cases.py within its derived bound, on dense noise (the helper also
 asserts that the bound tells the right value from +0, from the neighbouring row and from the previous output).  The zero
-tails are compared as bytes, `out` is pre-filled with 0xAA and 64 guard bytes follow it.  Where the stage promises bytes
-(a stream cut into calls, the same call twice, the host path) bytes are compared.
+tails are compared as bytes, `out` is pre-filled with 0xAA between 64 guard bytes on either side
+(tests/stage_harness.py).  Where the stage promises bytes (a stream cut into calls, the same call twice, the host path)
+bytes are compared.
 
 The kernel works in tiles of sdrg.channelizer_tile_outputs() output times, each staging its window of unpacked samples
 in LDS from aligned 16-byte loads (the ends of a window, and rows that are not 16-byte aligned, sample by sample), with
@@ -16,12 +17,9 @@ import pytest
 
 import channelizer_cases as cc
 import ddc_cases as dd
+from stage_harness import FS, GUARD, engine, invalid, out_buffer, read_out, to_device
 
 pytestmark = pytest.mark.gpu
-
-FS = 2_000_000
-GUARD = 64
-
 
 @pytest.fixture(scope="module")
 def S():
@@ -35,31 +33,6 @@ def T():
     return torch
 
 
-def engine(S, n, B, fs=FS):
-    return S.Engine(S.SDRConfig(centerFrequency=100_000_000, samplesPerReading=n, sampleRate=fs, freqFocusRangeKhz=5,
-                                soundMode=1), B)
-
-
-def invalid(S, fn, *a, **k):
-    with pytest.raises(S.SdrgError) as ei:
-        fn(*a, **k)
-    assert "SDRG_E_INVALID" in str(ei.value)
-
-
-def to_device(T, raw):
-    return T.from_numpy(np.ascontiguousarray(raw)).to("cuda:0")
-
-
-def out_buffer(T, rows, cap):
-    return T.full((rows * cap * 8 + GUARD,), 0xAA, dtype=T.uint8, device="cuda:0")
-
-
-def read_out(out_t, B, rows, cap):
-    o = out_t.cpu().numpy()
-    assert np.all(o[B * rows * cap * 8:] == 0xAA), "bytes written past out"
-    return o[:B * rows * cap * 8].view(np.complex64).reshape(B, rows, cap)
-
-
 def config(M, P, O, first=0, rows=None, cutoff_rel=0.5):
     return dict(cutoff_rel=cutoff_rel, channels=M, taps_per_channel=P, oversample=O, first_channel=first,
                 n_channels=M - first if rows is None else rows)
@@ -70,7 +43,7 @@ class Bank:
 
     def __init__(self, S, T, n, B, **cfg):
         self.S, self.T, self.B = S, T, B
-        self.eng = engine(S, n, B)
+        self.eng = engine(S, B, n)
         self.configure(**cfg)
 
     def configure(self, **cfg):
@@ -83,15 +56,15 @@ class Bank:
         self.model = cc.Bank(self.B, self.S.channelizer_design(**cfg), self.M, self.P, self.O)
 
     def device_call(self, fmt, raw):
-        """channelizer_device into a 0xAA-filled buffer with guard bytes: (out [B][rows][cap] complex64, n_out)."""
+        """channelizer_device into a 0xAA-filled buffer between guard bytes: (out [B][rows][cap] complex64, n_out)."""
         T, eng, rows = self.T, self.eng, self.cfg["n_channels"]
         cap = eng.channelizer_max_out()
         assert cap == -(-eng.cfg.samplesPerReading // (self.M // self.O))
-        iq_t, out_t = to_device(T, raw), out_buffer(T, self.B * rows, cap)
+        iq_t, out_t = to_device(T, raw), out_buffer(T, self.B * rows * cap * 8)
         T.cuda.synchronize()
-        n_out = eng.channelizer_device(iq_t.data_ptr(), fmt, out_t.data_ptr())
+        n_out = eng.channelizer_device(iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
         eng.synchronize()
-        return read_out(out_t, self.B, rows, cap), n_out
+        return read_out(out_t, (self.B, rows, cap), np.complex64), n_out
 
     def expect(self, got, n_out, fmt, raw, what=None, in_step=True):
         """in_step: the engine has made no call beyond this one."""
@@ -182,11 +155,11 @@ def test_iq_base_off_every_alignment(S, T):
         raw = dd.noise(fmt, B, n, seed=70 + shift)
         buf = T.zeros((B * n * 2 + 32,), dtype=T.uint8, device="cuda:0")
         buf[shift:shift + B * n * 2] = to_device(T, raw.view(np.uint8).reshape(-1))
-        out_t = out_buffer(T, B * 8, cap)
+        out_t = out_buffer(T, B * 8 * cap * 8)
         T.cuda.synchronize()
-        n_out = bk.eng.channelizer_device(buf.data_ptr() + shift, fmt, out_t.data_ptr())
+        n_out = bk.eng.channelizer_device(buf.data_ptr() + shift, fmt, out_t.data_ptr() + GUARD)
         bk.eng.synchronize()
-        bk.expect(read_out(out_t, B, 8, cap), n_out, fmt, raw, shift)
+        bk.expect(read_out(out_t, (B, 8, cap), np.complex64), n_out, fmt, raw, shift)
     bk.close()
 
 
@@ -328,11 +301,11 @@ def test_restarts(S, T):
 
 def test_refusals_write_nothing_and_commit_nothing(S, T):
     n, B, fmt = 800, 2, dd.CS16
-    eng = engine(S, n, B)
+    eng = engine(S, B, n)
     iq_t = to_device(T, dd.noise(fmt, B, n, seed=170))
-    out_t = out_buffer(T, B * 16, n)
+    out_t = out_buffer(T, B * 16 * n * 8)
     T.cuda.synchronize()
-    invalid(S, eng.channelizer_device, iq_t.data_ptr(), fmt, out_t.data_ptr())  # before any set_channelizer
+    invalid(S, eng.channelizer_device, iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)  # before any set_channelizer
     invalid(S, eng.channelizer_max_out)
     invalid(S, eng.channelizer_config)
     eng.close()
@@ -340,16 +313,16 @@ def test_refusals_write_nothing_and_commit_nothing(S, T):
     cfg = config(16, 4, 1)
     bk = Bank(S, T, n, B, **cfg)
     bk.check(fmt, dd.noise(fmt, B, n, seed=171))
-    invalid(S, bk.eng.channelizer_device, iq_t.data_ptr(), 99, out_t.data_ptr())
+    invalid(S, bk.eng.channelizer_device, iq_t.data_ptr(), 99, out_t.data_ptr() + GUARD)
     L, n_out = S.load(), ctypes.c_int32(-7)
-    assert L.sdrg_engine_channelizer_device(bk.eng._h, None, fmt, out_t.data_ptr(), ctypes.byref(n_out)) == -1
+    assert L.sdrg_engine_channelizer_device(bk.eng._h, None, fmt, out_t.data_ptr() + GUARD, ctypes.byref(n_out)) == -1
     assert L.sdrg_engine_channelizer_device(bk.eng._h, iq_t.data_ptr(), fmt, None, ctypes.byref(n_out)) == -1
-    assert L.sdrg_engine_channelizer_device(bk.eng._h, iq_t.data_ptr(), fmt, out_t.data_ptr(), None) == -1
+    assert L.sdrg_engine_channelizer_device(bk.eng._h, iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD, None) == -1
     assert L.sdrg_engine_channelizer_host(bk.eng._h, None, fmt, None, ctypes.byref(n_out)) == -1
     assert n_out.value == -7 and bk.eng.channelizer_config()["samples_consumed"] == n
     bk.check(fmt, dd.noise(fmt, B, n, seed=172), "after refused calls")
     bk.eng.set_channelizer(off=True)
-    invalid(S, bk.eng.channelizer_device, iq_t.data_ptr(), fmt, out_t.data_ptr())
+    invalid(S, bk.eng.channelizer_device, iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
     bk.eng.synchronize()
     assert np.all(out_t.cpu().numpy() == 0xAA), "a refused call wrote to out"
     bk.configure(**cfg)
@@ -361,7 +334,7 @@ def test_host_path_equals_device_path(S, T):
     n, B, fmt = 2500, 5, dd.CU8
     cfg = config(32, 5, 2, first=3, rows=20)
     dev = Bank(S, T, n, B, **cfg)
-    host = engine(S, n, B)
+    host = engine(S, B, n)
     host.set_channelizer(**cfg)
     for f in range(3):
         raw = dd.noise(fmt, B, n, seed=180 + f)
@@ -377,19 +350,19 @@ def test_wait_outputs_orders_a_consumer_stream(S, T):
     bk = Bank(S, T, n, B, **config(64, 8, 2, first=0, rows=16))
     cap = bk.eng.channelizer_max_out()
     consumer = T.cuda.Stream("cuda:0")
-    out_t = out_buffer(T, B * 16, cap)
+    out_t = out_buffer(T, B * 16 * cap * 8)
     copy = T.zeros_like(out_t)
     T.cuda.synchronize()
     for f in range(3):
         raw = dd.noise(fmt, B, n, seed=190 + f)
         iq_t = to_device(T, raw)
         T.cuda.synchronize()
-        n_out = bk.eng.channelizer_device(iq_t.data_ptr(), fmt, out_t.data_ptr())
+        n_out = bk.eng.channelizer_device(iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
         bk.eng.wait_outputs(consumer.cuda_stream)
         with T.cuda.stream(consumer):
             copy.copy_(out_t)
         consumer.synchronize()
-        bk.expect(read_out(copy, B, 16, cap), n_out, fmt, raw, f)
+        bk.expect(read_out(copy, (B, 16, cap), np.complex64), n_out, fmt, raw, f)
     bk.close()
 
 
@@ -417,16 +390,16 @@ def test_process_device_and_ddc_between_channelizer_calls(S, T, mode):
         return iq_t, spec, rec, pcm, ddc
 
     bk = Bank(S, T, n, B, **config(16, 8, 2))
-    plain = engine(S, n, B)
+    plain = engine(S, B, n)
     for eng in (bk.eng, plain):
         eng.set_pipelining(bits)
         eng.set_ddc(**ddc_cfg)
     cap = bk.eng.channelizer_max_out()
     outs, iqs, held = [], [], []
     for f in range(3):
-        iq_t, out_t = to_device(T, raws[f]), out_buffer(T, B * 16, cap)
+        iq_t, out_t = to_device(T, raws[f]), out_buffer(T, B * 16 * cap * 8)
         T.cuda.synchronize()
-        n_out = bk.eng.channelizer_device(iq_t.data_ptr(), fmt, out_t.data_ptr())
+        n_out = bk.eng.channelizer_device(iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
         outs.append((out_t, n_out))
         iqs.append(iq_t)
         if f < 2:
@@ -434,7 +407,7 @@ def test_process_device_and_ddc_between_channelizer_calls(S, T, mode):
     bk.eng.synchronize()
     plain.synchronize()
     for f, (out_t, n_out) in enumerate(outs):
-        bk.expect(read_out(out_t, B, 16, cap), n_out, fmt, raws[f], (mode, f), in_step=False)
+        bk.expect(read_out(out_t, (B, 16, cap), np.complex64), n_out, fmt, raws[f], (mode, f), in_step=False)
     assert bk.eng.channelizer_config()["samples_consumed"] == 3 * n
     for f, (a, b) in enumerate(held):
         for x, y, name in zip(a[1:], b[1:], ("spectra", "records", "pcm", "ddc")):
@@ -461,7 +434,7 @@ def test_rows_against_the_engines_own_ddc(S, T):
         assert offset == (k - M // 2) * FS / M
         cfg = dict(offset_hz=offset, cutoff_hz=0.5 * FS / M, decimation=D, taps=L - 1)
         assert S.ddc_design(FS, **cfg).tobytes() == h[:L - 1].tobytes()
-        ddc = engine(S, n, B)
+        ddc = engine(S, B, n)
         ddc.set_ddc(**cfg)
         for f, raw in enumerate(raws):
             want = ddc.ddc(raw, fmt)
@@ -495,10 +468,10 @@ def test_two_fm_carriers_end_to_end(S, T):
     iq[0, 0::2], iq[0, 1::2] = z.real, z.imag
     raw = np.round(iq * 128.0).clip(-128, 127).astype(np.int8)
 
-    bank = engine(S, n, B)
+    bank = engine(S, B, n)
     bank.set_channelizer(**config(M, P, O, cutoff_rel=0.4))
     cap = bank.channelizer_max_out()
-    audio = engine(S, 1024, M * B)
+    audio = engine(S, M * B, 1024)
     audio.set_demod(mode=S.DEMOD_FM, channel_rate_hz=fc, deviation_hz=dev, dc_cutoff_hz=0.0, deemphasis_us=0.0,
                     audio_decimation=R, audio_taps=255, audio_cutoff_hz=3000.0, gain=1.0, out_format=S.DEMOD_OUT_F32,
                     max_in=cap)

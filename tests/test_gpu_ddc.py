@@ -1,7 +1,7 @@
 """GPU tests of the DDC stage (csrc/ddc.hip, sdrg_engine_ddc_*): the tuned, filtered, decimated CF32 channel of each
 stream against the NumPy restatement in tests/ddc_cases.py fed the library's own taps and phasor tables.  Every
 comparison is of the bytes of the whole output (the stage is specified operation by operation: no tolerances), `out` is
-pre-filled with 0xAA and 64 guard bytes follow it.
+pre-filled with 0xAA between 64 guard bytes on either side (tests/stage_harness.py).
 
 The kernel works in tiles of sdrg.ddc_tile_outputs(D, T) outputs, each staging its window of mixed samples in LDS from
 aligned 16-byte loads (the ends of a window, and rows that are not 16-byte aligned, sample by sample), with the samples
@@ -13,12 +13,9 @@ import numpy as np
 import pytest
 
 import ddc_cases as dd
+from stage_harness import FS, GUARD, engine, invalid, out_buffer, read_out, same, to_device
 
 pytestmark = pytest.mark.gpu
-
-FS = 2_000_000
-GUARD = 64
-
 
 @pytest.fixture(scope="module")
 def S():
@@ -37,37 +34,12 @@ def tab(S):
     return S.nco_tables()
 
 
-def engine(S, n, B, fs=FS):
-    return S.Engine(S.SDRConfig(centerFrequency=100_000_000, samplesPerReading=n, sampleRate=fs, freqFocusRangeKhz=5,
-                                soundMode=1), B)
-
-
-def invalid(S, fn, *a, **k):
-    with pytest.raises(S.SdrgError) as ei:
-        fn(*a, **k)
-    assert "SDRG_E_INVALID" in str(ei.value)
-
-
-def to_device(T, raw):
-    return T.from_numpy(np.ascontiguousarray(raw)).to("cuda:0")
-
-
-def out_buffer(T, B, cap):
-    return T.full((B * cap * 8 + GUARD,), 0xAA, dtype=T.uint8, device="cuda:0")
-
-
-def read_out(out_t, B, cap):
-    o = out_t.cpu().numpy()
-    assert np.all(o[B * cap * 8:] == 0xAA), "bytes written past out"
-    return o[:B * cap * 8].view(np.complex64).reshape(B, cap)
-
-
 class Channel:
     """An engine with the DDC set, and the restatement that follows it call by call."""
 
     def __init__(self, S, T, tab, n, B, fs=FS, **cfg):
         self.S, self.T, self.tab, self.B, self.fs = S, T, tab, B, fs
-        self.eng = engine(S, n, B, fs)
+        self.eng = engine(S, B, n, fs)
         self.configure(**cfg)
 
     def configure(self, **cfg):
@@ -83,14 +55,14 @@ class Channel:
         self.model = dd.Ddc(self.B, h, self.tab, got["nco_increment"], self.cfg["decimation"])
 
     def device_call(self, fmt, raw):
-        """ddc_device into a 0xAA-filled buffer with guard bytes: (out [B][cap] complex64, n_out)."""
+        """ddc_device into a 0xAA-filled buffer between guard bytes: (out [B][cap] complex64, n_out)."""
         T, eng = self.T, self.eng
         cap = eng.ddc_max_out()
-        iq_t, out_t = to_device(T, raw), out_buffer(T, self.B, cap)
+        iq_t, out_t = to_device(T, raw), out_buffer(T, self.B * cap * 8)
         T.cuda.synchronize()
-        n_out = eng.ddc_device(iq_t.data_ptr(), fmt, out_t.data_ptr())
+        n_out = eng.ddc_device(iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
         eng.synchronize()
-        return read_out(out_t, self.B, cap), n_out
+        return read_out(out_t, (self.B, cap), np.complex64), n_out
 
     def check(self, fmt, raw, what=None):
         got, n_out = self.device_call(fmt, raw)
@@ -101,12 +73,6 @@ class Channel:
 
     def close(self):
         self.eng.close()
-
-
-def same(got, n_out, want, want_n, what=None):
-    assert n_out == want_n and got.shape == want.shape, (what, n_out, want_n, got.shape, want.shape)
-    bad = np.argwhere(got.view(np.uint64) != want.view(np.uint64))
-    assert got.tobytes() == want.tobytes(), (what, len(bad), [(tuple(i), got[tuple(i)], want[tuple(i)]) for i in bad[:4]])
 
 
 @pytest.mark.parametrize("fmt", [dd.CS8, dd.CU8, dd.CS16, dd.CF32])
@@ -147,12 +113,12 @@ def test_iq_base_off_every_alignment(S, T, tab):
         raw = dd.noise(fmt, B, n, seed=40 + shift)
         buf = T.zeros((B * n * 2 + 32,), dtype=T.uint8, device="cuda:0")
         buf[shift:shift + B * n * 2] = to_device(T, raw.view(np.uint8).reshape(-1))
-        out_t = out_buffer(T, B, cap)
+        out_t = out_buffer(T, B * cap * 8)
         T.cuda.synchronize()
-        n_out = ch.eng.ddc_device(buf.data_ptr() + shift, fmt, out_t.data_ptr())
+        n_out = ch.eng.ddc_device(buf.data_ptr() + shift, fmt, out_t.data_ptr() + GUARD)
         ch.eng.synchronize()
         want, want_n = ch.model.call(fmt, raw)
-        same(read_out(out_t, B, cap), n_out, want, want_n, shift)
+        same(read_out(out_t, (B, cap), np.complex64), n_out, want, want_n, shift)
     ch.close()
 
 
@@ -287,11 +253,11 @@ def test_restarts(S, T, tab):
 
 def test_refusals_write_nothing_and_commit_nothing(S, T, tab):
     n, B, fmt = 800, 2, dd.CS16
-    eng = engine(S, n, B)
+    eng = engine(S, B, n)
     iq_t = to_device(T, dd.noise(fmt, B, n, seed=140))
-    out_t = out_buffer(T, B, n)
+    out_t = out_buffer(T, B * n * 8)
     T.cuda.synchronize()
-    invalid(S, eng.ddc_device, iq_t.data_ptr(), fmt, out_t.data_ptr())  # before any set_ddc
+    invalid(S, eng.ddc_device, iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)  # before any set_ddc
     invalid(S, eng.ddc_max_out)
     invalid(S, eng.ddc_config)
     eng.close()
@@ -301,21 +267,22 @@ def test_refusals_write_nothing_and_commit_nothing(S, T, tab):
     ch.check(fmt, dd.noise(fmt, B, n, seed=141))
     # the rate drops so that cutoff_hz > fs / 2: the call fails, g0 and the history stay
     ch.eng.setSampleRate(1_000_000)
-    invalid(S, ch.eng.ddc_device, iq_t.data_ptr(), fmt, out_t.data_ptr())
-    invalid(S, ch.eng.ddc_device, iq_t.data_ptr(), 99, out_t.data_ptr())
+    invalid(S, ch.eng.ddc_device, iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
+    invalid(S, ch.eng.ddc_device, iq_t.data_ptr(), 99, out_t.data_ptr() + GUARD)
     assert ch.eng.ddc_config()["samples_consumed"] == n
     ch.eng.setSampleRate(FS)
     ch.check(fmt, dd.noise(fmt, B, n, seed=142), "after a refused call")
     # off: refused again, and set once more it starts afresh
     ch.eng.set_ddc(off=True)
-    invalid(S, ch.eng.ddc_device, iq_t.data_ptr(), fmt, out_t.data_ptr())
+    invalid(S, ch.eng.ddc_device, iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
     ch.eng.synchronize()
     assert np.all(out_t.cpu().numpy() == 0xAA), "a refused call wrote to out"
     ch.configure(**cfg)
     ch.check(fmt, dd.noise(fmt, B, n, seed=143), "after off and on")
     L = S.load()
-    assert L.sdrg_engine_ddc_device(ch.eng._h, None, fmt, out_t.data_ptr(), ctypes.byref(ctypes.c_int32())) == -1
-    assert L.sdrg_engine_ddc_device(ch.eng._h, iq_t.data_ptr(), fmt, out_t.data_ptr(), None) == -1
+    n_out = ctypes.c_int32()
+    assert L.sdrg_engine_ddc_device(ch.eng._h, None, fmt, out_t.data_ptr() + GUARD, ctypes.byref(n_out)) == -1
+    assert L.sdrg_engine_ddc_device(ch.eng._h, iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD, None) == -1
     ch.check(fmt, dd.noise(fmt, B, n, seed=144), "after null arguments")
     ch.close()
 
@@ -324,7 +291,7 @@ def test_host_path_equals_device_path(S, T, tab):
     n, B, fmt = 2500, 5, dd.CU8
     cfg = dict(offset_hz=77_000.0, cutoff_hz=40_000.0, decimation=9, taps=95)
     dev = Channel(S, T, tab, n, B, **cfg)
-    host = engine(S, n, B)
+    host = engine(S, B, n)
     host.set_ddc(**cfg)
     for f in range(3):
         raw = dd.noise(fmt, B, n, seed=150 + f)
@@ -340,20 +307,20 @@ def test_wait_outputs_orders_a_consumer_stream(S, T, tab):
     ch = Channel(S, T, tab, n, B, offset_hz=10_000.0, cutoff_hz=20_000.0, decimation=41, taps=255)
     cap = ch.eng.ddc_max_out()
     consumer = T.cuda.Stream("cuda:0")
-    out_t = out_buffer(T, B, cap)
+    out_t = out_buffer(T, B * cap * 8)
     copy = T.zeros_like(out_t)
     T.cuda.synchronize()
     for f in range(3):
         raw = dd.noise(fmt, B, n, seed=160 + f)
         iq_t = to_device(T, raw)
         T.cuda.synchronize()
-        n_out = ch.eng.ddc_device(iq_t.data_ptr(), fmt, out_t.data_ptr())
+        n_out = ch.eng.ddc_device(iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
         ch.eng.wait_outputs(consumer.cuda_stream)
         with T.cuda.stream(consumer):
             copy.copy_(out_t)
         consumer.synchronize()
         want, want_n = ch.model.call(fmt, raw)
-        same(read_out(copy, B, cap), n_out, want, want_n, f)
+        same(read_out(copy, (B, cap), np.complex64), n_out, want, want_n, f)
     ch.close()
 
 
@@ -379,14 +346,14 @@ def test_process_device_between_ddc_calls(S, T, tab, mode):
 
     ch = Channel(S, T, tab, n, B, offset_hz=20_000.0, cutoff_hz=20_000.0, decimation=41, taps=255)
     ch.eng.set_pipelining(bits)
-    plain = engine(S, n, B)
+    plain = engine(S, B, n)
     plain.set_pipelining(bits)
     cap = ch.eng.ddc_max_out()
     outs, iqs, held = [], [], []
     for f in range(3):
-        iq_t, out_t = to_device(T, raws[f]), out_buffer(T, B, cap)
+        iq_t, out_t = to_device(T, raws[f]), out_buffer(T, B * cap * 8)
         T.cuda.synchronize()
-        n_out = ch.eng.ddc_device(iq_t.data_ptr(), fmt, out_t.data_ptr())
+        n_out = ch.eng.ddc_device(iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
         outs.append((out_t, n_out))
         iqs.append(iq_t)
         if f < 2:
@@ -395,7 +362,7 @@ def test_process_device_between_ddc_calls(S, T, tab, mode):
     plain.synchronize()
     for f, (out_t, n_out) in enumerate(outs):
         want, want_n = ch.model.call(fmt, raws[f])
-        same(read_out(out_t, B, cap), n_out, want, want_n, (mode, f))
+        same(read_out(out_t, (B, cap), np.complex64), n_out, want, want_n, (mode, f))
     for f, (a, b) in enumerate(held):
         for x, y, name in zip(a[1:], b[1:], ("spectra", "records", "pcm")):
             assert x.cpu().numpy().tobytes() == y.cpu().numpy().tobytes(), (mode, f, name)
@@ -412,25 +379,25 @@ def test_zoom_fft(S, T, tab):
     offset = 300_000.0
     f_tone = offset + 25 * (125000 / 1024)
     ch = Channel(S, T, tab, n, B, offset_hz=offset, cutoff_hz=50_000.0, decimation=D, taps=255)
-    zoom = engine(S, 1024, B, fs=125000)
+    zoom = engine(S, B, 1024, fs=125000)
     cap = ch.eng.ddc_max_out()
     assert cap == 1024
     spec = T.zeros((B, 1024), dtype=T.float32, device="cuda:0")
-    out_t = out_buffer(T, B, cap)
+    out_t = out_buffer(T, B * cap * 8)
     for f in range(2):  # the second frame is past the filter's transient
         raw = dd.tone(fmt, B, 2 * n, f_tone / FS, amp=0.5)[:, 2 * n * f:2 * n * (f + 1)]
         iq_t = to_device(T, raw)
         T.cuda.synchronize()
-        n_out = ch.eng.ddc_device(iq_t.data_ptr(), fmt, out_t.data_ptr())
+        n_out = ch.eng.ddc_device(iq_t.data_ptr(), fmt, out_t.data_ptr() + GUARD)
         assert n_out == 1024
         ch.eng.synchronize()
-        zoom.process_device(out_t.data_ptr(), S.CF32, S.STAGE_SPECTRUM, spec.data_ptr(), None, None, 1000 + f)
+        zoom.process_device(out_t.data_ptr() + GUARD, S.CF32, S.STAGE_SPECTRUM, spec.data_ptr(), None, None, 1000 + f)
         zoom.synchronize()
         want, _ = ch.model.call(fmt, raw)
     got_spec = spec.cpu().numpy()
-    assert read_out(out_t, B, cap).tobytes() == want.tobytes()
+    assert read_out(out_t, (B, cap), np.complex64).tobytes() == want.tobytes()
     assert np.argmax(got_spec, axis=1).tolist() == [537] * B
-    ref = engine(S, 1024, B, fs=125000)
+    ref = engine(S, B, 1024, fs=125000)
     ref_spec, _, _ = ref.process(want.view(np.float32).reshape(B, -1), fmt=S.CF32, stages=S.STAGE_SPECTRUM, now_ms=1001)
     assert got_spec.tobytes() == ref_spec.tobytes()
     for e in (ch, zoom, ref):

@@ -17,10 +17,10 @@ from conftest import ROOT
 
 import ddc_cases as dd
 import demod_cases as dm
+from stage_harness import GUARD, engine, invalid, out_buffer, read_out, same
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 BASE = dict(mode=dm.FM, channel_rate_hz=200_000.0, deviation_hz=75_000.0, dc_cutoff_hz=300.0, deemphasis_us=75.0,
             audio_decimation=4, audio_taps=31, audio_cutoff_hz=15_000.0, gain=0.7, out_format=dm.OUT_F32, max_in=1024)
 
@@ -37,41 +37,12 @@ def T():
     return torch
 
 
-def engine(S, B, n=1024, fs=2_000_000):
-    return S.Engine(S.SDRConfig(centerFrequency=100_000_000, samplesPerReading=n, sampleRate=fs, freqFocusRangeKhz=5,
-                                soundMode=1), B)
-
-
-def invalid(S, fn, *a, **k):
-    with pytest.raises(S.SdrgError) as ei:
-        fn(*a, **k)
-    assert "SDRG_E_INVALID" in str(ei.value)
-
-
 def rows_on_device(T, chan, max_in):
     """chan complex64 [B][n] -> a device tensor [B][max_in][2] float32, NaN past n."""
     B, n = chan.shape
     rows = np.full((B, max_in, 2), np.nan, np.float32)
     rows[:, :n] = np.ascontiguousarray(chan).view(np.float32).reshape(B, n, 2)
     return T.from_numpy(rows).to("cuda:0")
-
-
-def out_buffer(T, nbytes):
-    return T.full((GUARD + nbytes + GUARD,), 0xAA, dtype=T.uint8, device="cuda:0")
-
-
-def read_out(out_t, B, cap, dtype):
-    o = out_t.cpu().numpy()
-    nbytes = B * cap * np.dtype(dtype).itemsize
-    assert np.all(o[:GUARD] == 0xAA) and np.all(o[GUARD + nbytes:] == 0xAA), "bytes written outside out"
-    return o[GUARD:GUARD + nbytes].view(dtype).reshape(B, cap)
-
-
-def same(got, n_out, want, want_n, what=None):
-    assert n_out == want_n and got.shape == want.shape and got.dtype == want.dtype, (what, n_out, want_n, got.shape)
-    bits = {2: np.uint16, 4: np.uint32}[got.dtype.itemsize]
-    bad = np.argwhere(got.view(bits) != want.view(bits))
-    assert got.tobytes() == want.tobytes(), (what, len(bad), [(tuple(i), got[tuple(i)], want[tuple(i)]) for i in bad[:4]])
 
 
 class Audio:
@@ -108,7 +79,7 @@ class Audio:
         T.cuda.synchronize()
         n_out = eng.demod_device(chan_t.data_ptr(), chan.shape[1], out_t.data_ptr() + GUARD)
         eng.synchronize()
-        return read_out(out_t, self.B, cap, self.dtype), n_out
+        return read_out(out_t, (self.B, cap), self.dtype), n_out
 
     def check(self, chan, what=None):
         got, n_out = self.device_call(chan)
@@ -383,7 +354,7 @@ def test_wait_outputs_orders_a_consumer_stream(S, T):
             copy.copy_(out_t)
         consumer.synchronize()
         want, want_n = au.model.call(chan)
-        same(read_out(copy, B, cap, np.float32), n_out, want, want_n, f)
+        same(read_out(copy, (B, cap), np.float32), n_out, want, want_n, f)
     au.close()
 
 
@@ -427,7 +398,7 @@ def test_process_device_and_ddc_device_between_demod_calls(S, T):
     plain.synchronize()
     for f, (out_t, n_out, _) in enumerate(outs):
         want, want_n = au.model.call(chans[f])
-        same(read_out(out_t, B, cap, np.float32), n_out, want, want_n, f)
+        same(read_out(out_t, (B, cap), np.float32), n_out, want, want_n, f)
     for f, (d_t, n_out, _) in enumerate(ddc_outs):
         want, want_n = ddc_model.call(fmt, raws[f])
         assert n_out == want_n and d_t.cpu().numpy().tobytes() == want.tobytes(), f

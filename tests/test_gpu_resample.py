@@ -15,10 +15,10 @@ import pytest
 import ddc_cases as dd
 import demod_cases as dm
 import resample_cases as rs
+from stage_harness import GUARD, engine, invalid, out_buffer, read_out, same
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 BASE = dict(interp=3, decim=2, taps_per_phase=8, cutoff_rel=0.9, components=1, out_format=rs.OUT_F32, gain=0.7,
             max_in=1024)
 RATIOS = [(3, 2, 8), (2, 3, 8), (123, 125, 16), (147, 160, 24), (8, 1, 4), (1, 8, 64), (512, 511, 16), (7, 5, 1)]
@@ -36,17 +36,6 @@ def T():
     return torch
 
 
-def engine(S, B, n=1024, fs=2_000_000):
-    return S.Engine(S.SDRConfig(centerFrequency=100_000_000, samplesPerReading=n, sampleRate=fs, freqFocusRangeKhz=5,
-                                soundMode=1), B)
-
-
-def invalid(S, fn, *a, **k):
-    with pytest.raises(S.SdrgError) as ei:
-        fn(*a, **k)
-    assert "SDRG_E_INVALID" in str(ei.value)
-
-
 def rows_on_device(T, x, stride, components):
     """x [B][n] (float32, or complex64 at components 2) -> a device tensor [B][stride][components] float32, NaN past
     n."""
@@ -55,24 +44,6 @@ def rows_on_device(T, x, stride, components):
     rows = np.full((B, max(stride, 1), components), np.nan, np.float32)
     rows[:, :n] = v
     return T.from_numpy(rows).to("cuda:0")
-
-
-def out_buffer(T, nbytes):
-    return T.full((GUARD + nbytes + GUARD,), 0xAA, dtype=T.uint8, device="cuda:0")
-
-
-def read_out(out_t, shape, dtype):
-    o = out_t.cpu().numpy()
-    nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    assert np.all(o[:GUARD] == 0xAA) and np.all(o[GUARD + nbytes:] == 0xAA), "bytes written outside out"
-    return o[GUARD:GUARD + nbytes].view(dtype).reshape(shape)
-
-
-def same(got, n_out, want, want_n, what=None):
-    assert n_out == want_n and got.shape == want.shape and got.dtype == want.dtype, (what, n_out, want_n, got.shape)
-    bits = {2: np.uint16, 4: np.uint32}[got.dtype.itemsize]
-    bad = np.argwhere(got.view(bits) != want.view(bits))
-    assert got.tobytes() == want.tobytes(), (what, len(bad), [(tuple(i), got[tuple(i)], want[tuple(i)]) for i in bad[:4]])
 
 
 class Rows:

@@ -12,7 +12,7 @@ import pytest
 import sdrg
 
 B, N = 3, 8
-STAGES = ("display", "integration", "peaks", "ddc", "demod", "channelizer")
+STAGES = ("display", "integration", "peaks", "ddc", "demod", "channelizer", "resample")
 
 
 class Library:
@@ -61,6 +61,7 @@ CONFIGS = [  # (structure, its setter, its getter, the fields given)
     (sdrg.DdcConfig, "set_ddc", "ddc_config", dict(offset_hz=-1250.5, taps=41)),
     (sdrg.DemodConfig, "set_demod", "demod_config", dict(deviation_hz=5000.0, audio_taps=3, gain=0.5, max_in=64)),
     (sdrg.ChannelizerConfig, "set_channelizer", "channelizer_config", dict(cutoff_rel=0.75, channels=16, n_channels=2)),
+    (sdrg.ResampleConfig, "set_resample", "resample_config", dict(interp=3, taps_per_phase=8, gain=0.5, max_in=64)),
 ]
 
 
@@ -77,7 +78,7 @@ def test_fields_fill_a_structure_and_read_back(eng, lib, cls, setter, getter, gi
     assert all(type(got[k]) is type(getattr(kept, k)) for k in names)
 
 
-@pytest.mark.parametrize("what", ("display", "peaks", "ddc", "demod", "channelizer"))
+@pytest.mark.parametrize("what", ("display", "peaks", "ddc", "demod", "channelizer", "resample"))
 def test_unknown_field(eng, lib, what):
     with pytest.raises(TypeError) as ei:
         getattr(eng, "set_" + what)(x=1)
@@ -86,7 +87,8 @@ def test_unknown_field(eng, lib, what):
 
 
 @pytest.mark.parametrize("fn,what", ((sdrg.demod_design, "demod"), (sdrg.channelizer_design, "channelizer"),
-                                     (sdrg.channelizer_tile_outputs, "channelizer")))
+                                     (sdrg.channelizer_tile_outputs, "channelizer"), (sdrg.resample_design, "resample"),
+                                     (sdrg.resample_tile_outputs, "resample")))
 def test_unknown_field_of_a_design_function(lib, fn, what):
     with pytest.raises(TypeError) as ei:
         fn(x=1)
@@ -94,7 +96,7 @@ def test_unknown_field_of_a_design_function(lib, fn, what):
     assert lib.calls == []
 
 
-@pytest.mark.parametrize("what", ("ddc", "demod", "channelizer"))
+@pytest.mark.parametrize("what", ("ddc", "demod", "channelizer", "resample"))
 def test_off(eng, lib, what):
     setter = getattr(eng, "set_" + what)
     with pytest.raises(TypeError) as ei:
@@ -147,13 +149,17 @@ def test_no_spectra_is_a_null_pointer(eng, lib, method):
 
 
 IQ_CALLS = (("ddc", "sdrg_engine_ddc_host"), ("ddc_demod", "sdrg_engine_ddc_demod_host"),
-            ("channelizer", "sdrg_engine_channelizer_host"))
+            ("channelizer", "sdrg_engine_channelizer_host"),
+            ("ddc_demod_resample_host", "sdrg_engine_ddc_demod_resample_host"))
 
 
 @pytest.mark.parametrize("fmt", (sdrg.CF32, sdrg.CS8, sdrg.CU8, sdrg.CS16))
 @pytest.mark.parametrize("method,entry", IQ_CALLS, ids=[c[0] for c in IQ_CALLS])
 def test_iq(eng, lib, method, entry, fmt):
     call = getattr(eng, method)
+    if method == "ddc_demod_resample_host":  # sizes its output from the resampler's configuration
+        eng.set_resample(interp=3, decim=2, taps_per_phase=8, components=1, max_in=64)
+        lib.calls.clear()
     for bad in (np.zeros((B, 2 * N + 1), np.int8), np.zeros(B * N, np.int8)):
         with pytest.raises(sdrg.SdrgError) as ei:
             call(bad, fmt=fmt)
