@@ -977,6 +977,106 @@ int32_t sdrg_engine_resample_host(sdrg_engine *eng, const void *in, int32_t in_s
  * max_in smaller than the demodulator's cap; a refused call commits nothing in any stage. */
 int32_t sdrg_engine_ddc_demod_resample_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the squelch stage, a power gate with hysteresis and a level read-out per
+ * channel.  Per stream, the n CF32 channel samples of a call (the DDC's out, a row of the channelizer's, or any rows in
+ * device memory) are cut into blocks of S samples at the global indices that are multiples of S.  Each completed
+ * block's mean power updates a smoothed level; a hysteresis gate with a hang time decides from that level how the next
+ * block passes; a transition is ramped over one block; a record per stream reports the level and the gate.  A decision
+ * never reaches back into the block that produced it: the stage adds no delay and out has one sample per input sample.
+ * Over the whole life of a stream (the calls' samples concatenated, whatever their lengths) the result is that of one
+ * call.  A sample gated to (+0, +0) is silence in both detectors of the demodulator (sqrtf(0) = +0, sdrg_atan2f(+-0,
+ * +-0) kf = +-0), so one gate in front of it serves every mode.  All arithmetic is float, every product and sum rounded
+ * on its own, unless "double" is stated; denormals are kept.  A non-finite input sample makes that stream's outputs and
+ * records unspecified from then on.
+ *   config     open_db, close_db finite with close_db <= open_db; tau_blocks finite, >= 0; block S a power of two in
+ *              [SDRG_SQUELCH_MIN_BLOCK, SDRG_SQUELCH_MAX_BLOCK]; hang_blocks H in [0, SDRG_SQUELCH_MAX_HANG]; max_in in
+ *              [1, 2^20]: every call's n <= in_stride <= max_in.  A rejected set_squelch changes nothing; an accepted
+ *              one, and sdrg_engine_squelch_reset, restart every stream: g = 0, L = +0, closed, hang 0, the current
+ *              block's code 0.
+ *   design     sdrg_squelch_design, in double, each result rounded to float once: open_thr = 10^(open_db / 10),
+ *              close_thr = 10^(close_db / 10), refused if either is not finite and positive as a float; beta =
+ *              1 - exp(-1 / tau_blocks), and beta = 1.0f exactly when tau_blocks is 0.  0 dB is a channel of mean
+ *              power 1.
+ *   power      sample j of a block (its in-block index: the global index mod S) has p_j = zr zr + zi zi: two rounded
+ *              products, one rounded sum.  The block's sum is the adjacent-pair tree over its S powers: q'[i] =
+ *              q[2 i] + q[2 i + 1], repeated until one value is left; P = q[0] * (1 / S).
+ *   level      for each completed block, in order: if beta == 1, L = P; otherwise d = P - L, then L = L + beta * d.
+ *   gate       then was = open, and: if open and L >= close_thr, hang = H; else if open and hang > 0, hang = hang - 1;
+ *              else if open, open = 0; if closed and L >= open_thr, open = 1 and hang = H.  The next block's code is
+ *              2 was + open: 0 closed, 1 ramp up, 2 ramp down, 3 open.  Global block 0 has code 0.
+ *   output     the sample at in-block index i under its block's code, r = 1 / S: code 0 (+0, +0); code 3 the input's
+ *              eight bytes; code 1 w = (float)(i + 1) * r and (zr * w, zi * w); code 2 w = (float)(S - 1 - i) * r and
+ *              (zr * w, zi * w).  out [n_streams][in_stride][2] float: every byte is written by every call, zero from n
+ *              on.  out may be chan itself (gating in place); any other overlap is undefined.  n = 0 is a valid call:
+ *              it writes out and the records and leaves the state where it is.
+ *   records    sdrg_squelch_record [n_streams], written by every call: level is L after the last block completed so far
+ *              (+0 before the first); level_db = 10.0f * log10f(level + 1e-20f) with glibc's log10f bit for bit (the
+ *              display stage's rule); open is the gate after that block; open_blocks is how many of the blocks this
+ *              call completed left the gate open.  *n_blocks = floor((g + n) / S) - floor(g / S), the blocks this call
+ *              completed, is set on the host before the call returns.
+ *   state      per stream the powers of the block in progress (S - 1 floats), L, open, hang and the current block's
+ *              code, in device memory (allocated at the first squelch call), in two halves a call reads and writes in
+ *              turn; per engine g, advanced by n once the call's launches have been issued: a failed call commits
+ *              nothing.  Calls shorter than a block accumulate; any number of calls may share one block.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_SQUELCH_MIN_BLOCK 16
+#define SDRG_SQUELCH_MAX_BLOCK 1024
+#define SDRG_SQUELCH_MAX_HANG 65535
+#define SDRG_SQUELCH_MAX_IN 1048576
+typedef struct sdrg_squelch_config {
+    double open_db;
+    double close_db;
+    double tau_blocks;
+    int32_t block;
+    int32_t hang_blocks;
+    int32_t max_in;
+} sdrg_squelch_config;
+
+typedef struct sdrg_squelch_record {
+    float level;
+    float level_db;
+    int32_t open;
+    int32_t open_blocks;
+} sdrg_squelch_record;
+
+/* Host-only, no device.  After the checks of set_squelch: the three design values above; any of the three pointers may
+ * be NULL. */
+int32_t sdrg_squelch_design(const sdrg_squelch_config *cfg, float *open_thr, float *close_thr, float *beta);
+/* Host-only: *tile = max(512, block), how many consecutive samples one workgroup takes: of the power kernel those of
+ * the global indices [k tile, (k + 1) tile), of the gate kernel those of the call's indices [k tile, (k + 1) tile) (for
+ * tests that want data across every seam). */
+int32_t sdrg_squelch_geometry(int32_t block, int32_t *tile);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the squelch.  A squelch call while it is off returns SDRG_E_INVALID and
+ * writes nothing. */
+int32_t sdrg_engine_set_squelch(sdrg_engine *eng, const sdrg_squelch_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its three design values and g, the samples every stream has
+ * consumed since the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_squelch(const sdrg_engine *eng, sdrg_squelch_config *cfg, float *open_thr, float *close_thr,
+                                float *beta, uint64_t *samples_consumed);
+int32_t sdrg_engine_squelch_reset(sdrg_engine *eng);
+/* chan and out: n_streams rows of in_stride complex samples ([n_streams][in_stride][2] float), of which the first n of
+ * every row are this call's (0 <= n <= in_stride <= max_in); records [n_streams] or NULL; all in device memory.  The
+ * rows of a channelizer's out [B][n_channels][cap][2] are those of an engine of B n_channels streams (in_stride = cap).
+ * Stream rules and waiting as sdrg_engine_demod_device: runs on the main stream (the caller's after
+ * sdrg_engine_set_stream); complete after sdrg_engine_synchronize, or on a stream after sdrg_engine_wait_outputs. */
+int32_t sdrg_engine_squelch_device(sdrg_engine *eng, const void *chan, int32_t in_stride, int32_t n, void *out,
+                                   sdrg_squelch_record *records, int32_t *n_blocks);
+/* Host buffers of the same shapes, synchronous; all n_streams * in_stride samples of chan are copied. */
+int32_t sdrg_engine_squelch_host(sdrg_engine *eng, const void *chan, int32_t in_stride, int32_t n, void *out,
+                                 sdrg_squelch_record *records, int32_t *n_blocks);
+/* Tune, gate and listen: sdrg_engine_ddc_demod_host with the squelch between the DDC and the demodulator, in place on
+ * the channel the chain keeps on the device (in_stride = the DDC's cap, n = the DDC call's n_out).  Only the audio rows
+ * and, unless records is NULL, the records [n_streams] come back.  SDRG_E_INVALID under sdrg_engine_ddc_demod_host's
+ * conditions, or if the squelch is off or its max_in is smaller than the DDC's cap; a refused call commits nothing in
+ * any stage.  sdrg_engine_ddc_demod_host itself never gates, whether or not a squelch is set. */
+int32_t sdrg_engine_ddc_squelch_demod_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out,
+                                           sdrg_squelch_record *records);
+/* The same for sdrg_engine_ddc_demod_resample_host. */
+int32_t sdrg_engine_ddc_squelch_demod_resample_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out,
+                                                    int32_t *n_out, sdrg_squelch_record *records);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

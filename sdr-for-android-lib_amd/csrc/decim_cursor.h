@@ -1,7 +1,8 @@
 // decim_cursor.h — the host's side of a decimating stage's stream position (engine.cpp: DDC, demodulator, channelizer,
-// resampler; fir_tile.h has the device's side).  A stage decimates by D from the first sample after a restart: the
-// outputs sit on the global sample indices that are multiples of D (DecimCursor); the resampler's output m sits on
-// the input index floor(m M / L) with the filter phase (m M) mod L (ResampleCursor).  Host only: no HIP.
+// resampler, squelch; fir_tile.h has the device's side).  A stage decimates by D from the first sample after a restart:
+// the outputs sit on the global sample indices that are multiples of D (DecimCursor); the resampler's output m sits on
+// the input index floor(m M / L) with the filter phase (m M) mod L (ResampleCursor); the squelch's blocks start on the
+// multiples of S (BlockCursor).  Host only: no HIP.
 #pragma once
 
 #include <stddef.h>
@@ -64,6 +65,18 @@ struct ResampleCursor : StreamCursor {
     }
     // the most outputs any call of n samples has (d = 0): the row length of `out`
     static int cap(int n, int L, int M) { return (int)(((int64_t)n * L + M - 1) / M); }
+};
+
+// The squelch's position (squelch.hip): the stream is cut into blocks of S samples (a power of two) at the global
+// indices that are multiples of S.  A call of n samples takes the positions [offset, offset + n) counted from the
+// start of the block in progress, and completes the blocks that end at or before g + n.
+struct BlockCursor : StreamCursor {
+    // samples of the block in progress that earlier calls consumed: g mod S
+    int offset(int S) const { return (int)(g % (uint64_t)S); }
+    // blocks a call of n samples completes: floor((g + n) / S) - floor(g / S)
+    int blocks(int n, int S) const { return (int)((g + (uint64_t)n) / (uint64_t)S - g / (uint64_t)S); }
+    // the most blocks any call of n samples completes (offset S - 1): the rows of the block scratch
+    static int cap(int n, int S) { return (int)(((int64_t)n + S - 1) / S); }
 };
 
 // A device buffer of two halves of half_elems values each: a call reads what the previous one wrote into one half and

@@ -308,6 +308,29 @@ void demod_design(const sdrg_demod_config &c, float *kf, float *alpha, float *a,
     if (h) lowpass_design(c.audio_cutoff_hz / fc, c.audio_taps, h);
 }
 
+// The squelch stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *squelch_check(const sdrg_squelch_config &c) {
+    if (!std::isfinite(c.open_db) || !std::isfinite(c.close_db)) return "open_db and close_db must be finite";
+    if (c.close_db > c.open_db) return "close_db above open_db";
+    if (!(c.tau_blocks >= 0.0) || !std::isfinite(c.tau_blocks)) return "tau_blocks must be >= 0 and finite";
+    if (c.block < SDRG_SQUELCH_MIN_BLOCK || c.block > SDRG_SQUELCH_MAX_BLOCK || (c.block & (c.block - 1)) != 0)
+        return "block must be a power of two in [16, 1024]";
+    if (c.hang_blocks < 0 || c.hang_blocks > SDRG_SQUELCH_MAX_HANG) return "hang_blocks outside [0, 65535]";
+    if (c.max_in < 1 || c.max_in > SDRG_SQUELCH_MAX_IN) return "max_in outside [1, 2^20]";
+    float open_thr, close_thr;
+    squelch_design(c, &open_thr, &close_thr, nullptr);
+    if (!std::isfinite(open_thr) || !(open_thr > 0.0f)) return "10^(open_db / 10) is not a finite, positive float";
+    if (!std::isfinite(close_thr) || !(close_thr > 0.0f)) return "10^(close_db / 10) is not a finite, positive float";
+    return nullptr;
+}
+
+// The squelch stage's constants (sdrg.h), in double, each rounded to float once
+void squelch_design(const sdrg_squelch_config &c, float *open_thr, float *close_thr, float *beta) {
+    if (open_thr) *open_thr = (float)std::pow(10.0, c.open_db / 10.0);
+    if (close_thr) *close_thr = (float)std::pow(10.0, c.close_db / 10.0);
+    if (beta) *beta = c.tau_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.tau_blocks)) : 1.0f;
+}
+
 // The resampler stage's configuration rules (sdrg.h): nullptr, or what is wrong
 const char *resample_check(const sdrg_resample_config &c) {
     const int L = c.interp, M = c.decim, P = c.taps_per_phase;

@@ -143,7 +143,7 @@ void release(Buf *...b) {
 }
 
 // The streaming stages' records: the configuration and whether one is set, the stream position, what the configuration
-// designs, and the device buffers, all of which free_buffers() releases (sdrg_engine_destroy calls the four).
+// designs, and the device buffers, all of which free_buffers() releases (sdrg_engine_destroy calls the five).
 
 // DDC stage (sdrg_engine_set_ddc / ddc_device / ddc_host; ddc.hip)
 struct DdcStage {
@@ -201,6 +201,18 @@ struct ResampleStage {
     int cap() const { return ResampleCursor::cap(cfg.max_in, cfg.interp, cfg.decim); }
     size_t half(int B) const { return (size_t)B * (size_t)(cfg.taps_per_phase - 1) * (size_t)cfg.components; }
     void free_buffers() { release(&hist, &d_taps); }
+};
+
+// squelch stage (sdrg_engine_set_squelch / squelch_device / squelch_host / ddc_squelch_demod_host; squelch.hip)
+struct SquelchStage {
+    sdrg_squelch_config cfg{};
+    bool set = false;
+    BlockCursor cur;
+    float open_thr = 0.0f, close_thr = 0.0f, beta = 0.0f;  // squelch_design of cfg
+    PingPong<float> state;  // halves of [n_streams][S + SQ_STATE_HEAD]: L, open, hang, code, the block's powers so far
+    DeviceBuf<float> blk;   // [the most blocks a call completes][n_streams]: the blocks' powers, then their codes
+    size_t half(int B) const { return (size_t)B * (size_t)(cfg.block + SQ_STATE_HEAD); }
+    void free_buffers() { release(&state, &blk); }
 };
 
 }  // namespace
@@ -353,8 +365,8 @@ struct sdrg_engine {
     bool disp_set = false;
     DeviceBuf<unsigned char> disp_out;  // the host calls' rows
     int host_spec_n = 0;          // N of the spectra the last process_host call with SPECTRUM left in d_spec_stage
-    // The device calls of the stages below (display, integration, peaks, DDC, demodulator, channelizer, resampler) write
-    // their outputs on s_main after the last process call's end marker, which is all a stream other than s_main
+    // The device calls of the stages below (display, integration, peaks, DDC, demodulator, channelizer, resampler,
+    // squelch) write their outputs on s_main after the last process call's end marker, which is all a stream other than s_main
     // follows.  Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs on s_main for that stream
     // to wait on.
     hipEvent_t ev_outputs = nullptr;
@@ -375,13 +387,15 @@ struct sdrg_engine {
     sdrg_peaks_config peaks{};
     bool peaks_set = false;
     DeviceBuf<unsigned char> peaks_out;  // the host calls' tables: [n_streams][max_peaks] sdrg_peak, then the summaries
-    // the streaming stages (DdcStage ... ResampleStage above)
+    // the streaming stages (DdcStage ... SquelchStage above)
     DdcStage ddc;
     DemodStage demod;
     ChanStage chan;
     ResampleStage rs;
-    // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host and the two
-    // chains), as bytes: the caller's input, and the rows it gets back.  One pair serves them all, as spec_in does its
+    SquelchStage sq;
+    // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host,
+    // squelch_host and the four chains), as bytes: the caller's input, and the rows it gets back (with the squelch's
+    // records behind them).  One pair serves them all, as spec_in does its
     // four: each of them waits on s_main before it returns, so no two uses overlap, and a call that fails after its
     // copy was enqueued leaves that copy ordered on s_main before whatever the next call enqueues there.
     DeviceBuf<char> stream_in, stream_out;
@@ -517,7 +531,7 @@ int32_t ensure_nco_table(sdrg_engine *e) {
     return SDRG_OK;
 }
 
-// ---- the streaming stages: DDC, demodulator, channelizer, resampler -------------------------------------------------
+// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch ----------------------------------------
 //
 // A call of a stage goes through three steps.  x_resolve makes every refusal and touches nothing; what it finds goes
 // into the stage's XCall.  x_reserve does everything that can fail without a launch (the stage's device buffers, the
@@ -528,6 +542,28 @@ int32_t ensure_nco_table(sdrg_engine *e) {
 struct StageCall {
     int n = 0, n_out = 0, cap = 0;       // samples per stream in, outputs per row, the row length of `out`
     size_t in_bytes = 0, out_bytes = 0;  // a host call's input and output
+    // A second output, which only the squelch has (its records): where the launch writes it, nullptr if the caller
+    // wants none, and its size.
+    void *aux = nullptr;
+    size_t aux_bytes = 0;
+};
+
+// A host call's second output sits in stream_out behind the out_bytes of rows, 16-byte aligned: HostAux takes the
+// caller's host pointer out of the call (`c`, the stage's whose launch writes it) and says how much stream_out must
+// hold; stage() points the call at the staging once host_begin has made it; finish() copies back, then host_end.
+struct HostAux {
+    StageCall *c;
+    void *host;
+    size_t at;
+    HostAux(StageCall *call, size_t out_bytes) : c(call), host(call->aux), at((out_bytes + 15) & ~(size_t)15) {}
+    size_t staged_bytes(size_t out_bytes) const { return host ? at + c->aux_bytes : out_bytes; }
+    void stage(sdrg_engine *e) const {
+        if (host) c->aux = e->stream_out.p + at;
+    }
+    int32_t finish(sdrg_engine *e, void *out, size_t out_bytes) const {
+        if (host) HIP_TRY(hipMemcpyAsync(host, c->aux, c->aux_bytes, hipMemcpyDeviceToHost, e->s_main));
+        return host_end(e, out, out_bytes);
+    }
 };
 
 int32_t require_set(bool set, const char *stage) {
@@ -546,9 +582,15 @@ int32_t stage_call(sdrg_engine *e, const char *in_name, const void *in, void *ou
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     rc = reserve(e, c);
-    if (!rc && host) rc = host_begin(e, in, c.in_bytes, c.out_bytes);
-    if (!rc) rc = host ? launch(e, c, e->stream_in.p, e->stream_out.p) : launch(e, c, in, out);
-    if (!rc && host) rc = host_end(e, out, c.out_bytes);
+    if (!rc && host) {  // c.aux, a second output, is the resolve's: null for the four stages with one output
+        const HostAux aux(&c, c.out_bytes);
+        rc = host_begin(e, in, c.in_bytes, aux.staged_bytes(c.out_bytes));
+        if (!rc) aux.stage(e);
+        if (!rc) rc = launch(e, c, e->stream_in.p, e->stream_out.p);
+        if (!rc) rc = aux.finish(e, out, c.out_bytes);
+    } else if (!rc) {
+        rc = launch(e, c, in, out);
+    }
     if (rc) return rc;
     *n_out = c.n_out;
     return SDRG_OK;
@@ -1304,6 +1346,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     e->demod.free_buffers();
     e->chan.free_buffers();
     e->rs.free_buffers();
+    e->sq.free_buffers();
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
     for (hipEvent_t ev : e->ev_stats_end)
         if (ev) (void)hipEventDestroy(ev);
@@ -2586,18 +2629,140 @@ int32_t sdrg_engine_resample_host(sdrg_engine *e, const void *in, int32_t in_str
     return rs_stage(e, "in", in, out, n_out, true, in_stride, n);
 }
 
-// ---- the chains: DDC -> demodulator (-> resampler), host memory in and out ------------------------------------------
+// ---- squelch stage (squelch.hip) -----------------------------------------------------------------------------------
+
+int32_t sdrg_squelch_design(const sdrg_squelch_config *cfg, float *open_thr, float *close_thr, float *beta) {
+    if (!cfg) return fail(SDRG_E_INVALID, "null squelch config");
+    if (const char *bad = squelch_check(*cfg)) return fail(SDRG_E_INVALID, "squelch: %s", bad);
+    squelch_design(*cfg, open_thr, close_thr, beta);
+    return SDRG_OK;
+}
+
+int32_t sdrg_squelch_geometry(int32_t block, int32_t *tile) {
+    if (!tile) return fail(SDRG_E_INVALID, "null tile");
+    if (block < SDRG_SQUELCH_MIN_BLOCK || block > SDRG_SQUELCH_MAX_BLOCK || (block & (block - 1)) != 0)
+        return fail(SDRG_E_INVALID, "squelch: block must be a power of two in [16, 1024]");
+    *tile = squelch_tile(block);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_squelch(sdrg_engine *e, const sdrg_squelch_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    SquelchStage &s = e->sq;
+    if (cfg) {
+        if (const char *bad = squelch_check(*cfg)) return fail(SDRG_E_INVALID, "squelch: %s", bad);
+        s.cfg = *cfg;
+        squelch_design(*cfg, &s.open_thr, &s.close_thr, &s.beta);
+    }
+    s.set = cfg != nullptr;
+    s.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_squelch(const sdrg_engine *e, sdrg_squelch_config *cfg, float *open_thr, float *close_thr,
+                                float *beta, uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    const SquelchStage &s = e->sq;
+    if (!s.set) return fail(SDRG_E_INVALID, "no squelch configuration set");
+    if (cfg) *cfg = s.cfg;
+    if (open_thr) *open_thr = s.open_thr;
+    if (close_thr) *close_thr = s.close_thr;
+    if (beta) *beta = s.beta;
+    if (samples_consumed) *samples_consumed = s.cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_squelch_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->sq.cur.restart();
+    return SDRG_OK;
+}
+
+struct SqCall : StageCall {
+    int in_stride;  // complex samples between the rows of chan and of out
+};
+
+// n_out is the blocks the call completes (*n_blocks); aux, the records
+static int32_t sq_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_squelch_record *records, SqCall *c) {
+    const SquelchStage &s = e->sq;
+    if (int32_t rc = require_set(s.set, "squelch")) return rc;
+    if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "squelch: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
+    if (in_stride < std::max(n, 1) || in_stride > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "squelch: in_stride %d outside [max(n, 1) = %d, max_in = %d]", in_stride,
+                    std::max(n, 1), s.cfg.max_in);
+    c->n = n;
+    c->in_stride = in_stride;
+    c->cap = in_stride;
+    c->n_out = s.cur.blocks(n, s.cfg.block);
+    c->in_bytes = c->out_bytes = (size_t)e->n_streams * (size_t)in_stride * 2 * sizeof(float);
+    c->aux = records;
+    c->aux_bytes = (size_t)e->n_streams * sizeof(sdrg_squelch_record);
+    return SDRG_OK;
+}
+
+static int32_t sq_reserve(sdrg_engine *e, const SqCall &) {
+    SquelchStage &s = e->sq;
+    const int32_t rc = ensure_device(&s.state, s.half(e->n_streams));
+    const size_t blocks = (size_t)BlockCursor::cap(s.cfg.max_in, s.cfg.block);
+    return rc ? rc : ensure_device(&s.blk, (size_t)e->n_streams * blocks);
+}
+
+// one squelch call on the main stream: chan and out (rows of in_stride complex samples; out may be chan) and c.aux, the
+// records or null, in device memory
+static int32_t sq_launch(sdrg_engine *e, const SqCall &c, const void *chan, void *out) {
+    SquelchStage &s = e->sq;
+    const size_t half = s.half(e->n_streams);
+    SquelchParams p{};
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.block = s.cfg.block;
+    p.hang = s.cfg.hang_blocks;
+    p.off = s.cur.offset(s.cfg.block);
+    p.n_blocks = c.n_out;
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.beta = s.beta;
+    p.open_thr = s.open_thr;
+    p.close_thr = s.close_thr;
+    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    p.state_new = s.state.next(s.cur, half);
+    p.blk = s.blk.p;
+    p.records = static_cast<sdrg_squelch_record *>(c.aux);
+    HIP_TRY(launch_squelch(static_cast<const float *>(chan), e->n_streams, p, static_cast<float *>(out), e->s_main));
+    s.cur.advance(c.n);  // a call without samples wrote out and the records only: the state stays where it is
+    e->outputs_unmarked = true;
+    return SDRG_OK;
+}
+
+static constexpr auto sq_stage =
+    &stage_call<SqCall, sq_resolve, sq_reserve, sq_launch, int32_t, int32_t, sdrg_squelch_record *>;
+
+int32_t sdrg_engine_squelch_device(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
+                                   sdrg_squelch_record *records, int32_t *n_blocks) {
+    return sq_stage(e, "chan", chan, out, n_blocks, false, in_stride, n, records);
+}
+
+int32_t sdrg_engine_squelch_host(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
+                                 sdrg_squelch_record *records, int32_t *n_blocks) {
+    return sq_stage(e, "chan", chan, out, n_blocks, true, in_stride, n, records);
+}
+
+// ---- the chains: DDC (-> squelch) -> demodulator (-> resampler), host memory in and out -----------------------------
 
 // Every refusal comes first, in the order the header lists them; then every stage's reserve and the buffers between
 // the stages; then the copy in, the launches, the copy out and the wait.  No x_launch is reachable before every
 // x_reserve of the call has returned SDRG_OK, so a call that fails for want of memory has advanced no stage's cursor:
 // "commits nothing in any stage" (include/sdrg.h) holds for SDRG_E_NOMEM as for the refusals.
-static int32_t chain_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out, bool resample) {
+// With `squelch`, the squelch stage gates the channel in place between the DDC and the demodulator, and its records
+// (unless null) come back with the audio, staged behind it in stream_out.
+static int32_t chain_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out, bool resample,
+                          bool squelch = false, sdrg_squelch_record *records = nullptr) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
     int32_t rc = require_set(e->demod.set, "demod");
     if (!rc && resample) rc = require_set(e->rs.set, "resample");
+    if (!rc && squelch) rc = require_set(e->sq.set, "squelch");
     DdcCall d;
+    SqCall q;
     DemodCall a;
     RsCall r;
     if (!rc) rc = ddc_resolve(e, fmt, &d);
@@ -2605,6 +2770,8 @@ static int32_t chain_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out
     // the checks between the stages come before the later stages' own: after them those cannot refuse their n
     if (e->demod.cfg.max_in < d.cap)
         return fail(SDRG_E_INVALID, "demod max_in %d smaller than the ddc's row length %d", e->demod.cfg.max_in, d.cap);
+    if (squelch && e->sq.cfg.max_in < d.cap)
+        return fail(SDRG_E_INVALID, "squelch max_in %d smaller than the ddc's row length %d", e->sq.cfg.max_in, d.cap);
     if (resample) {
         if (e->demod.cfg.out_format != SDRG_DEMOD_OUT_F32)
             return fail(SDRG_E_INVALID, "the resampler reads float audio: demod out_format must be SDRG_DEMOD_OUT_F32");
@@ -2617,20 +2784,25 @@ static int32_t chain_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out
     rc = demod_resolve(e, d.n_out, &a);
     a.in_stride = d.cap;  // the channel's rows are the DDC's
     if (!rc && resample) rc = rs_resolve(e, a.cap, a.n_out, &r);
+    if (!rc && squelch) rc = sq_resolve(e, d.cap, d.n_out, records, &q);
     if (rc) return rc;
     const StageCall &last = resample ? static_cast<const StageCall &>(r) : a;
+    const HostAux aux(&q, last.out_bytes);  // q.aux is null without a squelch: then nothing is staged or copied
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     rc = ddc_reserve(e, d);
+    if (!rc && squelch) rc = sq_reserve(e, q);
     if (!rc) rc = demod_reserve(e, a);
     if (!rc && resample) rc = rs_reserve(e, r);
     if (!rc) rc = ensure_device(&e->chain_chan, d.out_bytes / sizeof(float));
     if (!rc && resample) rc = ensure_device(&e->chain_audio, a.out_bytes / sizeof(float));
-    if (!rc) rc = host_begin(e, iq, d.in_bytes, last.out_bytes);
+    if (!rc) rc = host_begin(e, iq, d.in_bytes, aux.staged_bytes(last.out_bytes));
+    if (!rc) aux.stage(e);
     if (!rc) rc = ddc_launch(e, d, e->stream_in.p, e->chain_chan.p);
+    if (!rc && squelch) rc = sq_launch(e, q, e->chain_chan.p, e->chain_chan.p);
     if (!rc) rc = demod_launch(e, a, e->chain_chan.p, resample ? (void *)e->chain_audio.p : e->stream_out.p);
     if (!rc && resample) rc = rs_launch(e, r, e->chain_audio.p, e->stream_out.p);
-    if (!rc) rc = host_end(e, out, last.out_bytes);
+    if (!rc) rc = aux.finish(e, out, last.out_bytes);
     if (rc) return rc;
     *n_out = last.n_out;
     return SDRG_OK;
@@ -2642,6 +2814,16 @@ int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, 
 
 int32_t sdrg_engine_ddc_demod_resample_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
     return chain_host(e, iq, fmt, out, n_out, true);
+}
+
+int32_t sdrg_engine_ddc_squelch_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out,
+                                           sdrg_squelch_record *records) {
+    return chain_host(e, iq, fmt, out, n_out, false, true, records);
+}
+
+int32_t sdrg_engine_ddc_squelch_demod_resample_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out,
+                                                    int32_t *n_out, sdrg_squelch_record *records) {
+    return chain_host(e, iq, fmt, out, n_out, true, true, records);
 }
 
 int32_t sdrg_engine_set_callbacks(sdrg_engine *e, const sdrg_callbacks *cbs) {

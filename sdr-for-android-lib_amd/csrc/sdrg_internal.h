@@ -251,4 +251,25 @@ struct ResampleParams {
 constexpr int RESAMPLE_TILE = 256;  // outputs per workgroup, one per lane
 hipError_t launch_resample(const void *in, int n_streams, const ResampleParams &p, void *out, hipStream_t stream);
 
+// Squelch stage (squelch.hip): per stream the n complex samples at chan + stream * in_stride (float2) are the positions
+// [off, off + n) of a run of blocks of `block` samples, off = g mod block: n_blocks = (off + n) / block of them complete.
+// state_old / state_new [n_streams][block + SQ_STATE_HEAD] floats: {L, open, hang, the code of the block in progress}
+// (the last three as int bits), then that block's powers so far; fresh: state_old reads as zeros (and off is 0).  blk
+// [blocks][n_streams] floats is scratch: the completed blocks' mean powers, then, in their place, the code of the block
+// after each.  Writes out [n_streams][in_stride][2] whole (the gated samples, zeros from n on; out may be chan), and, if
+// n > 0, state_new; records [n_streams] unless nullptr.  n_streams, log2_block, inv_block and tile are the launcher's.
+struct SquelchParams {
+    int n, in_stride, block, hang, off, n_blocks, fresh;
+    float beta, open_thr, close_thr;
+    const float *state_old;
+    float *state_new;
+    float *blk;
+    sdrg_squelch_record *records;
+    int n_streams, log2_block, tile;
+    float inv_block;
+};
+constexpr int SQ_STATE_HEAD = 4;
+int squelch_tile(int block);  // consecutive samples per workgroup of the power and of the gate kernel
+hipError_t launch_squelch(const float *chan, int n_streams, const SquelchParams &p, float *out, hipStream_t stream);
+
 }  // namespace sdrg

@@ -138,6 +138,9 @@ EXPORTS = [
     "sdrg_resample_design", "sdrg_resample_tile_outputs", "sdrg_resample_ratio", "sdrg_engine_set_resample",
     "sdrg_engine_get_resample", "sdrg_engine_resample_reset", "sdrg_engine_resample_max_out",
     "sdrg_engine_resample_device", "sdrg_engine_resample_host", "sdrg_engine_ddc_demod_resample_host",
+    "sdrg_squelch_design", "sdrg_squelch_geometry", "sdrg_engine_set_squelch", "sdrg_engine_get_squelch",
+    "sdrg_engine_squelch_reset", "sdrg_engine_squelch_device", "sdrg_engine_squelch_host",
+    "sdrg_engine_ddc_squelch_demod_host", "sdrg_engine_ddc_squelch_demod_resample_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -224,6 +227,17 @@ class ResampleConfig(ctypes.Structure):
     _fields_ = [("cutoff_rel", ctypes.c_double), ("interp", ctypes.c_int32), ("decim", ctypes.c_int32),
                 ("taps_per_phase", ctypes.c_int32), ("components", ctypes.c_int32), ("out_format", ctypes.c_int32),
                 ("max_in", ctypes.c_int32), ("gain", ctypes.c_float)]
+
+
+class SquelchConfig(ctypes.Structure):
+    """sdrg_squelch_config: the squelch stage's thresholds, smoothing, block length, hang time and row length
+    (include/sdrg.h)."""
+    _fields_ = [("open_db", ctypes.c_double), ("close_db", ctypes.c_double), ("tau_blocks", ctypes.c_double),
+                ("block", ctypes.c_int32), ("hang_blocks", ctypes.c_int32), ("max_in", ctypes.c_int32)]
+
+
+# sdrg_squelch_record
+SquelchRecord = np.dtype([("level", "<f4"), ("level_db", "<f4"), ("open", "<i4"), ("open_blocks", "<i4")])
 
 
 def _filled(cls, what: str, fields: dict):
@@ -457,6 +471,17 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_resample_device": (_I32, [P, P, _I32, _I32, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_resample_host": (_I32, [P, P, _I32, _I32, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_ddc_demod_resample_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_squelch_design": (_I32, [ctypes.POINTER(SquelchConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
+                                       ctypes.POINTER(_F)]),
+        "sdrg_squelch_geometry": (_I32, [_I32, ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig)]),
+        "sdrg_engine_get_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
+                                           ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_squelch_reset": (_I32, [P]),
+        "sdrg_engine_squelch_device": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_squelch_host": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_ddc_squelch_demod_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32), P]),
+        "sdrg_engine_ddc_squelch_demod_resample_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32), P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -705,6 +730,24 @@ def resample_ratio(in_num: int, in_den: int, out_hz: int) -> tuple[int, int]:
     _check(load().sdrg_resample_ratio(int(in_num), int(in_den), int(out_hz), ctypes.byref(L), ctypes.byref(M)),
            "resample_ratio")
     return L.value, M.value
+
+
+def squelch_design(**fields) -> dict:
+    """The squelch stage's design for a configuration (host-side, no device): open_thr, close_thr and beta as
+    np.float32.  The fields are sdrg_squelch_config's (fields left out are 0)."""
+    c = _filled(SquelchConfig, "squelch", fields)
+    o, cl, beta = _F(), _F(), _F()
+    _check(load().sdrg_squelch_design(ctypes.byref(c), ctypes.byref(o), ctypes.byref(cl), ctypes.byref(beta)),
+           "squelch_design")
+    return {"open_thr": np.float32(o.value), "close_thr": np.float32(cl.value), "beta": np.float32(beta.value)}
+
+
+def squelch_geometry(block: int) -> int:
+    """tile: consecutive samples per workgroup of the squelch's power kernel (by global index) and of its gate kernel
+    (by the call's index) for a block length."""
+    t = _I32()
+    _check(load().sdrg_squelch_geometry(block, ctypes.byref(t)), "squelch_geometry")
+    return t.value
 
 
 def ssb_design(samp_count: int, sample_rate: int, sound_mode: int = 1) -> dict:
@@ -1209,6 +1252,60 @@ class Engine:
         device; returns the resampled audio, int16 or float32 [n_streams][n_out]."""
         return self._iq_call(load().sdrg_engine_ddc_demod_resample_host, "ddc_demod_resample_host", iq, fmt,
                              self._resample_out)
+
+    # ---- squelch stage ----------------------------------------------------------------------------
+    def set_squelch(self, **fields) -> None:
+        """sdrg_engine_set_squelch: open_db, close_db, tau_blocks, block, hang_blocks, max_in (fields left out are 0);
+        set_squelch(off=True) switches the stage off."""
+        self._set_stage(SquelchConfig, "squelch", fields)
+
+    def squelch_config(self) -> dict:
+        """The configuration in force, plus its design (open_thr, close_thr, beta as np.float32) and
+        samples_consumed."""
+        c, o, cl, beta, g = SquelchConfig(), _F(), _F(), _F(), ctypes.c_uint64()
+        _check(load().sdrg_engine_get_squelch(self._h, ctypes.byref(c), ctypes.byref(o), ctypes.byref(cl),
+                                              ctypes.byref(beta), ctypes.byref(g)), "get_squelch")
+        return dict(_as_dict(c), open_thr=np.float32(o.value), close_thr=np.float32(cl.value),
+                    beta=np.float32(beta.value), samples_consumed=g.value)
+
+    def squelch_reset(self) -> None:
+        _check(load().sdrg_engine_squelch_reset(self._h), "squelch_reset")
+
+    def squelch_device(self, chan_ptr: int, in_stride: int, n: int, out_ptr: int, records_ptr: int | None = None) -> int:
+        """Device path: chan [n_streams][in_stride] complex64 in (the first n of every row are the call's), the gated
+        rows of the same shape out (out_ptr may be chan_ptr) and, unless records_ptr is None, [n_streams] SquelchRecord;
+        asynchronous on the main stream.  Returns n_blocks, the blocks the call completed."""
+        return self._i32_call(load().sdrg_engine_squelch_device, "squelch_device", chan_ptr, in_stride, n, out_ptr,
+                              records_ptr)
+
+    def squelch_host(self, chan: np.ndarray, want_records: bool = True):
+        """Host path: chan is complex64 [n_streams][n], n <= max_in.  Returns (the gated complex64 [n_streams][n], the
+        records [n_streams] SquelchRecord or None, n_blocks)."""
+        chan = np.ascontiguousarray(chan, np.complex64).reshape(self.n_streams, -1)
+        n = chan.shape[1]
+        rows = chan if n else np.zeros((self.n_streams, 1), np.complex64)  # a call without samples still wants rows
+        out = np.empty_like(rows)
+        rec = np.empty(self.n_streams, SquelchRecord) if want_records else None
+        n_blocks = self._i32_call(load().sdrg_engine_squelch_host, "squelch_host", _ptr(rows), rows.shape[1], n,
+                                  _ptr(out), _ptr(rec))
+        return out[:, :n], rec, n_blocks
+
+    def _chain_with_records(self, fn, what: str, iq: np.ndarray, fmt: int, make_out):
+        iq, out, rec, n_out = self._iq(iq, fmt), make_out(), np.empty(self.n_streams, SquelchRecord), _I32()
+        _check(fn(self._h, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out), _ptr(rec)), what)
+        return out[..., :n_out.value], rec
+
+    def ddc_squelch_demod(self, iq: np.ndarray, fmt: int = CS8):
+        """Tune, gate and listen: ddc_demod() with the squelch in place on the channel between the DDC and the
+        demodulator; returns (the audio, int16 or float32 [n_streams][n_out], the records [n_streams] SquelchRecord)."""
+        return self._chain_with_records(load().sdrg_engine_ddc_squelch_demod_host, "ddc_squelch_demod_host", iq, fmt,
+                                        self._demod_out)
+
+    def ddc_squelch_demod_resample_host(self, iq: np.ndarray, fmt: int = CS8):
+        """ddc_demod_resample_host() with the squelch between the DDC and the demodulator; returns (the resampled
+        audio, the records)."""
+        return self._chain_with_records(load().sdrg_engine_ddc_squelch_demod_resample_host,
+                                        "ddc_squelch_demod_resample_host", iq, fmt, self._resample_out)
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
                        pcm_ptr: int | None, now_ms: int = 0) -> None:
