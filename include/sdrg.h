@@ -1077,6 +1077,120 @@ int32_t sdrg_engine_ddc_squelch_demod_host(sdrg_engine *eng, const void *iq, int
 int32_t sdrg_engine_ddc_squelch_demod_resample_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out,
                                                     int32_t *n_out, sdrg_squelch_record *records);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the AGC stage, one block-ramped gain per channel ahead of the
+ * demodulator.  Per stream, the n CF32 channel samples of a call (the DDC's out, the squelch's out, a row of the
+ * channelizer's, or any rows in device memory) are cut into blocks of S samples at the global indices that are multiples
+ * of S, as the squelch's are.  Each completed block's statistic (its mean power or its peak power) moves the stream's
+ * gain by an attack / hang / decay law; block b is multiplied by a ramp from the gain after block b - 2 to the gain after
+ * block b - 1.  The gain is therefore continuous across the seams of the blocks, and a decision never reaches back into
+ * the block that produced it: the stage adds no delay and out has one sample per input sample.  Over the whole life of a
+ * stream (the calls' samples concatenated, whatever their lengths) the result is that of one call.  All arithmetic is
+ * float, every product, sum, quotient and root rounded on its own (IEEE, correctly rounded), unless "double" is stated;
+ * denormals are kept.  A non-finite input sample makes that stream's outputs and records unspecified from then on.
+ *   config     target, the wanted RMS (detector MEAN) or peak (PEAK) amplitude of the output, finite and positive as a
+ *              float; max_gain_db and initial_gain_db finite; floor_db finite or -INFINITY; attack_blocks and
+ *              decay_blocks finite, >= 0; detector SDRG_AGC_DET_MEAN or SDRG_AGC_DET_PEAK; block S a power of two in
+ *              [SDRG_AGC_MIN_BLOCK, SDRG_AGC_MAX_BLOCK]; hang_blocks H in [0, SDRG_AGC_MAX_HANG]; max_in in [1, 2^20]:
+ *              every call's n <= in_stride <= max_in.  A rejected set_agc changes nothing; an accepted one, and
+ *              sdrg_engine_agc_reset, restart every stream: g = 0, G = G_prev = init_gain, hang 0, P_last = +0.
+ *   design     sdrg_agc_design, in double, each result rounded to float once: max_gain = 10^(max_gain_db / 20) and
+ *              init_gain = 10^(initial_gain_db / 20), refused unless both are finite and positive as floats and
+ *              init_gain <= max_gain; floor_thr = 10^(floor_db / 10), which may be +0 (floor_db = -INFINITY gives +0) and
+ *              must be finite; alpha_a = 1 - exp(-1 / attack_blocks) and alpha_d = 1 - exp(-1 / decay_blocks), each
+ *              1.0f exactly when its time is 0.  target is rounded to float once.
+ *   statistic  sample j of a block has p_j = zr zr + zi zi: two rounded products, one rounded sum.  MEAN: P is the
+ *              squelch's: the adjacent-pair tree over the S powers (q'[i] = q[2 i] + q[2 i + 1] until one value is left),
+ *              times 1 / S.  PEAK: P = max_j p_j.
+ *   step       for each completed block k, in order: P_last = P.  If P < floor_thr, nothing else changes (the hold: the
+ *              squelch's zeros give P = +0, so behind a closed gate the gain stays where it was).  Otherwise
+ *              a = sqrtf(P), want = fminf(target / a, max_gain) (a = 0 gives max_gain), d = want - G, and: if want < G,
+ *              G = want if alpha_a == 1, else G = G + alpha_a * d, hang = H, and the block counts as an attack; else if
+ *              hang > 0, hang = hang - 1; else G = want if alpha_d == 1, else G = G + alpha_d * d.  gain[k] is G after
+ *              the step (the hold included); gain[-1] = gain[-2] = init_gain.
+ *   output     sample i (in-block index) of global block b, with r = 1 / S, g0 = gain[b - 2], g1 = gain[b - 1]:
+ *              t = (float)(i + 1) * r, w = g0 + (g1 - g0) * t, and the output is (zr * w, zi * w).  Block 0 runs at
+ *              init_gain.  out [n_streams][in_stride][2] float: every byte is written by every call, zero from n on.  out
+ *              may be chan itself (in place); any other overlap is undefined.  n = 0 is a valid call: it writes out and
+ *              the records and leaves the state where it is.
+ *   records    sdrg_agc_record [n_streams], written by every call: gain is gain[k] of the last block completed so far
+ *              (init_gain before the first); gain_db = 20.0f * log10f(gain); level_db = 10.0f * log10f(P_last + 1e-20f),
+ *              P_last the statistic of that block (+0 before the first), both with glibc's log10f bit for bit (the
+ *              display stage's rule); attacks is how many of the blocks this call completed took the attack branch.
+ *              *n_blocks = floor((g + n) / S) - floor(g / S) is set on the host before the call returns.
+ *   state      per stream {G, G_prev, hang, P_last} and the powers of the block in progress (S - 1 floats), in device
+ *              memory (allocated at the first agc call), in two halves a call reads and writes in turn; per engine g,
+ *              advanced by n once the call's launches have been issued: a failed call commits nothing.  Calls shorter
+ *              than a block accumulate; any number of calls may share one block.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_AGC_MIN_BLOCK 16
+#define SDRG_AGC_MAX_BLOCK 1024
+#define SDRG_AGC_MAX_HANG 65535
+#define SDRG_AGC_MAX_IN 1048576
+#define SDRG_AGC_DET_MEAN 0
+#define SDRG_AGC_DET_PEAK 1
+typedef struct sdrg_agc_config {
+    double target;
+    double max_gain_db;
+    double initial_gain_db;
+    double floor_db;
+    double attack_blocks;
+    double decay_blocks;
+    int32_t detector;
+    int32_t block;
+    int32_t hang_blocks;
+    int32_t max_in;
+} sdrg_agc_config;
+
+typedef struct sdrg_agc_record {
+    float gain;
+    float gain_db;
+    float level_db;
+    int32_t attacks;
+} sdrg_agc_record;
+
+/* Host-only, no device.  After the checks of set_agc: the five design values above; any of the five pointers may be
+ * NULL. */
+int32_t sdrg_agc_design(const sdrg_agc_config *cfg, float *max_gain, float *init_gain, float *floor_thr, float *alpha_a,
+                        float *alpha_d);
+/* Host-only: *tile = max(512, block), how many consecutive samples one workgroup takes: of the power kernel those of
+ * the positions [k tile, (k + 1) tile) counted from the start of the block in progress, of the apply kernel those of the
+ * call's indices [k tile, (k + 1) tile) (for tests that want data across every seam). */
+int32_t sdrg_agc_geometry(int32_t block, int32_t *tile);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the AGC.  An agc call while it is off returns SDRG_E_INVALID and writes
+ * nothing. */
+int32_t sdrg_engine_set_agc(sdrg_engine *eng, const sdrg_agc_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its five design values and g, the samples every stream has
+ * consumed since the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_agc(const sdrg_engine *eng, sdrg_agc_config *cfg, float *max_gain, float *init_gain,
+                            float *floor_thr, float *alpha_a, float *alpha_d, uint64_t *samples_consumed);
+int32_t sdrg_engine_agc_reset(sdrg_engine *eng);
+/* chan and out: n_streams rows of in_stride complex samples ([n_streams][in_stride][2] float), of which the first n of
+ * every row are this call's (0 <= n <= in_stride <= max_in); records [n_streams] or NULL; all in device memory.  Stream
+ * rules and waiting as sdrg_engine_squelch_device. */
+int32_t sdrg_engine_agc_device(sdrg_engine *eng, const void *chan, int32_t in_stride, int32_t n, void *out,
+                               sdrg_agc_record *records, int32_t *n_blocks);
+/* Host buffers of the same shapes, synchronous; all n_streams * in_stride samples of chan are copied. */
+int32_t sdrg_engine_agc_host(sdrg_engine *eng, const void *chan, int32_t in_stride, int32_t n, void *out,
+                             sdrg_agc_record *records, int32_t *n_blocks);
+
+/* Tune and listen, with the steps the mask names: iq through DDC -> [squelch] -> [AGC] -> demodulator -> [resampler].
+ * The squelch and the AGC run in place on the channel the chain keeps on the device (in_stride = the DDC's cap, n = the
+ * DDC call's n_out); only the last stage's rows and, for each record pointer that is not NULL and whose stage is in the
+ * mask, that stage's records [n_streams] come back (a record pointer whose stage is not in the mask is ignored).  The
+ * four chain calls above are this call with the masks 0, SDRG_LISTEN_RESAMPLE, SDRG_LISTEN_SQUELCH and
+ * SDRG_LISTEN_SQUELCH | SDRG_LISTEN_RESAMPLE: they never run the AGC, whether or not one is set.  SDRG_E_INVALID, in
+ * this order: a null engine, iq, out or n_out; a mask with other bits; the demodulator off; the resampler, the squelch,
+ * the AGC off while in the mask; the DDC's own refusals; the demodulator's max_in, then the squelch's, then the AGC's
+ * smaller than the DDC's cap; with the resampler, a demodulator that does not write SDRG_DEMOD_OUT_F32, a resampler
+ * with components != 1 or a max_in smaller than the demodulator's cap.  A refused call commits nothing in any stage. */
+#define SDRG_LISTEN_SQUELCH 1
+#define SDRG_LISTEN_AGC 2
+#define SDRG_LISTEN_RESAMPLE 4
+int32_t sdrg_engine_listen_host(sdrg_engine *eng, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
+                                sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

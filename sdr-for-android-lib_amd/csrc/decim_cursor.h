@@ -67,7 +67,7 @@ struct ResampleCursor : StreamCursor {
     static int cap(int n, int L, int M) { return (int)(((int64_t)n * L + M - 1) / M); }
 };
 
-// The squelch's position (squelch.hip): the stream is cut into blocks of S samples (a power of two) at the global
+// The squelch's and the AGC's position (squelch.hip, agc.hip): the stream is cut into blocks of S samples (a power of two) at the global
 // indices that are multiples of S.  A call of n samples takes the positions [offset, offset + n) counted from the
 // start of the block in progress, and completes the blocks that end at or before g + n.
 struct BlockCursor : StreamCursor {

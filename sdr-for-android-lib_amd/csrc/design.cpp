@@ -331,6 +331,41 @@ void squelch_design(const sdrg_squelch_config &c, float *open_thr, float *close_
     if (beta) *beta = c.tau_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.tau_blocks)) : 1.0f;
 }
 
+// The AGC stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *agc_check(const sdrg_agc_config &c) {
+    if (!std::isfinite(c.target) || !std::isfinite((float)c.target) || !((float)c.target > 0.0f))
+        return "target is not a finite, positive float";
+    if (!std::isfinite(c.max_gain_db) || !std::isfinite(c.initial_gain_db))
+        return "max_gain_db and initial_gain_db must be finite";
+    if (std::isnan(c.floor_db) || c.floor_db == INFINITY) return "floor_db must be finite or -INFINITY";
+    if (!(c.attack_blocks >= 0.0) || !std::isfinite(c.attack_blocks)) return "attack_blocks must be >= 0 and finite";
+    if (!(c.decay_blocks >= 0.0) || !std::isfinite(c.decay_blocks)) return "decay_blocks must be >= 0 and finite";
+    if (c.detector != SDRG_AGC_DET_MEAN && c.detector != SDRG_AGC_DET_PEAK)
+        return "detector must be SDRG_AGC_DET_MEAN or SDRG_AGC_DET_PEAK";
+    if (c.block < SDRG_AGC_MIN_BLOCK || c.block > SDRG_AGC_MAX_BLOCK || (c.block & (c.block - 1)) != 0)
+        return "block must be a power of two in [16, 1024]";
+    if (c.hang_blocks < 0 || c.hang_blocks > SDRG_AGC_MAX_HANG) return "hang_blocks outside [0, 65535]";
+    if (c.max_in < 1 || c.max_in > SDRG_AGC_MAX_IN) return "max_in outside [1, 2^20]";
+    const AgcDesign d = agc_design(c);
+    if (!std::isfinite(d.max_gain) || !(d.max_gain > 0.0f)) return "10^(max_gain_db / 20) is not a finite, positive float";
+    if (!std::isfinite(d.init_gain) || !(d.init_gain > 0.0f))
+        return "10^(initial_gain_db / 20) is not a finite, positive float";
+    if (d.init_gain > d.max_gain) return "initial_gain_db above max_gain_db";
+    if (!std::isfinite(d.floor_thr)) return "10^(floor_db / 10) is not a finite float";
+    return nullptr;
+}
+
+// The AGC stage's constants (sdrg.h), in double, each rounded to float once
+AgcDesign agc_design(const sdrg_agc_config &c) {
+    AgcDesign d;
+    d.max_gain = (float)std::pow(10.0, c.max_gain_db / 20.0);
+    d.init_gain = (float)std::pow(10.0, c.initial_gain_db / 20.0);
+    d.floor_thr = (float)std::pow(10.0, c.floor_db / 10.0);  // pow(10, -inf) = +0
+    d.alpha_a = c.attack_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.attack_blocks)) : 1.0f;
+    d.alpha_d = c.decay_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.decay_blocks)) : 1.0f;
+    return d;
+}
+
 // The resampler stage's configuration rules (sdrg.h): nullptr, or what is wrong
 const char *resample_check(const sdrg_resample_config &c) {
     const int L = c.interp, M = c.decim, P = c.taps_per_phase;

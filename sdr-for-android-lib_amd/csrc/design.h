@@ -37,6 +37,12 @@ bool resample_ratio(uint64_t in_num, uint64_t in_den, uint64_t out_hz, int *inte
 // Squelch stage: the configuration rules (nullptr = valid) and open_thr, close_thr and beta (any pointer may be null)
 const char *squelch_check(const sdrg_squelch_config &cfg);
 void squelch_design(const sdrg_squelch_config &cfg, float *open_thr, float *close_thr, float *beta);
+// AGC stage: the configuration rules (nullptr = valid) and the five design values (any pointer may be null)
+struct AgcDesign {
+    float max_gain, init_gain, floor_thr, alpha_a, alpha_d;
+};
+const char *agc_check(const sdrg_agc_config &cfg);
+AgcDesign agc_design(const sdrg_agc_config &cfg);
 // AudioPulseDetector::makeLP2 / makeHP2 (audio_pulse_detector.cpp:29-55), Q = 0.7071: {b0, b1, b2, a1, a2}
 void design_pulse_sos(float fs, float fc, bool highpass, float c[5]);
 StatsGeometry stats_geometry(uint32_t sample_rate, uint32_t center_frequency, int n, int focus_khz);

@@ -143,7 +143,7 @@ void release(Buf *...b) {
 }
 
 // The streaming stages' records: the configuration and whether one is set, the stream position, what the configuration
-// designs, and the device buffers, all of which free_buffers() releases (sdrg_engine_destroy calls the five).
+// designs, and the device buffers, all of which free_buffers() releases (sdrg_engine_destroy calls the six).
 
 // DDC stage (sdrg_engine_set_ddc / ddc_device / ddc_host; ddc.hip)
 struct DdcStage {
@@ -212,6 +212,19 @@ struct SquelchStage {
     PingPong<float> state;  // halves of [n_streams][S + SQ_STATE_HEAD]: L, open, hang, code, the block's powers so far
     DeviceBuf<float> blk;   // [the most blocks a call completes][n_streams]: the blocks' powers, then their codes
     size_t half(int B) const { return (size_t)B * (size_t)(cfg.block + SQ_STATE_HEAD); }
+    void free_buffers() { release(&state, &blk); }
+};
+
+// AGC stage (sdrg_engine_set_agc / agc_device / agc_host / listen_host; agc.hip)
+struct AgcStage {
+    sdrg_agc_config cfg{};
+    bool set = false;
+    BlockCursor cur;
+    float target = 0.0f;    // cfg.target as a float
+    AgcDesign des{};        // agc_design of cfg
+    PingPong<float> state;  // halves of [n_streams][S + AGC_STATE_HEAD]: G, G_prev, hang, P_last, the block's powers so far
+    DeviceBuf<float> blk;   // [the most blocks a call completes][n_streams]: the blocks' statistics, then their gains
+    size_t half(int B) const { return (size_t)B * (size_t)(cfg.block + AGC_STATE_HEAD); }
     void free_buffers() { release(&state, &blk); }
 };
 
@@ -366,7 +379,7 @@ struct sdrg_engine {
     DeviceBuf<unsigned char> disp_out;  // the host calls' rows
     int host_spec_n = 0;          // N of the spectra the last process_host call with SPECTRUM left in d_spec_stage
     // The device calls of the stages below (display, integration, peaks, DDC, demodulator, channelizer, resampler,
-    // squelch) write their outputs on s_main after the last process call's end marker, which is all a stream other than s_main
+    // squelch, AGC) write their outputs on s_main after the last process call's end marker, which is all a stream other than s_main
     // follows.  Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs on s_main for that stream
     // to wait on.
     hipEvent_t ev_outputs = nullptr;
@@ -387,15 +400,16 @@ struct sdrg_engine {
     sdrg_peaks_config peaks{};
     bool peaks_set = false;
     DeviceBuf<unsigned char> peaks_out;  // the host calls' tables: [n_streams][max_peaks] sdrg_peak, then the summaries
-    // the streaming stages (DdcStage ... SquelchStage above)
+    // the streaming stages (DdcStage ... AgcStage above)
     DdcStage ddc;
     DemodStage demod;
     ChanStage chan;
     ResampleStage rs;
     SquelchStage sq;
+    AgcStage agc;
     // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host,
-    // squelch_host and the four chains), as bytes: the caller's input, and the rows it gets back (with the squelch's
-    // records behind them).  One pair serves them all, as spec_in does its
+    // squelch_host, agc_host and the chains), as bytes: the caller's input, and the rows it gets back (with the squelch's
+    // and the AGC's records behind them).  One pair serves them all, as spec_in does its
     // four: each of them waits on s_main before it returns, so no two uses overlap, and a call that fails after its
     // copy was enqueued leaves that copy ordered on s_main before whatever the next call enqueues there.
     DeviceBuf<char> stream_in, stream_out;
@@ -531,7 +545,7 @@ int32_t ensure_nco_table(sdrg_engine *e) {
     return SDRG_OK;
 }
 
-// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch ----------------------------------------
+// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC -----------------------------------
 //
 // A call of a stage goes through three steps.  x_resolve makes every refusal and touches nothing; what it finds goes
 // into the stage's XCall.  x_reserve does everything that can fail without a launch (the stage's device buffers, the
@@ -542,26 +556,35 @@ int32_t ensure_nco_table(sdrg_engine *e) {
 struct StageCall {
     int n = 0, n_out = 0, cap = 0;       // samples per stream in, outputs per row, the row length of `out`
     size_t in_bytes = 0, out_bytes = 0;  // a host call's input and output
-    // A second output, which only the squelch has (its records): where the launch writes it, nullptr if the caller
-    // wants none, and its size.
+    // A second output, which the squelch and the AGC have (their records): where the launch writes it, nullptr if the
+    // caller wants none, and its size.
     void *aux = nullptr;
     size_t aux_bytes = 0;
 };
 
-// A host call's second output sits in stream_out behind the out_bytes of rows, 16-byte aligned: HostAux takes the
-// caller's host pointer out of the call (`c`, the stage's whose launch writes it) and says how much stream_out must
-// hold; stage() points the call at the staging once host_begin has made it; finish() copies back, then host_end.
+// A host call's second outputs sit in stream_out behind the out_bytes of rows, each 16-byte aligned: HostAux takes the
+// callers' host pointers out of the calls (the stages' whose launches write them: one, or in a chain the squelch's and
+// the AGC's, either or both; a call without a second output takes no room) and says how much stream_out must hold;
+// stage() points the calls at the staging once host_begin has made it; finish() copies back, then host_end.
 struct HostAux {
-    StageCall *c;
-    void *host;
-    size_t at;
-    HostAux(StageCall *call, size_t out_bytes) : c(call), host(call->aux), at((out_bytes + 15) & ~(size_t)15) {}
-    size_t staged_bytes(size_t out_bytes) const { return host ? at + c->aux_bytes : out_bytes; }
+    StageCall *c[2];
+    void *host[2];
+    size_t at[2], end;
+    HostAux(size_t out_bytes, StageCall *first, StageCall *second = nullptr) : c{first, second}, end(out_bytes) {
+        for (int i = 0; i < 2; i++) {
+            host[i] = c[i] ? c[i]->aux : nullptr;
+            at[i] = (end + 15) & ~(size_t)15;
+            if (host[i]) end = at[i] + c[i]->aux_bytes;
+        }
+    }
+    size_t staged_bytes() const { return end; }
     void stage(sdrg_engine *e) const {
-        if (host) c->aux = e->stream_out.p + at;
+        for (int i = 0; i < 2; i++)
+            if (host[i]) c[i]->aux = e->stream_out.p + at[i];
     }
     int32_t finish(sdrg_engine *e, void *out, size_t out_bytes) const {
-        if (host) HIP_TRY(hipMemcpyAsync(host, c->aux, c->aux_bytes, hipMemcpyDeviceToHost, e->s_main));
+        for (int i = 0; i < 2; i++)
+            if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], c[i]->aux, c[i]->aux_bytes, hipMemcpyDeviceToHost, e->s_main));
         return host_end(e, out, out_bytes);
     }
 };
@@ -583,8 +606,8 @@ int32_t stage_call(sdrg_engine *e, const char *in_name, const void *in, void *ou
     HIP_TRY(dscope.error());
     rc = reserve(e, c);
     if (!rc && host) {  // c.aux, a second output, is the resolve's: null for the four stages with one output
-        const HostAux aux(&c, c.out_bytes);
-        rc = host_begin(e, in, c.in_bytes, aux.staged_bytes(c.out_bytes));
+        const HostAux aux(c.out_bytes, &c);
+        rc = host_begin(e, in, c.in_bytes, aux.staged_bytes());
         if (!rc) aux.stage(e);
         if (!rc) rc = launch(e, c, e->stream_in.p, e->stream_out.p);
         if (!rc) rc = aux.finish(e, out, c.out_bytes);
@@ -1347,6 +1370,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     e->chan.free_buffers();
     e->rs.free_buffers();
     e->sq.free_buffers();
+    e->agc.free_buffers();
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
     for (hipEvent_t ev : e->ev_stats_end)
         if (ev) (void)hipEventDestroy(ev);
@@ -2746,23 +2770,159 @@ int32_t sdrg_engine_squelch_host(sdrg_engine *e, const void *chan, int32_t in_st
     return sq_stage(e, "chan", chan, out, n_blocks, true, in_stride, n, records);
 }
 
-// ---- the chains: DDC (-> squelch) -> demodulator (-> resampler), host memory in and out -----------------------------
+// ---- AGC stage (agc.hip) ---------------------------------------------------------------------------------------------
 
+static void agc_design_out(const AgcDesign &d, float *max_gain, float *init_gain, float *floor_thr, float *alpha_a,
+                           float *alpha_d) {
+    if (max_gain) *max_gain = d.max_gain;
+    if (init_gain) *init_gain = d.init_gain;
+    if (floor_thr) *floor_thr = d.floor_thr;
+    if (alpha_a) *alpha_a = d.alpha_a;
+    if (alpha_d) *alpha_d = d.alpha_d;
+}
+
+int32_t sdrg_agc_design(const sdrg_agc_config *cfg, float *max_gain, float *init_gain, float *floor_thr, float *alpha_a,
+                        float *alpha_d) {
+    if (!cfg) return fail(SDRG_E_INVALID, "null agc config");
+    if (const char *bad = agc_check(*cfg)) return fail(SDRG_E_INVALID, "agc: %s", bad);
+    agc_design_out(agc_design(*cfg), max_gain, init_gain, floor_thr, alpha_a, alpha_d);
+    return SDRG_OK;
+}
+
+int32_t sdrg_agc_geometry(int32_t block, int32_t *tile) {
+    if (!tile) return fail(SDRG_E_INVALID, "null tile");
+    if (block < SDRG_AGC_MIN_BLOCK || block > SDRG_AGC_MAX_BLOCK || (block & (block - 1)) != 0)
+        return fail(SDRG_E_INVALID, "agc: block must be a power of two in [16, 1024]");
+    *tile = agc_tile(block);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_agc(sdrg_engine *e, const sdrg_agc_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    AgcStage &s = e->agc;
+    if (cfg) {
+        if (const char *bad = agc_check(*cfg)) return fail(SDRG_E_INVALID, "agc: %s", bad);
+        s.cfg = *cfg;
+        s.target = (float)cfg->target;
+        s.des = agc_design(*cfg);
+    }
+    s.set = cfg != nullptr;
+    s.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_agc(const sdrg_engine *e, sdrg_agc_config *cfg, float *max_gain, float *init_gain,
+                            float *floor_thr, float *alpha_a, float *alpha_d, uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    const AgcStage &s = e->agc;
+    if (!s.set) return fail(SDRG_E_INVALID, "no agc configuration set");
+    if (cfg) *cfg = s.cfg;
+    agc_design_out(s.des, max_gain, init_gain, floor_thr, alpha_a, alpha_d);
+    if (samples_consumed) *samples_consumed = s.cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_agc_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->agc.cur.restart();
+    return SDRG_OK;
+}
+
+struct AgcCall : StageCall {
+    int in_stride;  // complex samples between the rows of chan and of out
+};
+
+// n_out is the blocks the call completes (*n_blocks); aux, the records
+static int32_t agc_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_agc_record *records, AgcCall *c) {
+    const AgcStage &s = e->agc;
+    if (int32_t rc = require_set(s.set, "agc")) return rc;
+    if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "agc: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
+    if (in_stride < std::max(n, 1) || in_stride > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "agc: in_stride %d outside [max(n, 1) = %d, max_in = %d]", in_stride, std::max(n, 1),
+                    s.cfg.max_in);
+    c->n = n;
+    c->in_stride = in_stride;
+    c->cap = in_stride;
+    c->n_out = s.cur.blocks(n, s.cfg.block);
+    c->in_bytes = c->out_bytes = (size_t)e->n_streams * (size_t)in_stride * 2 * sizeof(float);
+    c->aux = records;
+    c->aux_bytes = (size_t)e->n_streams * sizeof(sdrg_agc_record);
+    return SDRG_OK;
+}
+
+static int32_t agc_reserve(sdrg_engine *e, const AgcCall &) {
+    AgcStage &s = e->agc;
+    const int32_t rc = ensure_device(&s.state, s.half(e->n_streams));
+    const size_t blocks = (size_t)BlockCursor::cap(s.cfg.max_in, s.cfg.block);
+    return rc ? rc : ensure_device(&s.blk, (size_t)e->n_streams * blocks);
+}
+
+// one agc call on the main stream: chan and out (rows of in_stride complex samples; out may be chan) and c.aux, the
+// records or null, in device memory
+static int32_t agc_launch(sdrg_engine *e, const AgcCall &c, const void *chan, void *out) {
+    AgcStage &s = e->agc;
+    const size_t half = s.half(e->n_streams);
+    AgcParams p{};
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.block = s.cfg.block;
+    p.hang = s.cfg.hang_blocks;
+    p.off = s.cur.offset(s.cfg.block);
+    p.n_blocks = c.n_out;
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.detector = s.cfg.detector;
+    p.target = s.target;
+    p.max_gain = s.des.max_gain;
+    p.init_gain = s.des.init_gain;
+    p.floor_thr = s.des.floor_thr;
+    p.alpha_a = s.des.alpha_a;
+    p.alpha_d = s.des.alpha_d;
+    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    p.state_new = s.state.next(s.cur, half);
+    p.blk = s.blk.p;
+    p.records = static_cast<sdrg_agc_record *>(c.aux);
+    HIP_TRY(launch_agc(static_cast<const float *>(chan), e->n_streams, p, static_cast<float *>(out), e->s_main));
+    s.cur.advance(c.n);  // a call without samples wrote out and the records only: the state stays where it is
+    e->outputs_unmarked = true;
+    return SDRG_OK;
+}
+
+static constexpr auto agc_stage =
+    &stage_call<AgcCall, agc_resolve, agc_reserve, agc_launch, int32_t, int32_t, sdrg_agc_record *>;
+
+int32_t sdrg_engine_agc_device(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
+                               sdrg_agc_record *records, int32_t *n_blocks) {
+    return agc_stage(e, "chan", chan, out, n_blocks, false, in_stride, n, records);
+}
+
+int32_t sdrg_engine_agc_host(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
+                             sdrg_agc_record *records, int32_t *n_blocks) {
+    return agc_stage(e, "chan", chan, out, n_blocks, true, in_stride, n, records);
+}
+
+// ---- the chains: DDC (-> squelch) (-> AGC) -> demodulator (-> resampler), host memory in and out --------------------
+
+// sdrg_engine_listen_host, and the four chain calls that are its masks without the AGC.
 // Every refusal comes first, in the order the header lists them; then every stage's reserve and the buffers between
 // the stages; then the copy in, the launches, the copy out and the wait.  No x_launch is reachable before every
 // x_reserve of the call has returned SDRG_OK, so a call that fails for want of memory has advanced no stage's cursor:
 // "commits nothing in any stage" (include/sdrg.h) holds for SDRG_E_NOMEM as for the refusals.
-// With `squelch`, the squelch stage gates the channel in place between the DDC and the demodulator, and its records
+// The squelch, then the AGC, work in place on the channel between the DDC and the demodulator, and their records
 // (unless null) come back with the audio, staged behind it in stream_out.
-static int32_t chain_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out, bool resample,
-                          bool squelch = false, sdrg_squelch_record *records = nullptr) {
+static int32_t chain_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
+                          sdrg_squelch_record *sq_records = nullptr, sdrg_agc_record *agc_records = nullptr) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    if (steps & ~(SDRG_LISTEN_SQUELCH | SDRG_LISTEN_AGC | SDRG_LISTEN_RESAMPLE))
+        return fail(SDRG_E_INVALID, "listen: unknown bits in steps 0x%x", (unsigned)steps);
+    const bool squelch = steps & SDRG_LISTEN_SQUELCH, agc = steps & SDRG_LISTEN_AGC, resample = steps & SDRG_LISTEN_RESAMPLE;
     int32_t rc = require_set(e->demod.set, "demod");
     if (!rc && resample) rc = require_set(e->rs.set, "resample");
     if (!rc && squelch) rc = require_set(e->sq.set, "squelch");
+    if (!rc && agc) rc = require_set(e->agc.set, "agc");
     DdcCall d;
     SqCall q;
+    AgcCall g;
     DemodCall a;
     RsCall r;
     if (!rc) rc = ddc_resolve(e, fmt, &d);
@@ -2772,6 +2932,8 @@ static int32_t chain_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out
         return fail(SDRG_E_INVALID, "demod max_in %d smaller than the ddc's row length %d", e->demod.cfg.max_in, d.cap);
     if (squelch && e->sq.cfg.max_in < d.cap)
         return fail(SDRG_E_INVALID, "squelch max_in %d smaller than the ddc's row length %d", e->sq.cfg.max_in, d.cap);
+    if (agc && e->agc.cfg.max_in < d.cap)
+        return fail(SDRG_E_INVALID, "agc max_in %d smaller than the ddc's row length %d", e->agc.cfg.max_in, d.cap);
     if (resample) {
         if (e->demod.cfg.out_format != SDRG_DEMOD_OUT_F32)
             return fail(SDRG_E_INVALID, "the resampler reads float audio: demod out_format must be SDRG_DEMOD_OUT_F32");
@@ -2784,22 +2946,26 @@ static int32_t chain_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out
     rc = demod_resolve(e, d.n_out, &a);
     a.in_stride = d.cap;  // the channel's rows are the DDC's
     if (!rc && resample) rc = rs_resolve(e, a.cap, a.n_out, &r);
-    if (!rc && squelch) rc = sq_resolve(e, d.cap, d.n_out, records, &q);
+    if (!rc && squelch) rc = sq_resolve(e, d.cap, d.n_out, sq_records, &q);
+    if (!rc && agc) rc = agc_resolve(e, d.cap, d.n_out, agc_records, &g);
     if (rc) return rc;
     const StageCall &last = resample ? static_cast<const StageCall &>(r) : a;
-    const HostAux aux(&q, last.out_bytes);  // q.aux is null without a squelch: then nothing is staged or copied
+    // a stage that is not in the mask was not resolved: its aux is null, and nothing is staged or copied for it
+    const HostAux aux(last.out_bytes, &q, &g);
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     rc = ddc_reserve(e, d);
     if (!rc && squelch) rc = sq_reserve(e, q);
+    if (!rc && agc) rc = agc_reserve(e, g);
     if (!rc) rc = demod_reserve(e, a);
     if (!rc && resample) rc = rs_reserve(e, r);
     if (!rc) rc = ensure_device(&e->chain_chan, d.out_bytes / sizeof(float));
     if (!rc && resample) rc = ensure_device(&e->chain_audio, a.out_bytes / sizeof(float));
-    if (!rc) rc = host_begin(e, iq, d.in_bytes, aux.staged_bytes(last.out_bytes));
+    if (!rc) rc = host_begin(e, iq, d.in_bytes, aux.staged_bytes());
     if (!rc) aux.stage(e);
     if (!rc) rc = ddc_launch(e, d, e->stream_in.p, e->chain_chan.p);
     if (!rc && squelch) rc = sq_launch(e, q, e->chain_chan.p, e->chain_chan.p);
+    if (!rc && agc) rc = agc_launch(e, g, e->chain_chan.p, e->chain_chan.p);
     if (!rc) rc = demod_launch(e, a, e->chain_chan.p, resample ? (void *)e->chain_audio.p : e->stream_out.p);
     if (!rc && resample) rc = rs_launch(e, r, e->chain_audio.p, e->stream_out.p);
     if (!rc) rc = aux.finish(e, out, last.out_bytes);
@@ -2808,22 +2974,27 @@ static int32_t chain_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out
     return SDRG_OK;
 }
 
+int32_t sdrg_engine_listen_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
+                                sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records) {
+    return chain_host(e, steps, iq, fmt, out, n_out, squelch_records, agc_records);
+}
+
 int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    return chain_host(e, iq, fmt, out, n_out, false);
+    return chain_host(e, 0, iq, fmt, out, n_out);
 }
 
 int32_t sdrg_engine_ddc_demod_resample_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    return chain_host(e, iq, fmt, out, n_out, true);
+    return chain_host(e, SDRG_LISTEN_RESAMPLE, iq, fmt, out, n_out);
 }
 
 int32_t sdrg_engine_ddc_squelch_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out,
                                            sdrg_squelch_record *records) {
-    return chain_host(e, iq, fmt, out, n_out, false, true, records);
+    return chain_host(e, SDRG_LISTEN_SQUELCH, iq, fmt, out, n_out, records);
 }
 
 int32_t sdrg_engine_ddc_squelch_demod_resample_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out,
                                                     int32_t *n_out, sdrg_squelch_record *records) {
-    return chain_host(e, iq, fmt, out, n_out, true, true, records);
+    return chain_host(e, SDRG_LISTEN_SQUELCH | SDRG_LISTEN_RESAMPLE, iq, fmt, out, n_out, records);
 }
 
 int32_t sdrg_engine_set_callbacks(sdrg_engine *e, const sdrg_callbacks *cbs) {

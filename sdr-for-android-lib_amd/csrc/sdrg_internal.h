@@ -272,4 +272,25 @@ constexpr int SQ_STATE_HEAD = 4;
 int squelch_tile(int block);  // consecutive samples per workgroup of the power and of the gate kernel
 hipError_t launch_squelch(const float *chan, int n_streams, const SquelchParams &p, float *out, hipStream_t stream);
 
+// AGC stage (agc.hip): the squelch's positions and blocks (n, in_stride, block, off, n_blocks, fresh as above).
+// state_old / state_new [n_streams][block + AGC_STATE_HEAD] floats: {G, G_prev, hang (int bits), P_last}, then the powers
+// so far of the block in progress; fresh: state_old reads as {init_gain, init_gain, 0, +0} (and off is 0).  blk
+// [blocks][n_streams] floats is scratch: the completed blocks' statistics (detector: the mean or the peak power), then,
+// in their place, the gain after each.  Writes out [n_streams][in_stride][2] whole (block b of the stream under the ramp
+// from gain[b - 2] to gain[b - 1], zeros from n on; out may be chan), and, if n > 0, state_new; records [n_streams] unless
+// nullptr.  n_streams, log2_block, inv_block and tile are the launcher's.
+struct AgcParams {
+    int n, in_stride, block, hang, off, n_blocks, fresh, detector;
+    float target, max_gain, init_gain, floor_thr, alpha_a, alpha_d;
+    const float *state_old;
+    float *state_new;
+    float *blk;
+    sdrg_agc_record *records;
+    int n_streams, log2_block, tile;
+    float inv_block;
+};
+constexpr int AGC_STATE_HEAD = 4;
+int agc_tile(int block);  // consecutive samples per workgroup of the power and of the apply kernel
+hipError_t launch_agc(const float *chan, int n_streams, const AgcParams &p, float *out, hipStream_t stream);
+
 }  // namespace sdrg

@@ -19,39 +19,14 @@
 //           block (block 0 of the call: the state's; block k: blk[k - 1]), and the zero tail up to in_stride.
 // No workgroup reads what another writes in the same launch, and the gate kernel's lanes read the samples they write: out
 // may be chan.  Compiled with -ffp-contract=off: every product and sum is rounded on its own.
+#include "block_power.h"
 #include "glibc_logf.h"
 #include "sdrg_internal.h"
 
 namespace sdrg {
 namespace {
 
-constexpr int SQ_THREADS = 256;
-constexpr int SQ_PASS = 2 * SQ_THREADS;  // positions a workgroup takes at a time
-constexpr int SQ_WAVE = 64;
-constexpr int SQ_AHEAD = 8;  // blocks the step kernel loads ahead of the chain
-
-// the value of the lane at distance 1, 2 (quad permutes), 4 (mirror of 8) or 8 (mirror of 16): the mirrors serve as
-// xor once the lanes of every group of 4, or of 8, hold the same value
-template <int CTRL>
-__device__ __forceinline__ float sq_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-
-// the sum over the `width` lanes (a power of two in [8, 64]) around this one, as the adjacent-pair tree
-__device__ __forceinline__ float sq_butterfly(float v, int width) {
-    v = v + sq_dpp<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-    v = v + sq_dpp<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-    v = v + sq_dpp<0x141>(v);  // row_half_mirror
-    if (width >= 16) v = v + sq_dpp<0x140>(v);  // row_mirror
-    if (width >= 32) v = v + __shfl_xor(v, 16);
-    if (width >= 64) v = v + __shfl_xor(v, 32);
-    return v;
-}
-
-__device__ __forceinline__ float sq_power(float2 z) {
-    const float a = z.x * z.x, b = z.y * z.y;
-    return a + b;
-}
+// SQ_THREADS, SQ_PASS, SQ_WAVE, SQ_AHEAD, sq_power and sq_butterfly (the DPP and bpermute tree) are block_power.h's
 
 template <bool VEC>
 __global__ __launch_bounds__(SQ_THREADS) void squelch_power_kernel(const float2 *chan, SquelchParams p) {

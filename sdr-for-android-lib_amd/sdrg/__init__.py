@@ -141,6 +141,8 @@ EXPORTS = [
     "sdrg_squelch_design", "sdrg_squelch_geometry", "sdrg_engine_set_squelch", "sdrg_engine_get_squelch",
     "sdrg_engine_squelch_reset", "sdrg_engine_squelch_device", "sdrg_engine_squelch_host",
     "sdrg_engine_ddc_squelch_demod_host", "sdrg_engine_ddc_squelch_demod_resample_host",
+    "sdrg_agc_design", "sdrg_agc_geometry", "sdrg_engine_set_agc", "sdrg_engine_get_agc", "sdrg_engine_agc_reset",
+    "sdrg_engine_agc_device", "sdrg_engine_agc_host", "sdrg_engine_listen_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -238,6 +240,23 @@ class SquelchConfig(ctypes.Structure):
 
 # sdrg_squelch_record
 SquelchRecord = np.dtype([("level", "<f4"), ("level_db", "<f4"), ("open", "<i4"), ("open_blocks", "<i4")])
+
+
+class AgcConfig(ctypes.Structure):
+    """sdrg_agc_config: the AGC stage's target, gain limits, floor, attack and decay times, detector, block length,
+    hang time and row length (include/sdrg.h)."""
+    _fields_ = [("target", ctypes.c_double), ("max_gain_db", ctypes.c_double), ("initial_gain_db", ctypes.c_double),
+                ("floor_db", ctypes.c_double), ("attack_blocks", ctypes.c_double), ("decay_blocks", ctypes.c_double),
+                ("detector", ctypes.c_int32), ("block", ctypes.c_int32), ("hang_blocks", ctypes.c_int32),
+                ("max_in", ctypes.c_int32)]
+
+
+# sdrg_agc_record
+AGC_RECORD_DTYPE = np.dtype([("gain", "<f4"), ("gain_db", "<f4"), ("level_db", "<f4"), ("attacks", "<i4")])
+AGC_DET_MEAN, AGC_DET_PEAK = 0, 1
+AGC_DESIGN_FIELDS = ("max_gain", "init_gain", "floor_thr", "alpha_a", "alpha_d")
+# the steps of Engine.listen (SDRG_LISTEN_*)
+LISTEN_SQUELCH, LISTEN_AGC, LISTEN_RESAMPLE = 1, 2, 4
 
 
 def _filled(cls, what: str, fields: dict):
@@ -482,6 +501,15 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_squelch_host": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_ddc_squelch_demod_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32), P]),
         "sdrg_engine_ddc_squelch_demod_resample_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32), P]),
+        "sdrg_agc_design": (_I32, [ctypes.POINTER(AgcConfig)] + [ctypes.POINTER(_F)] * 5),
+        "sdrg_agc_geometry": (_I32, [_I32, ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_agc": (_I32, [P, ctypes.POINTER(AgcConfig)]),
+        "sdrg_engine_get_agc": (_I32, [P, ctypes.POINTER(AgcConfig)] + [ctypes.POINTER(_F)] * 5 +
+                                [ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_agc_reset": (_I32, [P]),
+        "sdrg_engine_agc_device": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_agc_host": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_listen_host": (_I32, [P, _I32, P, _I32, P, ctypes.POINTER(_I32), P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -747,6 +775,23 @@ def squelch_geometry(block: int) -> int:
     (by the call's index) for a block length."""
     t = _I32()
     _check(load().sdrg_squelch_geometry(block, ctypes.byref(t)), "squelch_geometry")
+    return t.value
+
+
+def agc_design(**fields) -> dict:
+    """The AGC stage's design for a configuration (host-side, no device): max_gain, init_gain, floor_thr, alpha_a and
+    alpha_d as np.float32.  The fields are sdrg_agc_config's (fields left out are 0)."""
+    c = _filled(AgcConfig, "agc", fields)
+    v = [_F() for _ in AGC_DESIGN_FIELDS]
+    _check(load().sdrg_agc_design(ctypes.byref(c), *[ctypes.byref(x) for x in v]), "agc_design")
+    return {k: np.float32(x.value) for k, x in zip(AGC_DESIGN_FIELDS, v)}
+
+
+def agc_geometry(block: int) -> int:
+    """tile: consecutive samples per workgroup of the AGC's power kernel (counted from the start of the block in
+    progress) and of its apply kernel (by the call's index) for a block length."""
+    t = _I32()
+    _check(load().sdrg_agc_geometry(block, ctypes.byref(t)), "agc_geometry")
     return t.value
 
 
@@ -1306,6 +1351,56 @@ class Engine:
         audio, the records)."""
         return self._chain_with_records(load().sdrg_engine_ddc_squelch_demod_resample_host,
                                         "ddc_squelch_demod_resample_host", iq, fmt, self._resample_out)
+
+    # ---- AGC stage --------------------------------------------------------------------------------
+    def set_agc(self, **fields) -> None:
+        """sdrg_engine_set_agc: the fields of sdrg_agc_config (fields left out are 0); set_agc(off=True) switches the
+        stage off."""
+        self._set_stage(AgcConfig, "agc", fields)
+
+    def agc_config(self) -> dict:
+        """The configuration in force, plus its design (max_gain, init_gain, floor_thr, alpha_a, alpha_d as np.float32)
+        and samples_consumed."""
+        c, g = AgcConfig(), ctypes.c_uint64()
+        v = [_F() for _ in AGC_DESIGN_FIELDS]
+        _check(load().sdrg_engine_get_agc(self._h, ctypes.byref(c), *[ctypes.byref(x) for x in v], ctypes.byref(g)),
+               "get_agc")
+        return dict(_as_dict(c), **{k: np.float32(x.value) for k, x in zip(AGC_DESIGN_FIELDS, v)},
+                    samples_consumed=g.value)
+
+    def agc_reset(self) -> None:
+        _check(load().sdrg_engine_agc_reset(self._h), "agc_reset")
+
+    def agc_device(self, chan_ptr: int, in_stride: int, n: int, out_ptr: int, records_ptr: int | None = None) -> int:
+        """Device path: chan [n_streams][in_stride] complex64 in (the first n of every row are the call's), the levelled
+        rows of the same shape out (out_ptr may be chan_ptr) and, unless records_ptr is None, [n_streams]
+        AGC_RECORD_DTYPE; asynchronous on the main stream.  Returns n_blocks, the blocks the call completed."""
+        return self._i32_call(load().sdrg_engine_agc_device, "agc_device", chan_ptr, in_stride, n, out_ptr, records_ptr)
+
+    def agc_host(self, chan: np.ndarray, want_records: bool = True):
+        """Host path: chan is complex64 [n_streams][n], n <= max_in.  Returns (the levelled complex64 [n_streams][n],
+        the records [n_streams] AGC_RECORD_DTYPE or None, n_blocks)."""
+        chan = np.ascontiguousarray(chan, np.complex64).reshape(self.n_streams, -1)
+        n = chan.shape[1]
+        rows = chan if n else np.zeros((self.n_streams, 1), np.complex64)  # a call without samples still wants rows
+        out = np.empty_like(rows)
+        rec = np.empty(self.n_streams, AGC_RECORD_DTYPE) if want_records else None
+        n_blocks = self._i32_call(load().sdrg_engine_agc_host, "agc_host", _ptr(rows), rows.shape[1], n, _ptr(out),
+                                  _ptr(rec))
+        return out[:, :n], rec, n_blocks
+
+    def listen(self, iq: np.ndarray, fmt: int = CS8, steps: int = 0):
+        """sdrg_engine_listen_host: iq [n_streams][samplesPerReading * 2] raw samples through DDC -> [squelch] -> [AGC]
+        -> demodulator -> [resampler], the steps in brackets by the mask (LISTEN_SQUELCH | LISTEN_AGC |
+        LISTEN_RESAMPLE).  Returns (the audio [n_streams][n_out], the squelch's records or None, the AGC's records or
+        None)."""
+        iq, n_out = self._iq(iq, fmt), _I32()
+        out = self._resample_out() if steps & LISTEN_RESAMPLE else self._demod_out()
+        sq_rec = np.empty(self.n_streams, SquelchRecord) if steps & LISTEN_SQUELCH else None
+        agc_rec = np.empty(self.n_streams, AGC_RECORD_DTYPE) if steps & LISTEN_AGC else None
+        _check(load().sdrg_engine_listen_host(self._h, steps, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out),
+                                              _ptr(sq_rec), _ptr(agc_rec)), "listen_host")
+        return out[..., :n_out.value], sq_rec, agc_rec
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
                        pcm_ptr: int | None, now_ms: int = 0) -> None:
