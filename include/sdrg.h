@@ -1191,6 +1191,101 @@ int32_t sdrg_engine_agc_host(sdrg_engine *eng, const void *chan, int32_t in_stri
 int32_t sdrg_engine_listen_host(sdrg_engine *eng, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
                                 sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the sideband stage.  Per stream, the n CF32 channel samples of a call
+ * (the DDC's out, the squelch's or the AGC's, or any [n_streams][max_in][2] float rows in device memory) become the
+ * audio of one sideband, or of both, at channel_rate / R: the real part of a T-tap complex band-pass over
+ * [low_hz, high_hz] above the channel's centre (upper) or below it (lower), decimated by R, gain, and int16 PCM or
+ * float.  CW is the upper sideband of a channel tuned 700 Hz below the signal with a narrow band around 700 Hz.  Over
+ * the whole life of a stream (the calls' samples concatenated, whatever their lengths) the result is that of one call;
+ * each call writes the outputs its samples complete.  All arithmetic is float, every product and sum rounded on its
+ * own, unless "double" is stated; denormals are kept.  A non-finite input sample makes that stream's output
+ * unspecified from then on (the history carries it).  fc = channel_rate_hz.
+ *   config     fc > 0, finite; low_hz and high_hz finite with 0 <= low_hz < high_hz <= fc / 2; mode
+ *              SDRG_SIDEBAND_UPPER, SDRG_SIDEBAND_LOWER or SDRG_SIDEBAND_BOTH; audio_decimation R in
+ *              [1, SDRG_SIDEBAND_MAX_DECIMATION]; taps T odd in [1, SDRG_SIDEBAND_MAX_TAPS]; out_format
+ *              SDRG_SIDEBAND_OUT_S16 or SDRG_SIDEBAND_OUT_F32; max_in in [1, 2^20]: the row length of the input in
+ *              complex samples, every call's n <= max_in; gain finite.  A rejected set_sideband leaves the previous
+ *              configuration and state in force; an accepted one, and sdrg_engine_sideband_reset, restart every
+ *              stream: g = 0 and the history +0.
+ *   design     sdrg_sideband_design, in double, each result then rounded to float once: p[k], k in [0, T), is the
+ *              formula of sdrg_ddc_design with f = (high_hz - low_hz) / (2 fc), normalised to sum 1 and not rounded;
+ *              fm = (low_hz + high_hz) / 2; theta_k = 2 pi fm (k - (T - 1) / 2) / fc;
+ *              cr[k] = (float) (p[k] cos theta_k), ci[k] = (float) (p[k] sin theta_k).  T = 1 gives cr = 1, ci = 0.
+ *              c = cr + j ci passes [low_hz, high_hz] and stops [-high_hz, -low_hz]; its conjugate does the reverse.
+ *   filter     sample i of the call has the global index g + i; z[j] = (zr[j], zi[j]) is the stream's sample at the
+ *              global index j, (+0, +0) for j < 0.  For every m with g <= m R < g + n: acc = (+0, +0), then for
+ *              k = 0 .. T - 1 in this order acc.x = acc.x + cr[k] * zr[m R - k] and acc.y = acc.y + ci[k] * zi[m R - k]
+ *              (a rounded multiply, then a rounded add, each).  Then u = acc.x - acc.y, the upper sideband
+ *              Re(c * z), and l = acc.x + acc.y, the lower, Re(conj(c) * z).  n_out = ceil((g + n) / R) -
+ *              ceil(g / R), the same for every stream, 0 when the call holds no multiple of R.  The group delay of
+ *              (T - 1) / 2 channel samples is not compensated.
+ *   output     o = u * gain (UPPER) or l * gain (LOWER); BOTH writes the pair (u * gain, l * gain) interleaved.
+ *              SDRG_SIDEBAND_OUT_F32 writes o; SDRG_SIDEBAND_OUT_S16 writes
+ *              (int16_t) rintf(fminf(fmaxf(o, -1.0f), 1.0f) * 32767.0f), ties to even.  out [n_streams][cap], at BOTH
+ *              [n_streams][cap][2], cap = ceil(max_in / R); every byte is written by every call, the entries from
+ *              n_out on are zero.  n = 0 is a valid call: no outputs, the state unchanged.  *n_out is set on the host
+ *              before the call returns.
+ *   state      per stream the last T - 1 samples as float pairs, in device memory (allocated at the first sideband
+ *              call), in two halves a call reads and writes in turn; per engine g, advanced by n once the call's launch
+ *              has been issued: a failed call commits nothing.  The first call after a restart reads no half.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_SIDEBAND_UPPER 0
+#define SDRG_SIDEBAND_LOWER 1
+#define SDRG_SIDEBAND_BOTH 2
+#define SDRG_SIDEBAND_OUT_S16 0
+#define SDRG_SIDEBAND_OUT_F32 1
+#define SDRG_SIDEBAND_MAX_TAPS 511
+#define SDRG_SIDEBAND_MAX_DECIMATION 64
+#define SDRG_SIDEBAND_MAX_IN 1048576
+typedef struct sdrg_sideband_config {
+    double channel_rate_hz;
+    double low_hz;
+    double high_hz;
+    int32_t mode;
+    int32_t audio_decimation;
+    int32_t taps;
+    int32_t out_format;
+    int32_t max_in;
+    float gain;
+} sdrg_sideband_config;
+
+/* Host-only, no device.  After the checks of set_sideband: cr[cfg->taps] and ci[cfg->taps] of the design above; either
+ * pointer may be NULL. */
+int32_t sdrg_sideband_design(const sdrg_sideband_config *cfg, float *cr, float *ci);
+/* Host-only: *tile, how many consecutive outputs one workgroup computes for (R, T) (an output index that is a multiple
+ * of it starts a new tile): for tests that want data across every seam. */
+int32_t sdrg_sideband_geometry(int32_t audio_decimation, int32_t taps, int32_t *tile);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the sideband stage.  A sideband call while it is off returns
+ * SDRG_E_INVALID and writes nothing. */
+int32_t sdrg_engine_set_sideband(sdrg_engine *eng, const sdrg_sideband_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its design (cr, ci: taps floats each) and g, the samples every
+ * stream has consumed since the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_sideband(const sdrg_engine *eng, sdrg_sideband_config *cfg, float *cr, float *ci,
+                                 uint64_t *samples_consumed);
+int32_t sdrg_engine_sideband_reset(sdrg_engine *eng);
+/* cap = ceil(max_in / R): the row length of `out`, in outputs (int16 or float by out_format, pairs of them at BOTH). */
+int32_t sdrg_engine_sideband_max_out(const sdrg_engine *eng, int32_t *cap);
+/* chan [n_streams][max_in][2] float, of which the first n complex samples of every row are this call's (0 <= n <=
+ * max_in), and out [n_streams][cap] ([n_streams][cap][2] at BOTH) in device memory.  Reads chan only.  Stream rules and
+ * waiting as sdrg_engine_demod_device: runs on the main stream (the caller's after sdrg_engine_set_stream); complete
+ * after sdrg_engine_synchronize, or on a stream after sdrg_engine_wait_outputs. */
+int32_t sdrg_engine_sideband_device(sdrg_engine *eng, const void *chan, int32_t n, void *out, int32_t *n_out);
+/* Host buffers of the same shapes, synchronous. */
+int32_t sdrg_engine_sideband_host(sdrg_engine *eng, const void *chan, int32_t n, void *out, int32_t *n_out);
+/* Tune and listen to a sideband: sdrg_engine_listen_host with the sideband stage in the demodulator's place, iq through
+ * DDC -> [squelch] -> [AGC] -> sideband -> [resampler], the same mask bits, records and buffers kept on the device;
+ * the demodulator takes no part, whether or not one is set.  SDRG_E_INVALID, in this order: a null engine, iq, out or
+ * n_out; a mask with other bits; the sideband stage off; the resampler, the squelch, the AGC off while in the mask; the
+ * DDC's own refusals; the sideband stage's max_in, then the squelch's, then the AGC's smaller than the DDC's cap; with
+ * the resampler, a sideband stage that does not write SDRG_SIDEBAND_OUT_F32, a resampler whose components are not 1 for
+ * UPPER and LOWER and 2 for BOTH (the interleaved pair is filtered per component by the same real taps), or one with a
+ * max_in smaller than the sideband stage's cap.  A refused call commits nothing in any stage. */
+int32_t sdrg_engine_listen_sideband_host(sdrg_engine *eng, int32_t steps, const void *iq, int32_t fmt, void *out,
+                                         int32_t *n_out, sdrg_squelch_record *squelch_records,
+                                         sdrg_agc_record *agc_records);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

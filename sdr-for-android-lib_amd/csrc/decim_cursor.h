@@ -1,5 +1,5 @@
 // decim_cursor.h — the host's side of a decimating stage's stream position (engine.cpp: DDC, demodulator, channelizer,
-// resampler, squelch; fir_tile.h has the device's side).  A stage decimates by D from the first sample after a restart:
+// resampler, squelch, AGC, sideband; fir_tile.h has the device's side).  A stage decimates by D from the first sample after a restart:
 // the outputs sit on the global sample indices that are multiples of D (DecimCursor); the resampler's output m sits on
 // the input index floor(m M / L) with the filter phase (m M) mod L (ResampleCursor); the squelch's blocks start on the
 // multiples of S (BlockCursor).  Host only: no HIP.

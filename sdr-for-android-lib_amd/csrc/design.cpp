@@ -243,8 +243,9 @@ void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h) {
 void lowpass_design(double f, int taps, float *h) { lowpass_design_scaled(f, taps, 1.0, h); }
 
 // scale = 1 multiplies exactly: lowpass_design's floats are what they were as v[k] / sum
-void lowpass_design_scaled(double f, int taps, double scale, float *h) {
-    std::vector<double> v((size_t)taps);  // the resampler's prototype has up to 8192 coefficients
+// the windowed sinc before its normalisation, in double: v[k], and their sum returned
+static double lowpass_window(double f, int taps, std::vector<double> &v) {
+    v.resize((size_t)taps);  // the resampler's prototype has up to 8192 coefficients
     double sum = 0.0;
     for (int k = 0; k < taps; k++) {
         const int c = k - (taps - 1) / 2;
@@ -253,6 +254,12 @@ void lowpass_design_scaled(double f, int taps, double scale, float *h) {
         v[k] = ideal * w;
         sum += v[k];
     }
+    return sum;
+}
+
+void lowpass_design_scaled(double f, int taps, double scale, float *h) {
+    std::vector<double> v;
+    const double sum = lowpass_window(f, taps, v);
     for (int k = 0; k < taps; k++) h[k] = (float)(scale * v[k] / sum);
 }
 
@@ -306,6 +313,39 @@ void demod_design(const sdrg_demod_config &c, float *kf, float *alpha, float *a,
     if (alpha) *alpha = (float)(1.0 - std::exp(-2.0 * M_PI * c.dc_cutoff_hz / fc));
     if (a) *a = c.deemphasis_us > 0.0 ? (float)(1.0 - std::exp(-1.0 / (fc * c.deemphasis_us * 1e-6))) : 0.0f;
     if (h) lowpass_design(c.audio_cutoff_hz / fc, c.audio_taps, h);
+}
+
+// The sideband stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *sideband_check(const sdrg_sideband_config &c) {
+    if (!(c.channel_rate_hz > 0.0) || !std::isfinite(c.channel_rate_hz)) return "channel_rate_hz must be > 0 and finite";
+    if (!std::isfinite(c.low_hz) || !std::isfinite(c.high_hz)) return "low_hz and high_hz must be finite";
+    if (!(c.low_hz >= 0.0 && c.low_hz < c.high_hz && c.high_hz <= c.channel_rate_hz / 2.0))
+        return "0 <= low_hz < high_hz <= channel_rate_hz / 2 does not hold";
+    if (c.mode != SDRG_SIDEBAND_UPPER && c.mode != SDRG_SIDEBAND_LOWER && c.mode != SDRG_SIDEBAND_BOTH)
+        return "mode must be SDRG_SIDEBAND_UPPER, SDRG_SIDEBAND_LOWER or SDRG_SIDEBAND_BOTH";
+    if (c.audio_decimation < 1 || c.audio_decimation > SDRG_SIDEBAND_MAX_DECIMATION)
+        return "audio_decimation outside [1, 64]";
+    if (c.taps < 1 || c.taps > SDRG_SIDEBAND_MAX_TAPS || (c.taps & 1) == 0) return "taps must be odd and in [1, 511]";
+    if (c.out_format != SDRG_SIDEBAND_OUT_S16 && c.out_format != SDRG_SIDEBAND_OUT_F32)
+        return "out_format must be SDRG_SIDEBAND_OUT_S16 or SDRG_SIDEBAND_OUT_F32";
+    if (c.max_in < 1 || c.max_in > SDRG_SIDEBAND_MAX_IN) return "max_in outside [1, 2^20]";
+    if (!std::isfinite(c.gain)) return "gain must be finite";
+    return nullptr;
+}
+
+// The sideband stage's band-pass (sdrg.h): the DDC's low-pass of half the band's width, not rounded, turned to the
+// band's middle fm; in double, each component rounded to float once
+void sideband_design(const sdrg_sideband_config &c, float *cr, float *ci) {
+    const double fc = c.channel_rate_hz, fm = (c.low_hz + c.high_hz) / 2.0;
+    const int T = c.taps;
+    std::vector<double> v;
+    const double sum = lowpass_window((c.high_hz - c.low_hz) / (2.0 * fc), T, v);
+    for (int k = 0; k < T; k++) {
+        const double p = v[k] / sum;
+        const double theta = 2.0 * M_PI * fm * (double)(k - (T - 1) / 2) / fc;
+        if (cr) cr[k] = (float)(p * std::cos(theta));
+        if (ci) ci[k] = (float)(p * std::sin(theta));
+    }
 }
 
 // The squelch stage's configuration rules (sdrg.h): nullptr, or what is wrong

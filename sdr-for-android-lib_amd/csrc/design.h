@@ -43,6 +43,10 @@ struct AgcDesign {
 };
 const char *agc_check(const sdrg_agc_config &cfg);
 AgcDesign agc_design(const sdrg_agc_config &cfg);
+// Sideband stage: the configuration rules (nullptr = valid) and the band-pass as cr and ci, taps floats each (either
+// pointer may be null)
+const char *sideband_check(const sdrg_sideband_config &cfg);
+void sideband_design(const sdrg_sideband_config &cfg, float *cr, float *ci);
 // AudioPulseDetector::makeLP2 / makeHP2 (audio_pulse_detector.cpp:29-55), Q = 0.7071: {b0, b1, b2, a1, a2}
 void design_pulse_sos(float fs, float fc, bool highpass, float c[5]);
 StatsGeometry stats_geometry(uint32_t sample_rate, uint32_t center_frequency, int n, int focus_khz);

@@ -143,7 +143,7 @@ void release(Buf *...b) {
 }
 
 // The streaming stages' records: the configuration and whether one is set, the stream position, what the configuration
-// designs, and the device buffers, all of which free_buffers() releases (sdrg_engine_destroy calls the six).
+// designs, and the device buffers, all of which free_buffers() releases (sdrg_engine_destroy calls the seven).
 
 // DDC stage (sdrg_engine_set_ddc / ddc_device / ddc_host; ddc.hip)
 struct DdcStage {
@@ -226,6 +226,20 @@ struct AgcStage {
     DeviceBuf<float> blk;   // [the most blocks a call completes][n_streams]: the blocks' statistics, then their gains
     size_t half(int B) const { return (size_t)B * (size_t)(cfg.block + AGC_STATE_HEAD); }
     void free_buffers() { release(&state, &blk); }
+};
+
+// sideband stage (sdrg_engine_set_sideband / sideband_device / sideband_host / listen_sideband_host; sideband.hip)
+struct SidebandStage {
+    sdrg_sideband_config cfg{};
+    bool set = false;
+    DecimCursor cur;
+    std::vector<float> cr, ci;  // sideband_design of cfg
+    PingPong<float> hist;       // halves of [n_streams][taps - 1][2]: the samples before the next call's
+    DeviceBuf<float> d_taps;    // [taps][2]: (cr, ci), written by set_sideband
+    int cap() const { return DecimCursor::cap(cfg.max_in, cfg.audio_decimation); }
+    int width() const { return cfg.mode == SDRG_SIDEBAND_BOTH ? 2 : 1; }  // values per output
+    size_t half(int B) const { return (size_t)B * (size_t)(cfg.taps - 1) * 2; }
+    void free_buffers() { release(&hist, &d_taps); }
 };
 
 }  // namespace
@@ -379,8 +393,8 @@ struct sdrg_engine {
     DeviceBuf<unsigned char> disp_out;  // the host calls' rows
     int host_spec_n = 0;          // N of the spectra the last process_host call with SPECTRUM left in d_spec_stage
     // The device calls of the stages below (display, integration, peaks, DDC, demodulator, channelizer, resampler,
-    // squelch, AGC) write their outputs on s_main after the last process call's end marker, which is all a stream other than s_main
-    // follows.  Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs on s_main for that stream
+    // squelch, AGC, sideband) write their outputs on s_main after the last process call's end marker, which is all a
+    // stream other than s_main follows.  Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs on s_main for that stream
     // to wait on.
     hipEvent_t ev_outputs = nullptr;
     bool outputs_unmarked = false;
@@ -407,6 +421,7 @@ struct sdrg_engine {
     ResampleStage rs;
     SquelchStage sq;
     AgcStage agc;
+    SidebandStage sb;
     // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host,
     // squelch_host, agc_host and the chains), as bytes: the caller's input, and the rows it gets back (with the squelch's
     // and the AGC's records behind them).  One pair serves them all, as spec_in does its
@@ -545,7 +560,7 @@ int32_t ensure_nco_table(sdrg_engine *e) {
     return SDRG_OK;
 }
 
-// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC -----------------------------------
+// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband -------------------------
 //
 // A call of a stage goes through three steps.  x_resolve makes every refusal and touches nothing; what it finds goes
 // into the stage's XCall.  x_reserve does everything that can fail without a launch (the stage's device buffers, the
@@ -1371,6 +1386,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     e->rs.free_buffers();
     e->sq.free_buffers();
     e->agc.free_buffers();
+    e->sb.free_buffers();
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
     for (hipEvent_t ev : e->ev_stats_end)
         if (ev) (void)hipEventDestroy(ev);
@@ -2900,23 +2916,166 @@ int32_t sdrg_engine_agc_host(sdrg_engine *e, const void *chan, int32_t in_stride
     return agc_stage(e, "chan", chan, out, n_blocks, true, in_stride, n, records);
 }
 
-// ---- the chains: DDC (-> squelch) (-> AGC) -> demodulator (-> resampler), host memory in and out --------------------
+// ---- sideband stage (sideband.hip) ---------------------------------------------------------------------------------
 
-// sdrg_engine_listen_host, and the four chain calls that are its masks without the AGC.
+int32_t sdrg_sideband_design(const sdrg_sideband_config *cfg, float *cr, float *ci) {
+    if (!cfg) return fail(SDRG_E_INVALID, "null sideband config");
+    if (const char *bad = sideband_check(*cfg)) return fail(SDRG_E_INVALID, "sideband: %s", bad);
+    sideband_design(*cfg, cr, ci);
+    return SDRG_OK;
+}
+
+int32_t sdrg_sideband_geometry(int32_t audio_decimation, int32_t taps, int32_t *tile) {
+    if (!tile) return fail(SDRG_E_INVALID, "null tile");
+    if (audio_decimation < 1 || audio_decimation > SDRG_SIDEBAND_MAX_DECIMATION || taps < 1 ||
+        taps > SDRG_SIDEBAND_MAX_TAPS || (taps & 1) == 0)
+        return fail(SDRG_E_INVALID, "sideband: audio_decimation outside [1, 64] or taps not odd in [1, 511]");
+    *tile = sideband_tile_outputs(audio_decimation, taps);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_sideband(sdrg_engine *e, const sdrg_sideband_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    SidebandStage &s = e->sb;
+    if (cfg) {
+        if (const char *bad = sideband_check(*cfg)) return fail(SDRG_E_INVALID, "sideband: %s", bad);
+        const size_t T = (size_t)cfg->taps;
+        std::vector<float> cr(T), ci(T), pairs(2 * T);  // the device's copy is the pairs (cr, ci)
+        sideband_design(*cfg, cr.data(), ci.data());
+        for (size_t k = 0; k < T; k++) pairs[2 * k] = cr[k], pairs[2 * k + 1] = ci[k];
+        DeviceScope dscope(e->device);
+        HIP_TRY(dscope.error());
+        const int32_t rc = upload_floats(&s.d_taps, pairs, "sideband");
+        if (rc) return rc;
+        s.cr.swap(cr);
+        s.ci.swap(ci);
+        s.cfg = *cfg;
+    }
+    s.set = cfg != nullptr;
+    s.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_sideband(const sdrg_engine *e, sdrg_sideband_config *cfg, float *cr, float *ci,
+                                 uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    const SidebandStage &s = e->sb;
+    if (!s.set) return fail(SDRG_E_INVALID, "no sideband configuration set");
+    if (cfg) *cfg = s.cfg;
+    if (cr) std::copy(s.cr.begin(), s.cr.end(), cr);
+    if (ci) std::copy(s.ci.begin(), s.ci.end(), ci);
+    if (samples_consumed) *samples_consumed = s.cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_sideband_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->sb.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_sideband_max_out(const sdrg_engine *e, int32_t *cap) {
+    if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
+    if (int32_t rc = require_set(e->sb.set, "sideband")) return rc;
+    *cap = e->sb.cap();
+    return SDRG_OK;
+}
+
+struct SbCall : StageCall {
+    int in_stride;  // complex samples between the rows of chan: max_in, or in a chain the DDC's cap
+};
+
+static int32_t sb_resolve(const sdrg_engine *e, int32_t n, SbCall *c) {
+    const SidebandStage &s = e->sb;
+    if (int32_t rc = require_set(s.set, "sideband")) return rc;
+    if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "sideband: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
+    c->n = n;
+    c->in_stride = s.cfg.max_in;
+    c->cap = s.cap();
+    c->n_out = s.cur.n_out(n, s.cfg.audio_decimation);
+    c->in_bytes = (size_t)e->n_streams * (size_t)c->in_stride * 2 * sizeof(float);
+    c->out_bytes = (size_t)e->n_streams * (size_t)c->cap * (size_t)s.width() *
+                   (s.cfg.out_format == SDRG_SIDEBAND_OUT_F32 ? sizeof(float) : sizeof(int16_t));
+    return SDRG_OK;
+}
+
+static int32_t sb_reserve(sdrg_engine *e, const SbCall &) { return ensure_device(&e->sb.hist, e->sb.half(e->n_streams)); }
+
+// one sideband call on the main stream: chan (rows of in_stride complex samples), out in device memory
+static int32_t sb_launch(sdrg_engine *e, const SbCall &c, const void *chan, void *out) {
+    SidebandStage &s = e->sb;
+    const size_t half = s.half(e->n_streams);
+    SidebandParams p{};
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.decim = s.cfg.audio_decimation;
+    p.taps = s.cfg.taps;
+    p.first = s.cur.first(s.cfg.audio_decimation);
+    p.n_out = c.n_out;
+    p.cap = c.cap;
+    p.mode = s.cfg.mode;
+    p.out_format = s.cfg.out_format;
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.gain = s.cfg.gain;
+    p.taps_dev = s.d_taps.p;
+    p.hist_old = s.hist.old(s.cur, half);  // nullptr after a restart: the kernel gets no old history
+    p.hist_new = s.hist.next(s.cur, half);
+    HIP_TRY(launch_sideband(static_cast<const float *>(chan), e->n_streams, p, out, e->s_main));
+    s.cur.advance(c.n);  // a call without samples wrote out only: the state stays where it is
+    e->outputs_unmarked = true;
+    return SDRG_OK;
+}
+
+static constexpr auto sb_stage = &stage_call<SbCall, sb_resolve, sb_reserve, sb_launch, int32_t>;
+
+int32_t sdrg_engine_sideband_device(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
+    return sb_stage(e, "chan", chan, out, n_out, false, n);
+}
+
+int32_t sdrg_engine_sideband_host(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
+    return sb_stage(e, "chan", chan, out, n_out, true, n);
+}
+
+// ---- the chains: DDC (-> squelch) (-> AGC) -> demodulator or sideband (-> resampler), host memory in and out --------
+
+// The stage that turns the channel into audio.  What a chain asks of it, whichever it is: whether it is set, its
+// max_in and cap, whether it writes floats, how many components an output has, and its three steps.
+enum class Detector { Demod, Sideband };
+
+struct DetectorView {
+    const char *name;      // for require_set and the messages
+    const char *f32_name;  // the out_format the resampler needs, as the header spells it
+    bool set, f32;
+    int max_in, cap, components;
+};
+
+static DetectorView detector_view(const sdrg_engine *e, Detector det) {
+    if (det == Detector::Sideband)
+        return {"sideband", "SDRG_SIDEBAND_OUT_F32", e->sb.set, e->sb.cfg.out_format == SDRG_SIDEBAND_OUT_F32,
+                e->sb.cfg.max_in, e->sb.set ? e->sb.cap() : 0, e->sb.width()};
+    return {"demod", "SDRG_DEMOD_OUT_F32", e->demod.set, e->demod.cfg.out_format == SDRG_DEMOD_OUT_F32,
+            e->demod.cfg.max_in, e->demod.set ? e->demod.cap() : 0, 1};
+}
+
+// sdrg_engine_listen_host, and the four chain calls that are its masks without the AGC; with the sideband stage as the
+// detector, sdrg_engine_listen_sideband_host.
 // Every refusal comes first, in the order the header lists them; then every stage's reserve and the buffers between
 // the stages; then the copy in, the launches, the copy out and the wait.  No x_launch is reachable before every
 // x_reserve of the call has returned SDRG_OK, so a call that fails for want of memory has advanced no stage's cursor:
 // "commits nothing in any stage" (include/sdrg.h) holds for SDRG_E_NOMEM as for the refusals.
 // The squelch, then the AGC, work in place on the channel between the DDC and the demodulator, and their records
 // (unless null) come back with the audio, staged behind it in stream_out.
-static int32_t chain_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
-                          sdrg_squelch_record *sq_records = nullptr, sdrg_agc_record *agc_records = nullptr) {
+static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const void *iq, int32_t fmt, void *out,
+                          int32_t *n_out, sdrg_squelch_record *sq_records = nullptr,
+                          sdrg_agc_record *agc_records = nullptr) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
     if (steps & ~(SDRG_LISTEN_SQUELCH | SDRG_LISTEN_AGC | SDRG_LISTEN_RESAMPLE))
         return fail(SDRG_E_INVALID, "listen: unknown bits in steps 0x%x", (unsigned)steps);
     const bool squelch = steps & SDRG_LISTEN_SQUELCH, agc = steps & SDRG_LISTEN_AGC, resample = steps & SDRG_LISTEN_RESAMPLE;
-    int32_t rc = require_set(e->demod.set, "demod");
+    const bool sideband = det == Detector::Sideband;
+    const DetectorView v = detector_view(e, det);
+    int32_t rc = require_set(v.set, v.name);
     if (!rc && resample) rc = require_set(e->rs.set, "resample");
     if (!rc && squelch) rc = require_set(e->sq.set, "squelch");
     if (!rc && agc) rc = require_set(e->agc.set, "agc");
@@ -2924,32 +3083,40 @@ static int32_t chain_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t
     SqCall q;
     AgcCall g;
     DemodCall a;
+    SbCall s;
     RsCall r;
     if (!rc) rc = ddc_resolve(e, fmt, &d);
     if (rc) return rc;
     // the checks between the stages come before the later stages' own: after them those cannot refuse their n
-    if (e->demod.cfg.max_in < d.cap)
-        return fail(SDRG_E_INVALID, "demod max_in %d smaller than the ddc's row length %d", e->demod.cfg.max_in, d.cap);
+    if (v.max_in < d.cap)
+        return fail(SDRG_E_INVALID, "%s max_in %d smaller than the ddc's row length %d", v.name, v.max_in, d.cap);
     if (squelch && e->sq.cfg.max_in < d.cap)
         return fail(SDRG_E_INVALID, "squelch max_in %d smaller than the ddc's row length %d", e->sq.cfg.max_in, d.cap);
     if (agc && e->agc.cfg.max_in < d.cap)
         return fail(SDRG_E_INVALID, "agc max_in %d smaller than the ddc's row length %d", e->agc.cfg.max_in, d.cap);
     if (resample) {
-        if (e->demod.cfg.out_format != SDRG_DEMOD_OUT_F32)
-            return fail(SDRG_E_INVALID, "the resampler reads float audio: demod out_format must be SDRG_DEMOD_OUT_F32");
-        if (e->rs.cfg.components != 1)
-            return fail(SDRG_E_INVALID, "the resampler reads real audio: resample components must be 1");
-        if (e->rs.cfg.max_in < e->demod.cap())
-            return fail(SDRG_E_INVALID, "resample max_in %d smaller than the demod's row length %d", e->rs.cfg.max_in,
-                        e->demod.cap());
+        if (!v.f32)
+            return fail(SDRG_E_INVALID, "the resampler reads float audio: %s out_format must be %s", v.name, v.f32_name);
+        if (e->rs.cfg.components != v.components)
+            return fail(SDRG_E_INVALID, "the resampler reads %s: resample components must be %d",
+                        v.components == 1 ? "real audio" : "both sidebands", v.components);
+        if (e->rs.cfg.max_in < v.cap)
+            return fail(SDRG_E_INVALID, "resample max_in %d smaller than the %s's row length %d", e->rs.cfg.max_in, v.name,
+                        v.cap);
     }
-    rc = demod_resolve(e, d.n_out, &a);
-    a.in_stride = d.cap;  // the channel's rows are the DDC's
-    if (!rc && resample) rc = rs_resolve(e, a.cap, a.n_out, &r);
+    if (sideband) {
+        rc = sb_resolve(e, d.n_out, &s);
+        s.in_stride = d.cap;  // the channel's rows are the DDC's
+    } else {
+        rc = demod_resolve(e, d.n_out, &a);
+        a.in_stride = d.cap;
+    }
+    const StageCall &det_call = sideband ? static_cast<const StageCall &>(s) : a;
+    if (!rc && resample) rc = rs_resolve(e, det_call.cap, det_call.n_out, &r);
     if (!rc && squelch) rc = sq_resolve(e, d.cap, d.n_out, sq_records, &q);
     if (!rc && agc) rc = agc_resolve(e, d.cap, d.n_out, agc_records, &g);
     if (rc) return rc;
-    const StageCall &last = resample ? static_cast<const StageCall &>(r) : a;
+    const StageCall &last = resample ? static_cast<const StageCall &>(r) : det_call;
     // a stage that is not in the mask was not resolved: its aux is null, and nothing is staged or copied for it
     const HostAux aux(last.out_bytes, &q, &g);
     DeviceScope dscope(e->device);
@@ -2957,16 +3124,17 @@ static int32_t chain_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t
     rc = ddc_reserve(e, d);
     if (!rc && squelch) rc = sq_reserve(e, q);
     if (!rc && agc) rc = agc_reserve(e, g);
-    if (!rc) rc = demod_reserve(e, a);
+    if (!rc) rc = sideband ? sb_reserve(e, s) : demod_reserve(e, a);
     if (!rc && resample) rc = rs_reserve(e, r);
     if (!rc) rc = ensure_device(&e->chain_chan, d.out_bytes / sizeof(float));
-    if (!rc && resample) rc = ensure_device(&e->chain_audio, a.out_bytes / sizeof(float));
+    if (!rc && resample) rc = ensure_device(&e->chain_audio, det_call.out_bytes / sizeof(float));
     if (!rc) rc = host_begin(e, iq, d.in_bytes, aux.staged_bytes());
     if (!rc) aux.stage(e);
     if (!rc) rc = ddc_launch(e, d, e->stream_in.p, e->chain_chan.p);
     if (!rc && squelch) rc = sq_launch(e, q, e->chain_chan.p, e->chain_chan.p);
     if (!rc && agc) rc = agc_launch(e, g, e->chain_chan.p, e->chain_chan.p);
-    if (!rc) rc = demod_launch(e, a, e->chain_chan.p, resample ? (void *)e->chain_audio.p : e->stream_out.p);
+    void *audio = resample ? (void *)e->chain_audio.p : (void *)e->stream_out.p;
+    if (!rc) rc = sideband ? sb_launch(e, s, e->chain_chan.p, audio) : demod_launch(e, a, e->chain_chan.p, audio);
     if (!rc && resample) rc = rs_launch(e, r, e->chain_audio.p, e->stream_out.p);
     if (!rc) rc = aux.finish(e, out, last.out_bytes);
     if (rc) return rc;
@@ -2976,25 +3144,31 @@ static int32_t chain_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t
 
 int32_t sdrg_engine_listen_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
                                 sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records) {
-    return chain_host(e, steps, iq, fmt, out, n_out, squelch_records, agc_records);
+    return chain_host(e, Detector::Demod, steps, iq, fmt, out, n_out, squelch_records, agc_records);
 }
 
 int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    return chain_host(e, 0, iq, fmt, out, n_out);
+    return chain_host(e, Detector::Demod, 0, iq, fmt, out, n_out);
 }
 
 int32_t sdrg_engine_ddc_demod_resample_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
-    return chain_host(e, SDRG_LISTEN_RESAMPLE, iq, fmt, out, n_out);
+    return chain_host(e, Detector::Demod, SDRG_LISTEN_RESAMPLE, iq, fmt, out, n_out);
 }
 
 int32_t sdrg_engine_ddc_squelch_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out,
                                            sdrg_squelch_record *records) {
-    return chain_host(e, SDRG_LISTEN_SQUELCH, iq, fmt, out, n_out, records);
+    return chain_host(e, Detector::Demod, SDRG_LISTEN_SQUELCH, iq, fmt, out, n_out, records);
 }
 
 int32_t sdrg_engine_ddc_squelch_demod_resample_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out,
                                                     int32_t *n_out, sdrg_squelch_record *records) {
-    return chain_host(e, SDRG_LISTEN_SQUELCH | SDRG_LISTEN_RESAMPLE, iq, fmt, out, n_out, records);
+    return chain_host(e, Detector::Demod, SDRG_LISTEN_SQUELCH | SDRG_LISTEN_RESAMPLE, iq, fmt, out, n_out, records);
+}
+
+int32_t sdrg_engine_listen_sideband_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out,
+                                         int32_t *n_out, sdrg_squelch_record *squelch_records,
+                                         sdrg_agc_record *agc_records) {
+    return chain_host(e, Detector::Sideband, steps, iq, fmt, out, n_out, squelch_records, agc_records);
 }
 
 int32_t sdrg_engine_set_callbacks(sdrg_engine *e, const sdrg_callbacks *cbs) {

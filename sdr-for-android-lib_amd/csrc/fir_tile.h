@@ -1,5 +1,5 @@
-// fir_tile.h — the tile form the decimating stages share (ddc.hip, demod.hip's FIR kernel, channelizer.hip; resample.hip
-// takes its grid and carry_history, and has a filter phase per output in place of the polyphase layout below).
+// fir_tile.h — the tile form the decimating stages share (ddc.hip, demod.hip's FIR kernel, channelizer.hip, sideband.hip;
+// resample.hip takes its grid and carry_history, and has a filter phase per output in place of the polyphase layout below).
 //
 // A stage filters each stream with a window of H + 1 values and decimates by D.  A call's outputs j in [0, n_out) read
 // the values at the local indices t = first + j D - k, k in [0, H]; t in [0, N) is this call's frame, t in [-H, 0) the
@@ -13,8 +13,8 @@
 //                in memory, one uint4 load each; the chunks the window covers only in part, at its ends, and every chunk
 //                of a base that is not sample-aligned, sample by sample.  Both unpack as load_i1 / load_q1 of
 //                ssb_common.h.  Where a value lands in LDS, and what is done to it first, is the stage's (its sink).
-//   FIR          (polyphase_fir) one output per lane from the polyphase layout [u mod D][u / D], rows of `row` (odd)
-//                values: at tap k lane j reads u = j D + (H - k), one row for the whole wave and consecutive columns for
+//   FIR          (polyphase_fir; polyphase_fir_pairwise for a tap per component) one output per lane from the polyphase
+//                layout [u mod D][u / D], rows of `row` (odd) values: at tap k lane j reads u = j D + (H - k), one row for the whole wave and consecutive columns for
 //                consecutive lanes, so the reads are conflict-free for every D (a linear layout puts the lanes D values
 //                apart: gcd(D, 32)-way conflicts), and the row base moves by scalar arithmetic only.
 // Nothing here sets the contraction mode of a sum of its own: polyphase_fir belongs to stages compiled with
@@ -129,6 +129,43 @@ __device__ __forceinline__ V polyphase_fir(const float *tap_lds, const V *smp, i
     }
     for (; k < T; k++) {
         acc = acc + V(tap_lds[k]) * smp[at];
+        at += r == 0 ? wrap : -row;
+        r = r == 0 ? D - 1 : r - 1;
+    }
+    return acc;
+}
+
+// polyphase_fir's sibling for a tap per component (sideband.hip): acc = acc + c[k] * v[u] on the pairs, component by
+// component, the same u, order and layout.  The taps are pairs in LDS too, two to a 16-byte read.  V is a two-component
+// vector type whose * and + work per component.
+template <typename V>
+__device__ __forceinline__ V polyphase_fir_pairwise(const V *tap_lds, const V *smp, int T, int D, int row, int tid) {
+    constexpr int AHEAD = 8;  // LDS reads in flight per lane, as above
+    const int H = T - 1;
+    V acc = V(0.0f);
+    int r = H % D;
+    int at = (H % D) * row + H / D + tid;
+    const int wrap = (D - 1) * row - 1;
+    int k = 0;
+    for (; k + AHEAD <= T; k += AHEAD) {
+        V v[AHEAD], c[AHEAD];
+#pragma unroll
+        for (int i = 0; i < AHEAD; i += 2) {
+            const float4 cc = *reinterpret_cast<const float4 *>(tap_lds + k + i);
+            c[i] = V{cc.x, cc.y};
+            c[i + 1] = V{cc.z, cc.w};
+        }
+#pragma unroll
+        for (int i = 0; i < AHEAD; i++) {
+            v[i] = smp[at];
+            at += r == 0 ? wrap : -row;
+            r = r == 0 ? D - 1 : r - 1;
+        }
+#pragma unroll
+        for (int i = 0; i < AHEAD; i++) acc = acc + c[i] * v[i];
+    }
+    for (; k < T; k++) {
+        acc = acc + tap_lds[k] * smp[at];
         at += r == 0 ? wrap : -row;
         r = r == 0 ? D - 1 : r - 1;
     }

@@ -293,4 +293,22 @@ constexpr int AGC_STATE_HEAD = 4;
 int agc_tile(int block);  // consecutive samples per workgroup of the power and of the apply kernel
 hipError_t launch_agc(const float *chan, int n_streams, const AgcParams &p, float *out, hipStream_t stream);
 
+// Sideband stage (sideband.hip): per stream and output j in [0, n_out), A = sum_k cr[k] zr[first + j decim - k] and
+// Bm = sum_k ci[k] zi[first + j decim - k], z the n complex samples at chan + stream * in_stride (float2) and, at
+// indices in [-(taps - 1), 0), hist_old [n_streams][taps - 1][2] (fresh: zeros, not read); u = A - Bm, l = A + Bm.
+// Writes out [n_streams][cap] whole (u gain, l gain, or at mode BOTH the pairs of them; zeros from n_out on; float or
+// int16 by out_format) and, if n > 0, the samples at [n - (taps - 1), n) to hist_new.  taps_dev: [taps][2] floats
+// (cr, ci) in device memory.  tile, row, n_tiles, vec_ok and pair_ok are the launcher's.
+struct SidebandParams {
+    int n, in_stride, decim, taps, first, n_out, cap;
+    int mode, out_format, fresh;
+    float gain;
+    const float *taps_dev;
+    const float *hist_old;
+    float *hist_new;
+    int tile, row, n_tiles, vec_ok, pair_ok;
+};
+int sideband_tile_outputs(int decim, int taps);  // outputs per workgroup
+hipError_t launch_sideband(const float *chan, int n_streams, const SidebandParams &p, void *out, hipStream_t stream);
+
 }  // namespace sdrg

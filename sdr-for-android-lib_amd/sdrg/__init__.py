@@ -47,6 +47,10 @@ DEMOD_OUT_DTYPE = {DEMOD_OUT_S16: np.int16, DEMOD_OUT_F32: np.float32}
 RESAMPLE_OUT_S16, RESAMPLE_OUT_F32 = 0, 1                           # SDRG_RESAMPLE_OUT_*
 RESAMPLE_MAX_FACTOR, RESAMPLE_MAX_TAPS_PER_PHASE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_IN = 512, 64, 8192, 1 << 20
 RESAMPLE_OUT_DTYPE = {RESAMPLE_OUT_S16: np.int16, RESAMPLE_OUT_F32: np.float32}
+SIDEBAND_UPPER, SIDEBAND_LOWER, SIDEBAND_BOTH = 0, 1, 2             # SDRG_SIDEBAND_UPPER / _LOWER / _BOTH
+SIDEBAND_OUT_S16, SIDEBAND_OUT_F32 = 0, 1                           # SDRG_SIDEBAND_OUT_*
+SIDEBAND_MAX_TAPS, SIDEBAND_MAX_DECIMATION, SIDEBAND_MAX_IN = 511, 64, 1 << 20  # SDRG_SIDEBAND_MAX_*
+SIDEBAND_OUT_DTYPE = {SIDEBAND_OUT_S16: np.int16, SIDEBAND_OUT_F32: np.float32}
 STATUS = {0: "SDRG_OK", -1: "SDRG_E_INVALID", -2: "SDRG_E_UNSUPPORTED", -3: "SDRG_E_NOMEM", -4: "SDRG_E_HIP",
           -5: "SDRG_E_NODEVICE"}
 BYTES_PER_SAMPLE = {CF32: 8, CS8: 2, CU8: 2, CS16: 4}
@@ -143,6 +147,9 @@ EXPORTS = [
     "sdrg_engine_ddc_squelch_demod_host", "sdrg_engine_ddc_squelch_demod_resample_host",
     "sdrg_agc_design", "sdrg_agc_geometry", "sdrg_engine_set_agc", "sdrg_engine_get_agc", "sdrg_engine_agc_reset",
     "sdrg_engine_agc_device", "sdrg_engine_agc_host", "sdrg_engine_listen_host",
+    "sdrg_sideband_design", "sdrg_sideband_geometry", "sdrg_engine_set_sideband", "sdrg_engine_get_sideband",
+    "sdrg_engine_sideband_reset", "sdrg_engine_sideband_max_out", "sdrg_engine_sideband_device",
+    "sdrg_engine_sideband_host", "sdrg_engine_listen_sideband_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -255,7 +262,17 @@ class AgcConfig(ctypes.Structure):
 AGC_RECORD_DTYPE = np.dtype([("gain", "<f4"), ("gain_db", "<f4"), ("level_db", "<f4"), ("attacks", "<i4")])
 AGC_DET_MEAN, AGC_DET_PEAK = 0, 1
 AGC_DESIGN_FIELDS = ("max_gain", "init_gain", "floor_thr", "alpha_a", "alpha_d")
-# the steps of Engine.listen (SDRG_LISTEN_*)
+
+
+class SidebandConfig(ctypes.Structure):
+    """sdrg_sideband_config: the sideband stage's channel rate, band, mode, decimation, tap count, output format, row
+    length and gain (include/sdrg.h)."""
+    _fields_ = [("channel_rate_hz", ctypes.c_double), ("low_hz", ctypes.c_double), ("high_hz", ctypes.c_double),
+                ("mode", ctypes.c_int32), ("audio_decimation", ctypes.c_int32), ("taps", ctypes.c_int32),
+                ("out_format", ctypes.c_int32), ("max_in", ctypes.c_int32), ("gain", ctypes.c_float)]
+
+
+# the steps of Engine.listen and Engine.listen_sideband (SDRG_LISTEN_*)
 LISTEN_SQUELCH, LISTEN_AGC, LISTEN_RESAMPLE = 1, 2, 4
 
 
@@ -510,6 +527,15 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_agc_device": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_agc_host": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_listen_host": (_I32, [P, _I32, P, _I32, P, ctypes.POINTER(_I32), P, P]),
+        "sdrg_sideband_design": (_I32, [ctypes.POINTER(SidebandConfig), P, P]),
+        "sdrg_sideband_geometry": (_I32, [_I32, _I32, ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_sideband": (_I32, [P, ctypes.POINTER(SidebandConfig)]),
+        "sdrg_engine_get_sideband": (_I32, [P, ctypes.POINTER(SidebandConfig), P, P, ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_sideband_reset": (_I32, [P]),
+        "sdrg_engine_sideband_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_sideband_device": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_sideband_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_listen_sideband_host": (_I32, [P, _I32, P, _I32, P, ctypes.POINTER(_I32), P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -793,6 +819,23 @@ def agc_geometry(block: int) -> int:
     t = _I32()
     _check(load().sdrg_agc_geometry(block, ctypes.byref(t)), "agc_geometry")
     return t.value
+
+
+def sideband_design(**fields) -> dict:
+    """The sideband stage's band-pass for a configuration (host-side, no device): cr and ci, float32 [taps] each.  The
+    fields are sdrg_sideband_config's (fields left out are 0)."""
+    c = _filled(SidebandConfig, "sideband", fields)
+    T = c.taps if 0 < c.taps <= SIDEBAND_MAX_TAPS else 1
+    cr, ci = np.zeros(T, np.float32), np.zeros(T, np.float32)
+    _check(load().sdrg_sideband_design(ctypes.byref(c), _ptr(cr), _ptr(ci)), "sideband_design")
+    return dict(cr=cr, ci=ci)
+
+
+def sideband_geometry(audio_decimation: int, taps: int) -> int:
+    """How many consecutive outputs one workgroup of the sideband kernel computes for (R, T)."""
+    tile = _I32()
+    _check(load().sdrg_sideband_geometry(audio_decimation, taps, ctypes.byref(tile)), "sideband_geometry")
+    return tile.value
 
 
 def ssb_design(samp_count: int, sample_rate: int, sound_mode: int = 1) -> dict:
@@ -1401,6 +1444,62 @@ class Engine:
         _check(load().sdrg_engine_listen_host(self._h, steps, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out),
                                               _ptr(sq_rec), _ptr(agc_rec)), "listen_host")
         return out[..., :n_out.value], sq_rec, agc_rec
+
+    # ---- sideband stage ---------------------------------------------------------------------------
+    def set_sideband(self, **fields) -> None:
+        """sdrg_engine_set_sideband: the fields of sdrg_sideband_config (fields left out are 0); set_sideband(off=True)
+        switches the stage off."""
+        self._set_stage(SidebandConfig, "sideband", fields)
+
+    def sideband_config(self) -> dict:
+        """The configuration in force, plus its design (cr, ci) and samples_consumed."""
+        c, g = SidebandConfig(), ctypes.c_uint64()
+        cr, ci = np.zeros(SIDEBAND_MAX_TAPS, np.float32), np.zeros(SIDEBAND_MAX_TAPS, np.float32)
+        _check(load().sdrg_engine_get_sideband(self._h, ctypes.byref(c), _ptr(cr), _ptr(ci), ctypes.byref(g)),
+               "get_sideband")
+        return dict(_as_dict(c), cr=cr[:c.taps].copy(), ci=ci[:c.taps].copy(), samples_consumed=g.value)
+
+    def sideband_reset(self) -> None:
+        _check(load().sdrg_engine_sideband_reset(self._h), "sideband_reset")
+
+    def sideband_max_out(self) -> int:
+        """ceil(max_in / audio_decimation): the row length of a sideband call's output."""
+        return self._i32_call(load().sdrg_engine_sideband_max_out, "sideband_max_out")
+
+    def sideband_device(self, chan_ptr: int, n: int, out_ptr: int) -> int:
+        """Device path: chan [n_streams][max_in] complex64 in (the first n of every row are the call's), out
+        [n_streams][sideband_max_out()] int16 or float32 out, pairs (upper, lower) of them at SIDEBAND_BOTH;
+        asynchronous on the main stream.  Returns n_out."""
+        return self._i32_call(load().sdrg_engine_sideband_device, "sideband_device", chan_ptr, n, out_ptr)
+
+    def _sideband_out(self) -> np.ndarray:
+        c = self.sideband_config()
+        shape = (self.n_streams, self.sideband_max_out()) + ((2,) if c["mode"] == SIDEBAND_BOTH else ())
+        return np.empty(shape, SIDEBAND_OUT_DTYPE[c["out_format"]])
+
+    def sideband(self, chan: np.ndarray) -> np.ndarray:
+        """Host path: chan is complex64 [n_streams][n], n <= max_in; returns int16 or float32 [n_streams][n_out], with
+        a last axis of 2 (upper, lower) at SIDEBAND_BOTH."""
+        chan = np.asarray(chan, np.complex64).reshape(self.n_streams, -1)
+        n, max_in = chan.shape[1], self.sideband_config()["max_in"]
+        if n > max_in:
+            raise SdrgError(f"chan has {n} samples per stream, max_in is {max_in}")
+        rows = np.zeros((self.n_streams, max_in), np.complex64)
+        rows[:, :n] = chan
+        out = self._sideband_out()
+        return out[:, :self._i32_call(load().sdrg_engine_sideband_host, "sideband_host", _ptr(rows), n, _ptr(out))]
+
+    def listen_sideband(self, iq: np.ndarray, fmt: int = CS8, steps: int = 0):
+        """sdrg_engine_listen_sideband_host: listen() with the sideband stage in the demodulator's place, DDC ->
+        [squelch] -> [AGC] -> sideband -> [resampler].  Returns (the audio [n_streams][n_out], with a last axis of 2
+        at SIDEBAND_BOTH, the squelch's records or None, the AGC's records or None)."""
+        iq, n_out = self._iq(iq, fmt), _I32()
+        out = self._resample_out() if steps & LISTEN_RESAMPLE else self._sideband_out()
+        sq_rec = np.empty(self.n_streams, SquelchRecord) if steps & LISTEN_SQUELCH else None
+        agc_rec = np.empty(self.n_streams, AGC_RECORD_DTYPE) if steps & LISTEN_AGC else None
+        _check(load().sdrg_engine_listen_sideband_host(self._h, steps, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out),
+                                                       _ptr(sq_rec), _ptr(agc_rec)), "listen_sideband_host")
+        return out[:, :n_out.value], sq_rec, agc_rec
 
     def process_device(self, iq_ptr: int, fmt: int, stages: int, spectra_ptr: int | None, records_ptr: int | None,
                        pcm_ptr: int | None, now_ms: int = 0) -> None:
