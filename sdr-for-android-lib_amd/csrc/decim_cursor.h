@@ -1,7 +1,7 @@
 // decim_cursor.h — the host's side of a decimating stage's stream position (engine.cpp: DDC, demodulator, channelizer,
 // resampler, squelch, AGC, sideband; fir_tile.h has the device's side).  A stage decimates by D from the first sample after a restart:
 // the outputs sit on the global sample indices that are multiples of D (DecimCursor); the resampler's output m sits on
-// the input index floor(m M / L) with the filter phase (m M) mod L (ResampleCursor); the squelch's blocks start on the
+// the input index floor(m M / L) with the filter phase (m M) mod L (ResampleCursor); the block stages' blocks start on the
 // multiples of S (BlockCursor).  Host only: no HIP.
 #pragma once
 
@@ -67,8 +67,8 @@ struct ResampleCursor : StreamCursor {
     static int cap(int n, int L, int M) { return (int)(((int64_t)n * L + M - 1) / M); }
 };
 
-// The squelch's and the AGC's position (squelch.hip, agc.hip): the stream is cut into blocks of S samples (a power of two) at the global
-// indices that are multiples of S.  A call of n samples takes the positions [offset, offset + n) counted from the
+// The position of a block stage (the skeleton of block_stage.h: the squelch and the AGC): the stream is cut into blocks
+// of S samples (a power of two) at the global indices that are multiples of S.  A call of n samples takes the positions [offset, offset + n) counted from the
 // start of the block in progress, and completes the blocks that end at or before g + n.
 struct BlockCursor : StreamCursor {
     // samples of the block in progress that earlier calls consumed: g mod S

@@ -203,29 +203,27 @@ struct ResampleStage {
     void free_buffers() { release(&hist, &d_taps); }
 };
 
-// squelch stage (sdrg_engine_set_squelch / squelch_device / squelch_host / ddc_squelch_demod_host; squelch.hip)
-struct SquelchStage {
-    sdrg_squelch_config cfg{};
+// what a block stage (block_stage.h) keeps, whichever its law; Config has block, hang_blocks and max_in
+template <typename Config>
+struct BlockStage {
+    Config cfg{};
     bool set = false;
     BlockCursor cur;
-    float open_thr = 0.0f, close_thr = 0.0f, beta = 0.0f;  // squelch_design of cfg
-    PingPong<float> state;  // halves of [n_streams][S + SQ_STATE_HEAD]: L, open, hang, code, the block's powers so far
-    DeviceBuf<float> blk;   // [the most blocks a call completes][n_streams]: the blocks' powers, then their codes
-    size_t half(int B) const { return (size_t)B * (size_t)(cfg.block + SQ_STATE_HEAD); }
+    PingPong<float> state;  // halves of [n_streams][S + BLOCK_STATE_HEAD]: the law's four words, the block's powers so far
+    DeviceBuf<float> blk;   // [the most blocks a call completes][n_streams]: the blocks' statistics, then the law's words
+    size_t half(int B) const { return (size_t)B * (size_t)(cfg.block + BLOCK_STATE_HEAD); }
     void free_buffers() { release(&state, &blk); }
 };
 
+// squelch stage (sdrg_engine_set_squelch / squelch_device / squelch_host / ddc_squelch_demod_host; squelch.hip)
+struct SquelchStage : BlockStage<sdrg_squelch_config> {
+    float open_thr = 0.0f, close_thr = 0.0f, beta = 0.0f;  // squelch_design of cfg
+};
+
 // AGC stage (sdrg_engine_set_agc / agc_device / agc_host / listen_host; agc.hip)
-struct AgcStage {
-    sdrg_agc_config cfg{};
-    bool set = false;
-    BlockCursor cur;
-    float target = 0.0f;    // cfg.target as a float
-    AgcDesign des{};        // agc_design of cfg
-    PingPong<float> state;  // halves of [n_streams][S + AGC_STATE_HEAD]: G, G_prev, hang, P_last, the block's powers so far
-    DeviceBuf<float> blk;   // [the most blocks a call completes][n_streams]: the blocks' statistics, then their gains
-    size_t half(int B) const { return (size_t)B * (size_t)(cfg.block + AGC_STATE_HEAD); }
-    void free_buffers() { release(&state, &blk); }
+struct AgcStage : BlockStage<sdrg_agc_config> {
+    float target = 0.0f;  // cfg.target as a float
+    AgcDesign des{};      // agc_design of cfg
 };
 
 // sideband stage (sdrg_engine_set_sideband / sideband_device / sideband_host / listen_sideband_host; sideband.hip)
@@ -631,6 +629,71 @@ int32_t stage_call(sdrg_engine *e, const char *in_name, const void *in, void *ou
     }
     if (rc) return rc;
     *n_out = c.n_out;
+    return SDRG_OK;
+}
+
+// The block stages, squelch and AGC (block_stage.h): their three steps but for the law's constants, and
+// sdrg_<stage>_geometry
+static int32_t block_geometry(const char *stage, int32_t block, int32_t *tile) {
+    if (!tile) return fail(SDRG_E_INVALID, "null tile");
+    if (block < BLOCK_MIN || block > BLOCK_MAX || (block & (block - 1)) != 0)
+        return fail(SDRG_E_INVALID, "%s: block must be a power of two in [16, 1024]", stage);
+    *tile = block_tile(block);
+    return SDRG_OK;
+}
+
+struct BlockCall : StageCall {
+    int in_stride;  // complex samples between the rows of chan and of out
+};
+
+// n_out is the blocks the call completes (*n_blocks); aux, the records, record_bytes each
+template <typename Stage>
+static int32_t block_resolve(const sdrg_engine *e, const Stage &s, const char *stage, size_t record_bytes,
+                             int32_t in_stride, int32_t n, void *records, BlockCall *c) {
+    if (int32_t rc = require_set(s.set, stage)) return rc;
+    if (n < 0 || n > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "%s: n %d outside [0, max_in = %d]", stage, n, s.cfg.max_in);
+    if (in_stride < std::max(n, 1) || in_stride > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "%s: in_stride %d outside [max(n, 1) = %d, max_in = %d]", stage, in_stride,
+                    std::max(n, 1), s.cfg.max_in);
+    c->n = n;
+    c->in_stride = in_stride;
+    c->cap = in_stride;
+    c->n_out = s.cur.blocks(n, s.cfg.block);
+    c->in_bytes = c->out_bytes = (size_t)e->n_streams * (size_t)in_stride * 2 * sizeof(float);
+    c->aux = records;
+    c->aux_bytes = (size_t)e->n_streams * record_bytes;
+    return SDRG_OK;
+}
+
+template <typename Stage>
+static int32_t block_reserve(sdrg_engine *e, Stage *s) {
+    const int32_t rc = ensure_device(&s->state, s->half(e->n_streams));
+    const size_t blocks = (size_t)BlockCursor::cap(s->cfg.max_in, s->cfg.block);
+    return rc ? rc : ensure_device(&s->blk, (size_t)e->n_streams * blocks);
+}
+
+// One call of a block stage on the main stream: chan and out (rows of in_stride complex samples; out may be chan) and
+// c.aux, the records or null, in device memory.  p holds the law's constants; the BlockParams part is filled here.
+template <typename Stage, typename Params>
+static int32_t block_launch(sdrg_engine *e, Stage *s, const BlockCall &c, Params p,
+                            hipError_t (*launch)(const float *, int, const Params &, float *, hipStream_t),
+                            const void *chan, void *out) {
+    const size_t half = s->half(e->n_streams);
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.block = s->cfg.block;
+    p.hang = s->cfg.hang_blocks;
+    p.off = s->cur.offset(s->cfg.block);
+    p.n_blocks = c.n_out;
+    p.fresh = s->cur.fresh ? 1 : 0;
+    p.state_old = s->state.half(s->cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    p.state_new = s->state.next(s->cur, half);
+    p.blk = s->blk.p;
+    p.records = static_cast<decltype(p.records)>(c.aux);
+    HIP_TRY(launch(static_cast<const float *>(chan), e->n_streams, p, static_cast<float *>(out), e->s_main));
+    s->cur.advance(c.n);  // a call without samples wrote out and the records only: the state stays where it is
+    e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
@@ -2678,13 +2741,7 @@ int32_t sdrg_squelch_design(const sdrg_squelch_config *cfg, float *open_thr, flo
     return SDRG_OK;
 }
 
-int32_t sdrg_squelch_geometry(int32_t block, int32_t *tile) {
-    if (!tile) return fail(SDRG_E_INVALID, "null tile");
-    if (block < SDRG_SQUELCH_MIN_BLOCK || block > SDRG_SQUELCH_MAX_BLOCK || (block & (block - 1)) != 0)
-        return fail(SDRG_E_INVALID, "squelch: block must be a power of two in [16, 1024]");
-    *tile = squelch_tile(block);
-    return SDRG_OK;
-}
+int32_t sdrg_squelch_geometry(int32_t block, int32_t *tile) { return block_geometry("squelch", block, tile); }
 
 int32_t sdrg_engine_set_squelch(sdrg_engine *e, const sdrg_squelch_config *cfg) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
@@ -2718,63 +2775,22 @@ int32_t sdrg_engine_squelch_reset(sdrg_engine *e) {
     return SDRG_OK;
 }
 
-struct SqCall : StageCall {
-    int in_stride;  // complex samples between the rows of chan and of out
-};
-
-// n_out is the blocks the call completes (*n_blocks); aux, the records
-static int32_t sq_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_squelch_record *records, SqCall *c) {
-    const SquelchStage &s = e->sq;
-    if (int32_t rc = require_set(s.set, "squelch")) return rc;
-    if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "squelch: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
-    if (in_stride < std::max(n, 1) || in_stride > s.cfg.max_in)
-        return fail(SDRG_E_INVALID, "squelch: in_stride %d outside [max(n, 1) = %d, max_in = %d]", in_stride,
-                    std::max(n, 1), s.cfg.max_in);
-    c->n = n;
-    c->in_stride = in_stride;
-    c->cap = in_stride;
-    c->n_out = s.cur.blocks(n, s.cfg.block);
-    c->in_bytes = c->out_bytes = (size_t)e->n_streams * (size_t)in_stride * 2 * sizeof(float);
-    c->aux = records;
-    c->aux_bytes = (size_t)e->n_streams * sizeof(sdrg_squelch_record);
-    return SDRG_OK;
+static int32_t sq_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_squelch_record *records, BlockCall *c) {
+    return block_resolve(e, e->sq, "squelch", sizeof(*records), in_stride, n, records, c);
 }
 
-static int32_t sq_reserve(sdrg_engine *e, const SqCall &) {
-    SquelchStage &s = e->sq;
-    const int32_t rc = ensure_device(&s.state, s.half(e->n_streams));
-    const size_t blocks = (size_t)BlockCursor::cap(s.cfg.max_in, s.cfg.block);
-    return rc ? rc : ensure_device(&s.blk, (size_t)e->n_streams * blocks);
-}
+static int32_t sq_reserve(sdrg_engine *e, const BlockCall &) { return block_reserve(e, &e->sq); }
 
-// one squelch call on the main stream: chan and out (rows of in_stride complex samples; out may be chan) and c.aux, the
-// records or null, in device memory
-static int32_t sq_launch(sdrg_engine *e, const SqCall &c, const void *chan, void *out) {
-    SquelchStage &s = e->sq;
-    const size_t half = s.half(e->n_streams);
+static int32_t sq_launch(sdrg_engine *e, const BlockCall &c, const void *chan, void *out) {
     SquelchParams p{};
-    p.n = c.n;
-    p.in_stride = c.in_stride;
-    p.block = s.cfg.block;
-    p.hang = s.cfg.hang_blocks;
-    p.off = s.cur.offset(s.cfg.block);
-    p.n_blocks = c.n_out;
-    p.fresh = s.cur.fresh ? 1 : 0;
-    p.beta = s.beta;
-    p.open_thr = s.open_thr;
-    p.close_thr = s.close_thr;
-    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
-    p.state_new = s.state.next(s.cur, half);
-    p.blk = s.blk.p;
-    p.records = static_cast<sdrg_squelch_record *>(c.aux);
-    HIP_TRY(launch_squelch(static_cast<const float *>(chan), e->n_streams, p, static_cast<float *>(out), e->s_main));
-    s.cur.advance(c.n);  // a call without samples wrote out and the records only: the state stays where it is
-    e->outputs_unmarked = true;
-    return SDRG_OK;
+    p.beta = e->sq.beta;
+    p.open_thr = e->sq.open_thr;
+    p.close_thr = e->sq.close_thr;
+    return block_launch(e, &e->sq, c, p, launch_squelch, chan, out);
 }
 
 static constexpr auto sq_stage =
-    &stage_call<SqCall, sq_resolve, sq_reserve, sq_launch, int32_t, int32_t, sdrg_squelch_record *>;
+    &stage_call<BlockCall, sq_resolve, sq_reserve, sq_launch, int32_t, int32_t, sdrg_squelch_record *>;
 
 int32_t sdrg_engine_squelch_device(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
                                    sdrg_squelch_record *records, int32_t *n_blocks) {
@@ -2805,13 +2821,7 @@ int32_t sdrg_agc_design(const sdrg_agc_config *cfg, float *max_gain, float *init
     return SDRG_OK;
 }
 
-int32_t sdrg_agc_geometry(int32_t block, int32_t *tile) {
-    if (!tile) return fail(SDRG_E_INVALID, "null tile");
-    if (block < SDRG_AGC_MIN_BLOCK || block > SDRG_AGC_MAX_BLOCK || (block & (block - 1)) != 0)
-        return fail(SDRG_E_INVALID, "agc: block must be a power of two in [16, 1024]");
-    *tile = agc_tile(block);
-    return SDRG_OK;
-}
+int32_t sdrg_agc_geometry(int32_t block, int32_t *tile) { return block_geometry("agc", block, tile); }
 
 int32_t sdrg_engine_set_agc(sdrg_engine *e, const sdrg_agc_config *cfg) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
@@ -2844,48 +2854,15 @@ int32_t sdrg_engine_agc_reset(sdrg_engine *e) {
     return SDRG_OK;
 }
 
-struct AgcCall : StageCall {
-    int in_stride;  // complex samples between the rows of chan and of out
-};
+static int32_t agc_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_agc_record *records, BlockCall *c) {
+    return block_resolve(e, e->agc, "agc", sizeof(*records), in_stride, n, records, c);
+}
 
-// n_out is the blocks the call completes (*n_blocks); aux, the records
-static int32_t agc_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_agc_record *records, AgcCall *c) {
+static int32_t agc_reserve(sdrg_engine *e, const BlockCall &) { return block_reserve(e, &e->agc); }
+
+static int32_t agc_launch(sdrg_engine *e, const BlockCall &c, const void *chan, void *out) {
     const AgcStage &s = e->agc;
-    if (int32_t rc = require_set(s.set, "agc")) return rc;
-    if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "agc: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
-    if (in_stride < std::max(n, 1) || in_stride > s.cfg.max_in)
-        return fail(SDRG_E_INVALID, "agc: in_stride %d outside [max(n, 1) = %d, max_in = %d]", in_stride, std::max(n, 1),
-                    s.cfg.max_in);
-    c->n = n;
-    c->in_stride = in_stride;
-    c->cap = in_stride;
-    c->n_out = s.cur.blocks(n, s.cfg.block);
-    c->in_bytes = c->out_bytes = (size_t)e->n_streams * (size_t)in_stride * 2 * sizeof(float);
-    c->aux = records;
-    c->aux_bytes = (size_t)e->n_streams * sizeof(sdrg_agc_record);
-    return SDRG_OK;
-}
-
-static int32_t agc_reserve(sdrg_engine *e, const AgcCall &) {
-    AgcStage &s = e->agc;
-    const int32_t rc = ensure_device(&s.state, s.half(e->n_streams));
-    const size_t blocks = (size_t)BlockCursor::cap(s.cfg.max_in, s.cfg.block);
-    return rc ? rc : ensure_device(&s.blk, (size_t)e->n_streams * blocks);
-}
-
-// one agc call on the main stream: chan and out (rows of in_stride complex samples; out may be chan) and c.aux, the
-// records or null, in device memory
-static int32_t agc_launch(sdrg_engine *e, const AgcCall &c, const void *chan, void *out) {
-    AgcStage &s = e->agc;
-    const size_t half = s.half(e->n_streams);
     AgcParams p{};
-    p.n = c.n;
-    p.in_stride = c.in_stride;
-    p.block = s.cfg.block;
-    p.hang = s.cfg.hang_blocks;
-    p.off = s.cur.offset(s.cfg.block);
-    p.n_blocks = c.n_out;
-    p.fresh = s.cur.fresh ? 1 : 0;
     p.detector = s.cfg.detector;
     p.target = s.target;
     p.max_gain = s.des.max_gain;
@@ -2893,18 +2870,11 @@ static int32_t agc_launch(sdrg_engine *e, const AgcCall &c, const void *chan, vo
     p.floor_thr = s.des.floor_thr;
     p.alpha_a = s.des.alpha_a;
     p.alpha_d = s.des.alpha_d;
-    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
-    p.state_new = s.state.next(s.cur, half);
-    p.blk = s.blk.p;
-    p.records = static_cast<sdrg_agc_record *>(c.aux);
-    HIP_TRY(launch_agc(static_cast<const float *>(chan), e->n_streams, p, static_cast<float *>(out), e->s_main));
-    s.cur.advance(c.n);  // a call without samples wrote out and the records only: the state stays where it is
-    e->outputs_unmarked = true;
-    return SDRG_OK;
+    return block_launch(e, &e->agc, c, p, launch_agc, chan, out);
 }
 
 static constexpr auto agc_stage =
-    &stage_call<AgcCall, agc_resolve, agc_reserve, agc_launch, int32_t, int32_t, sdrg_agc_record *>;
+    &stage_call<BlockCall, agc_resolve, agc_reserve, agc_launch, int32_t, int32_t, sdrg_agc_record *>;
 
 int32_t sdrg_engine_agc_device(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
                                sdrg_agc_record *records, int32_t *n_blocks) {
@@ -3080,8 +3050,8 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     if (!rc && squelch) rc = require_set(e->sq.set, "squelch");
     if (!rc && agc) rc = require_set(e->agc.set, "agc");
     DdcCall d;
-    SqCall q;
-    AgcCall g;
+    BlockCall q;
+    BlockCall g;
     DemodCall a;
     SbCall s;
     RsCall r;

@@ -251,46 +251,46 @@ struct ResampleParams {
 constexpr int RESAMPLE_TILE = 256;  // outputs per workgroup, one per lane
 hipError_t launch_resample(const void *in, int n_streams, const ResampleParams &p, void *out, hipStream_t stream);
 
-// Squelch stage (squelch.hip): per stream the n complex samples at chan + stream * in_stride (float2) are the positions
-// [off, off + n) of a run of blocks of `block` samples, off = g mod block: n_blocks = (off + n) / block of them complete.
-// state_old / state_new [n_streams][block + SQ_STATE_HEAD] floats: {L, open, hang, the code of the block in progress}
-// (the last three as int bits), then that block's powers so far; fresh: state_old reads as zeros (and off is 0).  blk
-// [blocks][n_streams] floats is scratch: the completed blocks' mean powers, then, in their place, the code of the block
-// after each.  Writes out [n_streams][in_stride][2] whole (the gated samples, zeros from n on; out may be chan), and, if
-// n > 0, state_new; records [n_streams] unless nullptr.  n_streams, log2_block, inv_block and tile are the launcher's.
-struct SquelchParams {
+// The block stages (block_stage.h: the squelch and the AGC): per stream the n complex samples at chan + stream *
+// in_stride (float2) are the positions [off, off + n) of a run of blocks of `block` samples, off = g mod block: n_blocks
+// = (off + n) / block of them complete.  state_old / state_new [n_streams][block + BLOCK_STATE_HEAD] floats: the law's
+// four words, then the powers so far of the block in progress; fresh: state_old is not read (and off is 0).  blk
+// [blocks][n_streams] floats is scratch: the completed blocks' statistics, then, in their place, what the law leaves
+// for the pass kernel.  Writes out [n_streams][in_stride][2] whole (zeros from n on; out may be chan), and, if n > 0,
+// state_new; the stage's records [n_streams] unless nullptr.  n_streams, log2_block, tile and inv_block are the
+// launcher's.
+struct BlockParams {
     int n, in_stride, block, hang, off, n_blocks, fresh;
-    float beta, open_thr, close_thr;
     const float *state_old;
     float *state_new;
     float *blk;
-    sdrg_squelch_record *records;
     int n_streams, log2_block, tile;
     float inv_block;
 };
-constexpr int SQ_STATE_HEAD = 4;
-int squelch_tile(int block);  // consecutive samples per workgroup of the power and of the gate kernel
+constexpr int BLOCK_STATE_HEAD = 4;
+constexpr int BLOCK_PASS = 512;  // positions a workgroup takes at a time
+constexpr int BLOCK_MIN = SDRG_SQUELCH_MIN_BLOCK, BLOCK_MAX = SDRG_SQUELCH_MAX_BLOCK, BLOCK_MAX_IN = SDRG_SQUELCH_MAX_IN;
+static_assert(BLOCK_MIN == SDRG_AGC_MIN_BLOCK && BLOCK_MAX == SDRG_AGC_MAX_BLOCK && BLOCK_MAX_IN == SDRG_AGC_MAX_IN,
+              "one skeleton: the two stages' limits are the same");
+// consecutive samples per workgroup of the power and of the pass kernel
+inline int block_tile(int block) { return block > BLOCK_PASS ? block : BLOCK_PASS; }
+
+// Squelch stage (squelch.hip).  The state's words: {L, open, hang, the code of the block in progress} (the last three as
+// int bits); a fresh stream's read as zeros.  blk ends as the code of the block after each; out is the gated samples.
+struct SquelchParams : BlockParams {
+    float beta, open_thr, close_thr;
+    sdrg_squelch_record *records;
+};
 hipError_t launch_squelch(const float *chan, int n_streams, const SquelchParams &p, float *out, hipStream_t stream);
 
-// AGC stage (agc.hip): the squelch's positions and blocks (n, in_stride, block, off, n_blocks, fresh as above).
-// state_old / state_new [n_streams][block + AGC_STATE_HEAD] floats: {G, G_prev, hang (int bits), P_last}, then the powers
-// so far of the block in progress; fresh: state_old reads as {init_gain, init_gain, 0, +0} (and off is 0).  blk
-// [blocks][n_streams] floats is scratch: the completed blocks' statistics (detector: the mean or the peak power), then,
-// in their place, the gain after each.  Writes out [n_streams][in_stride][2] whole (block b of the stream under the ramp
-// from gain[b - 2] to gain[b - 1], zeros from n on; out may be chan), and, if n > 0, state_new; records [n_streams] unless
-// nullptr.  n_streams, log2_block, inv_block and tile are the launcher's.
-struct AgcParams {
-    int n, in_stride, block, hang, off, n_blocks, fresh, detector;
+// AGC stage (agc.hip).  The state's words: {G, G_prev, hang (int bits), P_last}; a fresh stream's read as {init_gain,
+// init_gain, 0, +0}.  blk's statistics are the mean or the peak power (detector), and it ends as the gain after each
+// block; out is block b of the stream under the ramp from gain[b - 2] to gain[b - 1].
+struct AgcParams : BlockParams {
+    int detector;
     float target, max_gain, init_gain, floor_thr, alpha_a, alpha_d;
-    const float *state_old;
-    float *state_new;
-    float *blk;
     sdrg_agc_record *records;
-    int n_streams, log2_block, tile;
-    float inv_block;
 };
-constexpr int AGC_STATE_HEAD = 4;
-int agc_tile(int block);  // consecutive samples per workgroup of the power and of the apply kernel
 hipError_t launch_agc(const float *chan, int n_streams, const AgcParams &p, float *out, hipStream_t stream);
 
 // Sideband stage (sideband.hip): per stream and output j in [0, n_out), A = sum_k cr[k] zr[first + j decim - k] and

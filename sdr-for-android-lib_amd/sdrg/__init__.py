@@ -1366,17 +1366,20 @@ class Engine:
         return self._i32_call(load().sdrg_engine_squelch_device, "squelch_device", chan_ptr, in_stride, n, out_ptr,
                               records_ptr)
 
-    def squelch_host(self, chan: np.ndarray, want_records: bool = True):
-        """Host path: chan is complex64 [n_streams][n], n <= max_in.  Returns (the gated complex64 [n_streams][n], the
-        records [n_streams] SquelchRecord or None, n_blocks)."""
+    def _block_host(self, fn, what: str, chan: np.ndarray, record_dtype, want_records: bool):
+        """The host call of a block stage (squelch_host, agc_host): (out [n_streams][n], records or None, n_blocks)."""
         chan = np.ascontiguousarray(chan, np.complex64).reshape(self.n_streams, -1)
         n = chan.shape[1]
         rows = chan if n else np.zeros((self.n_streams, 1), np.complex64)  # a call without samples still wants rows
         out = np.empty_like(rows)
-        rec = np.empty(self.n_streams, SquelchRecord) if want_records else None
-        n_blocks = self._i32_call(load().sdrg_engine_squelch_host, "squelch_host", _ptr(rows), rows.shape[1], n,
-                                  _ptr(out), _ptr(rec))
+        rec = np.empty(self.n_streams, record_dtype) if want_records else None
+        n_blocks = self._i32_call(fn, what, _ptr(rows), rows.shape[1], n, _ptr(out), _ptr(rec))
         return out[:, :n], rec, n_blocks
+
+    def squelch_host(self, chan: np.ndarray, want_records: bool = True):
+        """Host path: chan is complex64 [n_streams][n], n <= max_in.  Returns (the gated complex64 [n_streams][n], the
+        records [n_streams] SquelchRecord or None, n_blocks)."""
+        return self._block_host(load().sdrg_engine_squelch_host, "squelch_host", chan, SquelchRecord, want_records)
 
     def _chain_with_records(self, fn, what: str, iq: np.ndarray, fmt: int, make_out):
         iq, out, rec, n_out = self._iq(iq, fmt), make_out(), np.empty(self.n_streams, SquelchRecord), _I32()
@@ -1423,14 +1426,7 @@ class Engine:
     def agc_host(self, chan: np.ndarray, want_records: bool = True):
         """Host path: chan is complex64 [n_streams][n], n <= max_in.  Returns (the levelled complex64 [n_streams][n],
         the records [n_streams] AGC_RECORD_DTYPE or None, n_blocks)."""
-        chan = np.ascontiguousarray(chan, np.complex64).reshape(self.n_streams, -1)
-        n = chan.shape[1]
-        rows = chan if n else np.zeros((self.n_streams, 1), np.complex64)  # a call without samples still wants rows
-        out = np.empty_like(rows)
-        rec = np.empty(self.n_streams, AGC_RECORD_DTYPE) if want_records else None
-        n_blocks = self._i32_call(load().sdrg_engine_agc_host, "agc_host", _ptr(rows), rows.shape[1], n, _ptr(out),
-                                  _ptr(rec))
-        return out[:, :n], rec, n_blocks
+        return self._block_host(load().sdrg_engine_agc_host, "agc_host", chan, AGC_RECORD_DTYPE, want_records)
 
     def listen(self, iq: np.ndarray, fmt: int = CS8, steps: int = 0):
         """sdrg_engine_listen_host: iq [n_streams][samplesPerReading * 2] raw samples through DDC -> [squelch] -> [AGC]

@@ -17,7 +17,7 @@ import ddc_cases as dd
 import demod_cases as dm
 import resample_cases as rs
 import squelch_cases as sq
-from stage_harness import FS, GUARD, engine, invalid, out_buffer, read_out, same, to_device
+from stage_harness import FS, GUARD, BlockRig, engine, invalid, out_buffer, read_out, rows_bytes, same, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -37,76 +37,15 @@ def T():
     return torch
 
 
-def rows_bytes(chan, stride):
-    """chan complex64 [B][n] -> float32 [B][stride][2], NaN past n."""
-    B, n = chan.shape
-    rows = np.full((B, stride, 2), np.nan, np.float32)
-    rows[:, :n] = np.ascontiguousarray(chan).view(np.float32).reshape(B, n, 2)
-    return rows
-
-
-class Gate:
+class Gate(BlockRig):
     """An engine with the squelch set, and the restatement that follows it call by call."""
+    stage = "squelch"
+    record = "SquelchRecord"
 
-    def __init__(self, S, T, B, n=1024, **cfg):
-        self.S, self.T, self.B = S, T, B
-        self.eng = engine(S, B, n)
-        self.configure(**cfg)
-
-    def configure(self, **cfg):
-        self.cfg = cfg
-        self.eng.set_squelch(**cfg)
-        self.remodel()
-
-    def remodel(self):
-        """A fresh restatement from the library's design of the configuration in force."""
-        d = self.eng.squelch_config()
-        assert all(d[k] == v for k, v in self.cfg.items()), d
-        assert d["samples_consumed"] == 0
+    def make_model(self, d):
         des = self.S.squelch_design(**self.cfg)
         assert all(des[k].tobytes() == d[k].tobytes() for k in ("open_thr", "close_thr", "beta"))
-        self.model = sq.Squelch(self.B, d["open_thr"], d["close_thr"], d["beta"], d["block"], d["hang_blocks"])
-
-    def device_call(self, chan, in_stride=None, records=True, in_place=False, shift=0):
-        """squelch_device into 0xAA-filled buffers between guard bytes: (out [B][stride], records [B][4] as uint32 or
-        None, n_blocks).  shift: bytes by which chan and out are moved off their 16-byte alignment."""
-        T, eng, B = self.T, self.eng, self.B
-        stride = self.cfg["max_in"] if in_stride is None else in_stride
-        rows = rows_bytes(chan, stride)
-        nbytes = B * stride * 8
-        out_t = out_buffer(T, nbytes + shift)
-        rec_t = out_buffer(T, B * 16)
-        if in_place:
-            out_t[GUARD + shift:GUARD + shift + nbytes] = T.from_numpy(rows.view(np.uint8).reshape(-1)).to("cuda:0")
-            chan_ptr = out_t.data_ptr() + GUARD + shift
-        else:
-            chan_t = T.full((nbytes + shift,), 0, dtype=T.uint8, device="cuda:0")
-            chan_t[shift:] = T.from_numpy(rows.view(np.uint8).reshape(-1)).to("cuda:0")
-            chan_ptr = chan_t.data_ptr() + shift
-        T.cuda.synchronize()
-        nb = eng.squelch_device(chan_ptr, stride, chan.shape[1], out_t.data_ptr() + GUARD + shift,
-                                rec_t.data_ptr() + GUARD if records else None)
-        eng.synchronize()
-        o = out_t.cpu().numpy()
-        assert np.all(o[:GUARD + shift] == 0xAA) and np.all(o[GUARD + shift + nbytes:] == 0xAA), "bytes outside out"
-        out = o[GUARD + shift:GUARD + shift + nbytes].copy().view(np.complex64).reshape(B, stride)
-        if not records:
-            assert np.all(rec_t.cpu().numpy() == 0xAA), "records written without a pointer"
-            return out, None, nb
-        return out, read_out(rec_t, (B, 4), np.uint32), nb
-
-    def check(self, chan, what=None, **kw):
-        got, rec, nb = self.device_call(chan, **kw)
-        want, want_rec, want_nb = self.model.call(chan, in_stride=got.shape[1])
-        same(got, nb, want, want_nb, what)
-        if rec is not None:
-            same(rec, nb, want_rec.view(np.uint32).reshape(self.B, 4), want_nb, (what, "records"))
-            rec = rec.view(self.S.SquelchRecord)[:, 0]
-        assert self.eng.squelch_config()["samples_consumed"] == self.model.g
-        return got, rec, nb
-
-    def close(self):
-        self.eng.close()
+        return sq.Squelch(self.B, d["open_thr"], d["close_thr"], d["beta"], d["block"], d["hang_blocks"])
 
 
 @pytest.mark.parametrize("B", [1, 9, 65, 130])

@@ -23,8 +23,12 @@ $HIP -I$D/csrc -Iinclude -ffp-contract=off -c $D/csrc/ddc.hip -o $B/ddc.o
 $HIP -I$D/csrc -Iinclude -ffp-contract=off -c $D/csrc/demod.hip -o $B/demod.o
 $HIP -I$D/csrc -Iinclude -c $D/csrc/channelizer.hip -o $B/channelizer.o
 $HIP -I$D/csrc -Iinclude -ffp-contract=off -c $D/csrc/resample.hip -o $B/resample.o
+$HIP -I$D/csrc -Iinclude -ffp-contract=off -c $D/csrc/squelch.hip -o $B/squelch.o
+$HIP -I$D/csrc -Iinclude -ffp-contract=off -c $D/csrc/agc.hip -o $B/agc.o
+$HIP -I$D/csrc -Iinclude -ffp-contract=off -c $D/csrc/sideband.hip -o $B/sideband.o
 for f in design engine pulse_bank ingest compat ssb_processor dist; do $CXX -c $D/csrc/$f.cpp -o $B/$f.o; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $D/lib/libsdrg_$NAME.so $B/spectrum.o $B/fftany.o $B/stats.o \
     $B/ssb.o $B/pulse.o $B/gather.o $B/design.o $B/engine.o $B/pulse_bank.o $B/ingest.o $B/compat.o $B/ssb_processor.o \
-    $B/dist.o $B/display.o $B/integrate.o $B/peaks.o $B/ddc.o $B/demod.o $B/channelizer.o $B/resample.o -lm -lpthread -ldl
+    $B/dist.o $B/display.o $B/integrate.o $B/peaks.o $B/ddc.o $B/demod.o $B/channelizer.o $B/resample.o \
+    $B/squelch.o $B/agc.o $B/sideband.o -lm -lpthread -ldl
 echo built $D/lib/libsdrg_$NAME.so
