@@ -109,7 +109,7 @@ __global__ __launch_bounds__(CHAN_THREADS) void chan_kernel(const char *__restri
     const int tid = threadIdx.x, b = blockIdx.y;
     const int N = p.n, D = p.decim, M = p.channels, L = M * p.taps_per_channel, H = L - 1;
     const char *frame = iq + (size_t)b * (size_t)N * BPS;
-    const f2 *hist_old = p.hist_old ? reinterpret_cast<const f2 *>(p.hist_old) + (size_t)b * (size_t)H : nullptr;
+    const f2 *hist_old = stream_history<f2>(p.hist_old, b, H);
     f2 *orows = reinterpret_cast<f2 *>(out) + (size_t)b * (size_t)p.n_channels * (size_t)p.cap;
 
     if ((int)blockIdx.x == p.n_tiles) {  // the new history and the zero tails of the written rows
@@ -121,14 +121,12 @@ __global__ __launch_bounds__(CHAN_THREADS) void chan_kernel(const char *__restri
         return;
     }
 
-    const int tile = p.tile;
-    const int j0 = (int)blockIdx.x * tile, nj = min(tile, p.n_out - j0);
-    const int w0 = p.first + j0 * D - H;     // local index of the window's first sample
-    const int count = (nj - 1) * D + L;      // samples in the window: w0 + count - 1 = the last output's newest sample
+    const FirWindow w(p, L);
+    const int tile = p.tile, j0 = w.j0, nj = w.nj;
     f2 *smp = chan_lds;                      // the window; later the transposed spectra
     f2 *U = chan_lds + p.region;             // [tile][M + 1]: branch sums, then the DFT's intermediate
 
-    stage_iq_window<FMT, CHAN_THREADS>(frame, hist_old, w0, count, H, p.vec_ok, tid, ChanSink<FMT>{smp});
+    stage_iq_window<FMT, CHAN_THREADS>(frame, hist_old, w.w0, w.count, H, p.vec_ok, tid, ChanSink<FMT>{smp});
     __syncthreads();
 
     // branch sums.  Output times past nj of a last tile read words of the window's region that hold nothing of this

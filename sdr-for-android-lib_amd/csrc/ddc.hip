@@ -82,29 +82,27 @@ __global__ __launch_bounds__(DDC_THREADS) void ddc_kernel(const char *__restrict
     const int tid = threadIdx.x, b = blockIdx.y;
     const int N = p.n, D = p.decim, T = p.taps, H = T - 1;
     const char *frame = iq + (size_t)b * (size_t)N * BPS;
-    const ddc_f2 *hist_old = p.hist_old ? reinterpret_cast<const ddc_f2 *>(p.hist_old) + (size_t)b * (size_t)H : nullptr;
+    const ddc_f2 *hist_old = stream_history<ddc_f2>(p.hist_old, b, H);
     const float2 *phasors = reinterpret_cast<const float2 *>(p.phasors);
     ddc_f2 *orow = reinterpret_cast<ddc_f2 *>(out) + (size_t)b * (size_t)p.cap;
 
-    if ((int)blockIdx.x == p.n_tiles) {  // the new history (re-mixed from the frame) and the zero tail of out
-        ddc_f2 *hist_new = reinterpret_cast<ddc_f2 *>(p.hist_new) + (size_t)b * (size_t)H;
-        carry_history<DDC_THREADS>(hist_new, hist_old, N, H, tid, [&](int t) {
-            return ddc_mix(phasors[t], load_i1<FMT>(frame, t), load_q1<FMT>(frame, t));
-        });
-        for (int j = p.n_out + tid; j < p.cap; j += DDC_THREADS) orow[j] = ddc_f2{0.0f, 0.0f};
+    if ((int)blockIdx.x == p.n_tiles) {  // the new history is re-mixed from the frame
+        close_stream<DDC_THREADS, 1>(p.hist_new, hist_old, b, N, H, orow, p.n_out, p.cap, tid,
+                                     [&](int t) {
+                                         return ddc_mix(phasors[t], load_i1<FMT>(frame, t), load_q1<FMT>(frame, t));
+                                     });
         return;
     }
 
-    const int j0 = (int)blockIdx.x * p.tile, nj = min(p.tile, p.n_out - j0);
-    const int w0 = p.first + j0 * D - H;     // local index of the window's first sample
-    const int count = (nj - 1) * D + T;      // samples in the window: w0 + count - 1 = the last output's newest sample
+    const FirWindow w(p, T);
     float *tap_lds = reinterpret_cast<float *>(ddc_lds);  // the taps, then the window
     ddc_f2 *smp = ddc_lds + DDC_TAP_SLOTS;
-    for (int i = tid; i < T; i += DDC_THREADS) tap_lds[i] = taps.h[i];
-    stage_iq_window<FMT, DDC_THREADS>(frame, hist_old, w0, count, H, p.vec_ok, tid, DdcSink<FMT>{smp, phasors, D, p.row});
+    stage_taps<DDC_THREADS>(tap_lds, taps.h, T, tid);
+    stage_iq_window<FMT, DDC_THREADS>(frame, hist_old, w.w0, w.count, H, p.vec_ok, tid,
+                                      DdcSink<FMT>{smp, phasors, D, p.row});
     __syncthreads();
 
-    if (tid < nj) orow[j0 + tid] = polyphase_fir(tap_lds, smp, T, D, p.row, tid);
+    if (tid < w.nj) orow[w.j0 + tid] = polyphase_fir(tap_lds, smp, T, D, p.row, tid);
 }
 
 }  // namespace
@@ -115,15 +113,11 @@ hipError_t launch_ddc(const void *iq, int fmt, int n_streams, const DdcParams &p
                       hipStream_t stream) {
     if (n_streams <= 0) return hipSuccess;
     DdcParams p = p0;
-    if (!iq || !out || !p.nco_tab || !p.phasors || p.n < 1 || p.n > (1 << 20) || p.decim < 1 || p.decim > SDRG_DDC_MAX_DECIMATION ||
-        p.taps < 1 || p.taps > SDRG_DDC_MAX_TAPS || (p.taps & 1) == 0 || (p.taps > 1 && !p.hist_new) || p.first < 0 ||
-        p.first >= p.decim || p.n_out < 0 || p.cap != (p.n + p.decim - 1) / p.decim || p.n_out > p.cap ||
-        (p.n_out > 0 && (int64_t)p.first + (int64_t)(p.n_out - 1) * p.decim >= p.n) || n_streams > 65535)
+    if (!iq || !out || !p.nco_tab || !p.phasors || p.n < 1 || p.n > (1 << 20) || (p.taps > 1 && !p.hist_new) ||
+        n_streams > 65535 ||
+        !fir_tile_plan(&p, DDC_LDS_SAMPLES, DDC_THREADS, SDRG_DDC_MAX_DECIMATION, SDRG_DDC_MAX_TAPS) ||
+        p.cap != (p.n + p.decim - 1) / p.decim)  // the rows are as long as the frame's outputs can be
         return hipErrorInvalidValue;
-    p.tile = ddc_tile_outputs(p.decim, p.taps);
-    p.row = (p.tile - 1 + (p.taps + p.decim - 1) / p.decim) | 1;
-    p.n_tiles = (p.n_out + p.tile - 1) / p.tile;
-    if (p.tile < 1 || (int64_t)p.row * p.decim > DDC_LDS_SAMPLES) return hipErrorInvalidValue;
     void (*k)(const char *, DdcParams, DdcTaps, float *) = nullptr;
     const int bps = for_iq_format(fmt, [&](auto f) { k = ddc_kernel<decltype(f)::value>; });
     if (bps == 0) return hipErrorInvalidValue;

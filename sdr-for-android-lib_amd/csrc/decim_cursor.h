@@ -1,8 +1,10 @@
-// decim_cursor.h — the host's side of a decimating stage's stream position (engine.cpp: DDC, demodulator, channelizer,
-// resampler, squelch, AGC, sideband; fir_tile.h has the device's side).  A stage decimates by D from the first sample after a restart:
-// the outputs sit on the global sample indices that are multiples of D (DecimCursor); the resampler's output m sits on
-// the input index floor(m M / L) with the filter phase (m M) mod L (ResampleCursor); the block stages' blocks start on the
-// multiples of S (BlockCursor).  Host only: no HIP.
+// decim_cursor.h — the host's side of a streaming stage's stream position (engine.cpp: DDC, demodulator, channelizer,
+// resampler, squelch, AGC, sideband; fir_tile.h and block_stage.h have the device's side).  A stage decimates by D from
+// the first sample after a restart: the outputs sit on the global sample indices that are multiples of D
+// (DecimCursor); the resampler's output m sits on the input index floor(m M / L) with the filter phase (m M) mod L
+// (ResampleCursor); the block stages' blocks start on the multiples of S (BlockCursor).  What a call reads of the
+// stream before it comes from one half of a PingPong; the five FIR stages get PingPong::old, which is nullptr after a
+// restart: no old history, zeros.  Host only: no HIP.
 #pragma once
 
 #include <stddef.h>
@@ -59,7 +61,7 @@ struct ResampleCursor : StreamCursor {
     // local input index (q - g) and filter phase of the next call's first output
     int q0(int L, int M) const { return ahead(L, M) / L; }
     int phi0(int L, int M) const { return ahead(L, M) % L; }
-    // outputs of a call of n samples: ceil((g + n) L / M) - ceil(g L / M) = ceil((n L - d) / M), which is 0 for n L <= d
+    // outputs of a call of n samples: ceil((g + n) L / M) - ceil(g L / M) = ceil((n L - d) / M), 0 for n L <= d
     int n_out(int n, int L, int M) const {
         return (int)(((int64_t)n * L - ahead(L, M) + M - 1) / M);
     }
@@ -68,8 +70,9 @@ struct ResampleCursor : StreamCursor {
 };
 
 // The position of a block stage (the skeleton of block_stage.h: the squelch and the AGC): the stream is cut into blocks
-// of S samples (a power of two) at the global indices that are multiples of S.  A call of n samples takes the positions [offset, offset + n) counted from the
-// start of the block in progress, and completes the blocks that end at or before g + n.
+// of S samples (a power of two) at the global indices that are multiples of S.  A call of n samples takes the
+// positions [offset, offset + n) counted from the start of the block in progress, and completes the blocks that end
+// at or before g + n.
 struct BlockCursor : StreamCursor {
     // samples of the block in progress that earlier calls consumed: g mod S
     int offset(int S) const { return (int)(g % (uint64_t)S); }

@@ -159,49 +159,30 @@ __global__ __launch_bounds__(DEMOD_WAVE) void demod_chain_kernel(DemodParams p, 
 }
 
 template <int FMT>
-struct DemodOut;
-template <>
-struct DemodOut<SDRG_DEMOD_OUT_F32> {
-    typedef float type;
-    static __device__ __forceinline__ float make(float o) { return o; }
-};
-template <>
-struct DemodOut<SDRG_DEMOD_OUT_S16> {
-    typedef int16_t type;
-    static __device__ __forceinline__ int16_t make(float o) {
-        return (int16_t)rintf(fminf(fmaxf(o, -1.0f), 1.0f) * 32767.0f);
-    }
-};
-
-template <int FMT>
 __global__ __launch_bounds__(DEMOD_THREADS) void demod_fir_kernel(DemodParams p, DemodTaps taps, void *__restrict__ out) {
-    typedef typename DemodOut<FMT>::type out_t;
+    typedef typename FirOut<FMT>::type out_t;
     extern __shared__ __attribute__((aligned(16))) float demod_lds[];
     const int tid = threadIdx.x, b = blockIdx.y;
     const int N = p.n, R = p.decim, T = p.taps, H = T - 1;
     const float *v = p.scratch + (size_t)b * (size_t)p.scratch_stride;
-    const float *hist_old = p.fresh ? nullptr : p.hist_old + (size_t)b * (size_t)H;
+    const float *hist_old = stream_history<float>(p.hist_old, b, H);
     out_t *orow = static_cast<out_t *>(out) + (size_t)b * (size_t)p.cap;
 
-    if ((int)blockIdx.x == p.n_tiles) {  // the new history (a call without samples keeps the old one) and the zero tail
-        if (N > 0)
-            carry_history<DEMOD_THREADS>(p.hist_new + (size_t)b * (size_t)H, hist_old, N, H, tid,
-                                        [&](int t) { return v[t]; });
-        for (int j = p.n_out + tid; j < p.cap; j += DEMOD_THREADS) orow[j] = (out_t)0;
+    if ((int)blockIdx.x == p.n_tiles) {
+        close_stream<DEMOD_THREADS, 1>(p.hist_new, hist_old, b, N, H, orow, p.n_out, p.cap, tid,
+                                       [&](int t) { return v[t]; });
         return;
     }
 
-    const int j0 = (int)blockIdx.x * p.tile, nj = min(p.tile, p.n_out - j0);
-    const int w0 = p.first + j0 * R - H;  // local index of the window's first value
-    const int count = (nj - 1) * R + T;   // values in the window: w0 + count - 1 = the last output's newest one
+    const FirWindow w(p, T);
     const int row = p.row;
     float *tap_lds = demod_lds, *smp = demod_lds + DEMOD_TAP_SLOTS;
-    for (int i = tid; i < T; i += DEMOD_THREADS) tap_lds[i] = taps.h[i];
+    stage_taps<DEMOD_THREADS>(tap_lds, taps.h, T, tid);
     {
         int r = tid % R, q = tid / R;  // [u mod R][u / R] of u = tid, then u += DEMOD_THREADS
         const int dr = DEMOD_THREADS % R, dq = DEMOD_THREADS / R;
-        for (int u = tid; u < count; u += DEMOD_THREADS) {
-            const int t = w0 + u;  // < N: the last output's newest value is first + (n_out - 1) R < N
+        for (int u = tid; u < w.count; u += DEMOD_THREADS) {
+            const int t = w.w0 + u;  // < N: the last output's newest value is first + (n_out - 1) R < N
             float x = 0.0f;
             if (t >= 0)
                 x = v[t];
@@ -214,7 +195,7 @@ __global__ __launch_bounds__(DEMOD_THREADS) void demod_fir_kernel(DemodParams p,
     }
     __syncthreads();
 
-    if (tid < nj) orow[j0 + tid] = DemodOut<FMT>::make(polyphase_fir(tap_lds, smp, T, R, row, tid) * p.gain);
+    if (tid < w.nj) orow[w.j0 + tid] = FirOut<FMT>::make(polyphase_fir(tap_lds, smp, T, R, row, tid) * p.gain);
 }
 
 }  // namespace
@@ -225,19 +206,14 @@ hipError_t launch_demod(const float *chan, int n_streams, const DemodParams &p0,
                         hipStream_t stream) {
     if (n_streams <= 0) return hipSuccess;
     DemodParams p = p0;
-    if (!out || p.n < 0 || p.n > SDRG_DEMOD_MAX_IN || p.decim < 1 || p.decim > SDRG_DEMOD_MAX_DECIMATION || p.taps < 1 ||
-        p.taps > SDRG_DEMOD_MAX_TAPS || (p.taps & 1) == 0 || p.first < 0 || p.first >= p.decim || p.n_out < 0 ||
-        p.cap < 1 || p.n_out > p.cap || (p.n_out > 0 && (int64_t)p.first + (int64_t)(p.n_out - 1) * p.decim >= p.n) ||
-        (p.mode != SDRG_DEMOD_AM && p.mode != SDRG_DEMOD_FM) ||
+    if (!out || p.n < 0 || p.n > SDRG_DEMOD_MAX_IN || (p.mode != SDRG_DEMOD_AM && p.mode != SDRG_DEMOD_FM) ||
         (p.out_format != SDRG_DEMOD_OUT_S16 && p.out_format != SDRG_DEMOD_OUT_F32) || n_streams > 65535)
         return hipErrorInvalidValue;
     if (p.n > 0 && (!chan || !p.scratch || !p.state_new || p.in_stride < p.n || p.scratch_stride < p.n ||
                     (p.taps > 1 && !p.hist_new) || (!p.fresh && (!p.state_old || (p.taps > 1 && !p.hist_old)))))
         return hipErrorInvalidValue;
-    p.tile = demod_tile_outputs(p.decim, p.taps);
-    p.row = (p.tile - 1 + (p.taps + p.decim - 1) / p.decim) | 1;
-    p.n_tiles = (p.n_out + p.tile - 1) / p.tile;
-    if (p.tile < 1 || (int64_t)p.row * p.decim > DEMOD_LDS_SAMPLES) return hipErrorInvalidValue;
+    if (!fir_tile_plan(&p, DEMOD_LDS_SAMPLES, DEMOD_THREADS, SDRG_DEMOD_MAX_DECIMATION, SDRG_DEMOD_MAX_TAPS))
+        return hipErrorInvalidValue;
     hipError_t er;
     if (p.n > 0) {
         const dim3 grid((unsigned)((p.n + DEMOD_THREADS - 1) / DEMOD_THREADS), (unsigned)n_streams);

@@ -565,9 +565,12 @@ int32_t ensure_nco_table(sdrg_engine *e) {
 // NCO table, the DDC's taps) and commits no cursor.  x_launch fills the kernel's parameters, launches, and only then
 // advances the cursor.  stage_call runs the three for one stage, chain_host for several.
 
-// what every resolved call has; a stage's XCall adds what its own launch needs
+// what every resolved call has; the DDC's and the channelizer's calls add what their own launches need
 struct StageCall {
     int n = 0, n_out = 0, cap = 0;       // samples per stream in, outputs per row, the row length of `out`
+    // Values between the rows of the input, for the stages that read rows another stage may have written: the stage's
+    // max_in or the caller's, or in a chain the DDC's cap.  The block stages' `out` has the same rows.
+    int in_stride = 0;
     size_t in_bytes = 0, out_bytes = 0;  // a host call's input and output
     // A second output, which the squelch and the AGC have (their records): where the launch writes it, nullptr if the
     // caller wants none, and its size.
@@ -632,6 +635,22 @@ int32_t stage_call(sdrg_engine *e, const char *in_name, const void *in, void *ou
     return SDRG_OK;
 }
 
+// The host's part of a tile-form launch (FirTileParams: the DDC, the demodulator, the sideband stage): the call, where
+// the cursor puts the first output, and the history's two halves, which start hist_at floats into a half of `pp`.
+// After a restart hist_old is nullptr: zeros.
+static void fir_tile_fill(FirTileParams *p, const DecimCursor &cur, int decim, int taps, const StageCall &c,
+                          const PingPong<float> &pp, size_t half, size_t hist_at = 0) {
+    p->n = c.n;
+    p->decim = decim;
+    p->taps = taps;
+    p->first = cur.first(decim);
+    p->n_out = c.n_out;
+    p->cap = c.cap;
+    const float *old = pp.old(cur, half);
+    p->hist_old = old ? old + hist_at : nullptr;
+    p->hist_new = pp.next(cur, half) + hist_at;
+}
+
 // The block stages, squelch and AGC (block_stage.h): their three steps but for the law's constants, and
 // sdrg_<stage>_geometry
 static int32_t block_geometry(const char *stage, int32_t block, int32_t *tile) {
@@ -642,14 +661,10 @@ static int32_t block_geometry(const char *stage, int32_t block, int32_t *tile) {
     return SDRG_OK;
 }
 
-struct BlockCall : StageCall {
-    int in_stride;  // complex samples between the rows of chan and of out
-};
-
 // n_out is the blocks the call completes (*n_blocks); aux, the records, record_bytes each
 template <typename Stage>
 static int32_t block_resolve(const sdrg_engine *e, const Stage &s, const char *stage, size_t record_bytes,
-                             int32_t in_stride, int32_t n, void *records, BlockCall *c) {
+                             int32_t in_stride, int32_t n, void *records, StageCall *c) {
     if (int32_t rc = require_set(s.set, stage)) return rc;
     if (n < 0 || n > s.cfg.max_in)
         return fail(SDRG_E_INVALID, "%s: n %d outside [0, max_in = %d]", stage, n, s.cfg.max_in);
@@ -676,7 +691,7 @@ static int32_t block_reserve(sdrg_engine *e, Stage *s) {
 // One call of a block stage on the main stream: chan and out (rows of in_stride complex samples; out may be chan) and
 // c.aux, the records or null, in device memory.  p holds the law's constants; the BlockParams part is filled here.
 template <typename Stage, typename Params>
-static int32_t block_launch(sdrg_engine *e, Stage *s, const BlockCall &c, Params p,
+static int32_t block_launch(sdrg_engine *e, Stage *s, const StageCall &c, Params p,
                             hipError_t (*launch)(const float *, int, const Params &, float *, hipStream_t),
                             const void *chan, void *out) {
     const size_t half = s->half(e->n_streams);
@@ -2327,20 +2342,11 @@ static int32_t ddc_reserve(sdrg_engine *e, const DdcCall &c) {
 // one ddc call on the main stream: iq, out in device memory
 static int32_t ddc_launch(sdrg_engine *e, const DdcCall &c, const void *iq, void *out) {
     DdcStage &s = e->ddc;
-    const int D = s.cfg.decimation;
-    const size_t half = s.half(e->n_streams);
     DdcParams p{};
-    p.n = c.n;
-    p.decim = D;
-    p.taps = s.cfg.taps;
-    p.first = c.cur.first(D);
-    p.n_out = c.n_out;
-    p.cap = c.cap;
+    fir_tile_fill(&p, c.cur, s.cfg.decimation, s.cfg.taps, c, s.hist, s.half(e->n_streams));
     p.inc = nco_increment(s.cfg.offset_hz, c.fs);
     p.g0_lo = (uint32_t)c.cur.g;
     p.nco_tab = e->d_nco_tab;
-    p.hist_old = s.hist.old(c.cur, half);
-    p.hist_new = s.hist.next(c.cur, half);
     p.phasors = s.w.p;
     HIP_TRY(launch_ddc(iq, c.fmt, e->n_streams, p, s.taps, static_cast<float *>(out), e->s_main));
     s.cur = c.cur;
@@ -2419,11 +2425,7 @@ int32_t sdrg_engine_demod_max_out(const sdrg_engine *e, int32_t *cap) {
     return SDRG_OK;
 }
 
-struct DemodCall : StageCall {
-    int in_stride;  // complex samples between the rows of chan: max_in, or in a chain the DDC's cap
-};
-
-static int32_t demod_resolve(const sdrg_engine *e, int32_t n, DemodCall *c) {
+static int32_t demod_resolve(const sdrg_engine *e, int32_t n, StageCall *c) {
     const DemodStage &s = e->demod;
     if (int32_t rc = require_set(s.set, "demod")) return rc;
     if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "demod: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
@@ -2437,26 +2439,20 @@ static int32_t demod_resolve(const sdrg_engine *e, int32_t n, DemodCall *c) {
     return SDRG_OK;
 }
 
-static int32_t demod_reserve(sdrg_engine *e, const DemodCall &) {
+static int32_t demod_reserve(sdrg_engine *e, const StageCall &) {
     const int32_t rc = ensure_device(&e->demod.state, e->demod.half(e->n_streams));
     return rc ? rc : ensure_device(&e->demod.scratch, (size_t)e->n_streams * (size_t)e->demod.cfg.max_in);
 }
 
 // one demod call on the main stream: chan (rows of in_stride complex samples), out in device memory
-static int32_t demod_launch(sdrg_engine *e, const DemodCall &c, const void *chan, void *out) {
+static int32_t demod_launch(sdrg_engine *e, const StageCall &c, const void *chan, void *out) {
     DemodStage &s = e->demod;
     const size_t B = (size_t)e->n_streams, half = s.half(e->n_streams);
-    float *old_half = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
-    float *new_half = s.state.next(s.cur, half);
     DemodParams p{};
-    p.n = c.n;
+    // a half holds the streams' four state words, then the history
+    fir_tile_fill(&p, s.cur, s.cfg.audio_decimation, s.cfg.audio_taps, c, s.state, half, B * 4);
     p.in_stride = c.in_stride;
     p.scratch_stride = s.cfg.max_in;
-    p.decim = s.cfg.audio_decimation;
-    p.taps = s.cfg.audio_taps;
-    p.first = s.cur.first(s.cfg.audio_decimation);
-    p.n_out = c.n_out;
-    p.cap = c.cap;
     p.mode = s.cfg.mode;
     p.out_format = s.cfg.out_format;
     p.fresh = s.cur.fresh ? 1 : 0;
@@ -2464,10 +2460,8 @@ static int32_t demod_launch(sdrg_engine *e, const DemodCall &c, const void *chan
     p.alpha = s.alpha;
     p.a = s.a;
     p.gain = s.cfg.gain;
-    p.state_old = old_half;
-    p.hist_old = old_half + B * 4;
-    p.state_new = new_half;
-    p.hist_new = new_half + B * 4;
+    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    p.state_new = s.state.next(s.cur, half);
     p.scratch = s.scratch.p;
     HIP_TRY(launch_demod(static_cast<const float *>(chan), e->n_streams, p, s.taps, out, e->s_main));
     s.cur.advance(c.n);  // a call without samples wrote out only: the state stays where it is
@@ -2475,7 +2469,7 @@ static int32_t demod_launch(sdrg_engine *e, const DemodCall &c, const void *chan
     return SDRG_OK;
 }
 
-static constexpr auto demod_stage = &stage_call<DemodCall, demod_resolve, demod_reserve, demod_launch, int32_t>;
+static constexpr auto demod_stage = &stage_call<StageCall, demod_resolve, demod_reserve, demod_launch, int32_t>;
 
 int32_t sdrg_engine_demod_device(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
     return demod_stage(e, "chan", chan, out, n_out, false, n);
@@ -2672,11 +2666,7 @@ int32_t sdrg_engine_resample_max_out(const sdrg_engine *e, int32_t *cap) {
     return SDRG_OK;
 }
 
-struct RsCall : StageCall {
-    int in_stride;  // values between the rows of in
-};
-
-static int32_t rs_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, RsCall *c) {
+static int32_t rs_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, StageCall *c) {
     const ResampleStage &s = e->rs;
     if (int32_t rc = require_set(s.set, "resample")) return rc;
     if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "resample: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
@@ -2691,10 +2681,10 @@ static int32_t rs_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, Rs
     return SDRG_OK;
 }
 
-static int32_t rs_reserve(sdrg_engine *e, const RsCall &) { return ensure_device(&e->rs.hist, e->rs.half(e->n_streams)); }
+static int32_t rs_reserve(sdrg_engine *e, const StageCall &) { return ensure_device(&e->rs.hist, e->rs.half(e->n_streams)); }
 
 // one resample call on the main stream: in (rows of in_stride values), out in device memory
-static int32_t rs_launch(sdrg_engine *e, const RsCall &c, const void *in, void *out) {
+static int32_t rs_launch(sdrg_engine *e, const StageCall &c, const void *in, void *out) {
     ResampleStage &s = e->rs;
     const size_t half = s.half(e->n_streams);
     ResampleParams p{};
@@ -2709,10 +2699,9 @@ static int32_t rs_launch(sdrg_engine *e, const RsCall &c, const void *in, void *
     p.cap = c.cap;
     p.components = s.cfg.components;
     p.out_format = s.cfg.out_format;
-    p.fresh = s.cur.fresh ? 1 : 0;
     p.gain = s.cfg.gain;
     p.taps = s.d_taps.p;
-    p.hist_old = s.hist.old(s.cur, half);
+    p.hist_old = s.hist.old(s.cur, half);  // nullptr after a restart: zeros
     p.hist_new = s.hist.next(s.cur, half);
     HIP_TRY(launch_resample(in, e->n_streams, p, out, e->s_main));
     s.cur.advance(c.n);  // a call without samples wrote out only: the state stays where it is
@@ -2720,7 +2709,7 @@ static int32_t rs_launch(sdrg_engine *e, const RsCall &c, const void *in, void *
     return SDRG_OK;
 }
 
-static constexpr auto rs_stage = &stage_call<RsCall, rs_resolve, rs_reserve, rs_launch, int32_t, int32_t>;
+static constexpr auto rs_stage = &stage_call<StageCall, rs_resolve, rs_reserve, rs_launch, int32_t, int32_t>;
 
 int32_t sdrg_engine_resample_device(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *out,
                                     int32_t *n_out) {
@@ -2775,13 +2764,13 @@ int32_t sdrg_engine_squelch_reset(sdrg_engine *e) {
     return SDRG_OK;
 }
 
-static int32_t sq_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_squelch_record *records, BlockCall *c) {
+static int32_t sq_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_squelch_record *records, StageCall *c) {
     return block_resolve(e, e->sq, "squelch", sizeof(*records), in_stride, n, records, c);
 }
 
-static int32_t sq_reserve(sdrg_engine *e, const BlockCall &) { return block_reserve(e, &e->sq); }
+static int32_t sq_reserve(sdrg_engine *e, const StageCall &) { return block_reserve(e, &e->sq); }
 
-static int32_t sq_launch(sdrg_engine *e, const BlockCall &c, const void *chan, void *out) {
+static int32_t sq_launch(sdrg_engine *e, const StageCall &c, const void *chan, void *out) {
     SquelchParams p{};
     p.beta = e->sq.beta;
     p.open_thr = e->sq.open_thr;
@@ -2790,7 +2779,7 @@ static int32_t sq_launch(sdrg_engine *e, const BlockCall &c, const void *chan, v
 }
 
 static constexpr auto sq_stage =
-    &stage_call<BlockCall, sq_resolve, sq_reserve, sq_launch, int32_t, int32_t, sdrg_squelch_record *>;
+    &stage_call<StageCall, sq_resolve, sq_reserve, sq_launch, int32_t, int32_t, sdrg_squelch_record *>;
 
 int32_t sdrg_engine_squelch_device(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
                                    sdrg_squelch_record *records, int32_t *n_blocks) {
@@ -2854,13 +2843,13 @@ int32_t sdrg_engine_agc_reset(sdrg_engine *e) {
     return SDRG_OK;
 }
 
-static int32_t agc_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_agc_record *records, BlockCall *c) {
+static int32_t agc_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_agc_record *records, StageCall *c) {
     return block_resolve(e, e->agc, "agc", sizeof(*records), in_stride, n, records, c);
 }
 
-static int32_t agc_reserve(sdrg_engine *e, const BlockCall &) { return block_reserve(e, &e->agc); }
+static int32_t agc_reserve(sdrg_engine *e, const StageCall &) { return block_reserve(e, &e->agc); }
 
-static int32_t agc_launch(sdrg_engine *e, const BlockCall &c, const void *chan, void *out) {
+static int32_t agc_launch(sdrg_engine *e, const StageCall &c, const void *chan, void *out) {
     const AgcStage &s = e->agc;
     AgcParams p{};
     p.detector = s.cfg.detector;
@@ -2874,7 +2863,7 @@ static int32_t agc_launch(sdrg_engine *e, const BlockCall &c, const void *chan, 
 }
 
 static constexpr auto agc_stage =
-    &stage_call<BlockCall, agc_resolve, agc_reserve, agc_launch, int32_t, int32_t, sdrg_agc_record *>;
+    &stage_call<StageCall, agc_resolve, agc_reserve, agc_launch, int32_t, int32_t, sdrg_agc_record *>;
 
 int32_t sdrg_engine_agc_device(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
                                sdrg_agc_record *records, int32_t *n_blocks) {
@@ -2951,11 +2940,7 @@ int32_t sdrg_engine_sideband_max_out(const sdrg_engine *e, int32_t *cap) {
     return SDRG_OK;
 }
 
-struct SbCall : StageCall {
-    int in_stride;  // complex samples between the rows of chan: max_in, or in a chain the DDC's cap
-};
-
-static int32_t sb_resolve(const sdrg_engine *e, int32_t n, SbCall *c) {
+static int32_t sb_resolve(const sdrg_engine *e, int32_t n, StageCall *c) {
     const SidebandStage &s = e->sb;
     if (int32_t rc = require_set(s.set, "sideband")) return rc;
     if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "sideband: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
@@ -2969,34 +2954,25 @@ static int32_t sb_resolve(const sdrg_engine *e, int32_t n, SbCall *c) {
     return SDRG_OK;
 }
 
-static int32_t sb_reserve(sdrg_engine *e, const SbCall &) { return ensure_device(&e->sb.hist, e->sb.half(e->n_streams)); }
+static int32_t sb_reserve(sdrg_engine *e, const StageCall &) { return ensure_device(&e->sb.hist, e->sb.half(e->n_streams)); }
 
 // one sideband call on the main stream: chan (rows of in_stride complex samples), out in device memory
-static int32_t sb_launch(sdrg_engine *e, const SbCall &c, const void *chan, void *out) {
+static int32_t sb_launch(sdrg_engine *e, const StageCall &c, const void *chan, void *out) {
     SidebandStage &s = e->sb;
-    const size_t half = s.half(e->n_streams);
     SidebandParams p{};
-    p.n = c.n;
+    fir_tile_fill(&p, s.cur, s.cfg.audio_decimation, s.cfg.taps, c, s.hist, s.half(e->n_streams));
     p.in_stride = c.in_stride;
-    p.decim = s.cfg.audio_decimation;
-    p.taps = s.cfg.taps;
-    p.first = s.cur.first(s.cfg.audio_decimation);
-    p.n_out = c.n_out;
-    p.cap = c.cap;
     p.mode = s.cfg.mode;
     p.out_format = s.cfg.out_format;
-    p.fresh = s.cur.fresh ? 1 : 0;
     p.gain = s.cfg.gain;
     p.taps_dev = s.d_taps.p;
-    p.hist_old = s.hist.old(s.cur, half);  // nullptr after a restart: the kernel gets no old history
-    p.hist_new = s.hist.next(s.cur, half);
     HIP_TRY(launch_sideband(static_cast<const float *>(chan), e->n_streams, p, out, e->s_main));
     s.cur.advance(c.n);  // a call without samples wrote out only: the state stays where it is
     e->outputs_unmarked = true;
     return SDRG_OK;
 }
 
-static constexpr auto sb_stage = &stage_call<SbCall, sb_resolve, sb_reserve, sb_launch, int32_t>;
+static constexpr auto sb_stage = &stage_call<StageCall, sb_resolve, sb_reserve, sb_launch, int32_t>;
 
 int32_t sdrg_engine_sideband_device(sdrg_engine *e, const void *chan, int32_t n, void *out, int32_t *n_out) {
     return sb_stage(e, "chan", chan, out, n_out, false, n);
@@ -3017,14 +2993,17 @@ struct DetectorView {
     const char *f32_name;  // the out_format the resampler needs, as the header spells it
     bool set, f32;
     int max_in, cap, components;
+    int32_t (*resolve)(const sdrg_engine *, int32_t n, StageCall *);
+    int32_t (*reserve)(sdrg_engine *, const StageCall &);
+    int32_t (*launch)(sdrg_engine *, const StageCall &, const void *chan, void *out);
 };
 
 static DetectorView detector_view(const sdrg_engine *e, Detector det) {
     if (det == Detector::Sideband)
         return {"sideband", "SDRG_SIDEBAND_OUT_F32", e->sb.set, e->sb.cfg.out_format == SDRG_SIDEBAND_OUT_F32,
-                e->sb.cfg.max_in, e->sb.set ? e->sb.cap() : 0, e->sb.width()};
+                e->sb.cfg.max_in, e->sb.set ? e->sb.cap() : 0, e->sb.width(), sb_resolve, sb_reserve, sb_launch};
     return {"demod", "SDRG_DEMOD_OUT_F32", e->demod.set, e->demod.cfg.out_format == SDRG_DEMOD_OUT_F32,
-            e->demod.cfg.max_in, e->demod.set ? e->demod.cap() : 0, 1};
+            e->demod.cfg.max_in, e->demod.set ? e->demod.cap() : 0, 1, demod_resolve, demod_reserve, demod_launch};
 }
 
 // sdrg_engine_listen_host, and the four chain calls that are its masks without the AGC; with the sideband stage as the
@@ -3043,18 +3022,13 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     if (steps & ~(SDRG_LISTEN_SQUELCH | SDRG_LISTEN_AGC | SDRG_LISTEN_RESAMPLE))
         return fail(SDRG_E_INVALID, "listen: unknown bits in steps 0x%x", (unsigned)steps);
     const bool squelch = steps & SDRG_LISTEN_SQUELCH, agc = steps & SDRG_LISTEN_AGC, resample = steps & SDRG_LISTEN_RESAMPLE;
-    const bool sideband = det == Detector::Sideband;
     const DetectorView v = detector_view(e, det);
     int32_t rc = require_set(v.set, v.name);
     if (!rc && resample) rc = require_set(e->rs.set, "resample");
     if (!rc && squelch) rc = require_set(e->sq.set, "squelch");
     if (!rc && agc) rc = require_set(e->agc.set, "agc");
     DdcCall d;
-    BlockCall q;
-    BlockCall g;
-    DemodCall a;
-    SbCall s;
-    RsCall r;
+    StageCall q, g, a, r;  // the squelch's, the AGC's, the detector's and the resampler's
     if (!rc) rc = ddc_resolve(e, fmt, &d);
     if (rc) return rc;
     // the checks between the stages come before the later stages' own: after them those cannot refuse their n
@@ -3074,19 +3048,13 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
             return fail(SDRG_E_INVALID, "resample max_in %d smaller than the %s's row length %d", e->rs.cfg.max_in, v.name,
                         v.cap);
     }
-    if (sideband) {
-        rc = sb_resolve(e, d.n_out, &s);
-        s.in_stride = d.cap;  // the channel's rows are the DDC's
-    } else {
-        rc = demod_resolve(e, d.n_out, &a);
-        a.in_stride = d.cap;
-    }
-    const StageCall &det_call = sideband ? static_cast<const StageCall &>(s) : a;
-    if (!rc && resample) rc = rs_resolve(e, det_call.cap, det_call.n_out, &r);
+    rc = v.resolve(e, d.n_out, &a);
+    a.in_stride = d.cap;  // the channel's rows are the DDC's
+    if (!rc && resample) rc = rs_resolve(e, a.cap, a.n_out, &r);
     if (!rc && squelch) rc = sq_resolve(e, d.cap, d.n_out, sq_records, &q);
     if (!rc && agc) rc = agc_resolve(e, d.cap, d.n_out, agc_records, &g);
     if (rc) return rc;
-    const StageCall &last = resample ? static_cast<const StageCall &>(r) : det_call;
+    const StageCall &last = resample ? r : a;
     // a stage that is not in the mask was not resolved: its aux is null, and nothing is staged or copied for it
     const HostAux aux(last.out_bytes, &q, &g);
     DeviceScope dscope(e->device);
@@ -3094,17 +3062,17 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     rc = ddc_reserve(e, d);
     if (!rc && squelch) rc = sq_reserve(e, q);
     if (!rc && agc) rc = agc_reserve(e, g);
-    if (!rc) rc = sideband ? sb_reserve(e, s) : demod_reserve(e, a);
+    if (!rc) rc = v.reserve(e, a);
     if (!rc && resample) rc = rs_reserve(e, r);
     if (!rc) rc = ensure_device(&e->chain_chan, d.out_bytes / sizeof(float));
-    if (!rc && resample) rc = ensure_device(&e->chain_audio, det_call.out_bytes / sizeof(float));
+    if (!rc && resample) rc = ensure_device(&e->chain_audio, a.out_bytes / sizeof(float));
     if (!rc) rc = host_begin(e, iq, d.in_bytes, aux.staged_bytes());
     if (!rc) aux.stage(e);
     if (!rc) rc = ddc_launch(e, d, e->stream_in.p, e->chain_chan.p);
     if (!rc && squelch) rc = sq_launch(e, q, e->chain_chan.p, e->chain_chan.p);
     if (!rc && agc) rc = agc_launch(e, g, e->chain_chan.p, e->chain_chan.p);
     void *audio = resample ? (void *)e->chain_audio.p : (void *)e->stream_out.p;
-    if (!rc) rc = sideband ? sb_launch(e, s, e->chain_chan.p, audio) : demod_launch(e, a, e->chain_chan.p, audio);
+    if (!rc) rc = v.launch(e, a, e->chain_chan.p, audio);
     if (!rc && resample) rc = rs_launch(e, r, e->chain_audio.p, e->stream_out.p);
     if (!rc) rc = aux.finish(e, out, last.out_bytes);
     if (rc) return rc;

@@ -32,36 +32,17 @@ static_assert(RESAMPLE_TILE == RESAMPLE_THREADS, "one output per lane");
 constexpr int RESAMPLE_PITCH_OR = RESAMPLE_LAB_PITCH_OR;  // 1: the odd row pitch C | 1 (a lab build may set 0: the pitch C)
 
 typedef float rs_f2 __attribute__((ext_vector_type(2)));
-typedef short rs_s2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int16_t resample_s16(float o) {
-    return (int16_t)rintf(fminf(fmaxf(o, -1.0f), 1.0f) * 32767.0f);
-}
-
+// fir_tile.h's output trait for a value V: a float's, or for a pair its `pair`, made component by component
 template <typename V, int FMT>
-struct ResampleOut;
-template <>
-struct ResampleOut<float, SDRG_RESAMPLE_OUT_F32> {
-    typedef float type;
-    static __device__ __forceinline__ float make(float o) { return o; }
-};
-template <>
-struct ResampleOut<float, SDRG_RESAMPLE_OUT_S16> {
-    typedef int16_t type;
-    static __device__ __forceinline__ int16_t make(float o) { return resample_s16(o); }
-};
-template <>
-struct ResampleOut<rs_f2, SDRG_RESAMPLE_OUT_F32> {
-    typedef rs_f2 type;
-    static __device__ __forceinline__ rs_f2 make(rs_f2 o) { return o; }
-};
-template <>
-struct ResampleOut<rs_f2, SDRG_RESAMPLE_OUT_S16> {
-    typedef rs_s2 type;
-    static __device__ __forceinline__ rs_s2 make(rs_f2 o) {
-        rs_s2 r;
-        r.x = resample_s16(o.x);
-        r.y = resample_s16(o.y);
+struct ResampleOut : FirOut<FMT> {};
+template <int FMT>
+struct ResampleOut<rs_f2, FMT> {
+    typedef typename FirOut<FMT>::pair type;
+    static __device__ __forceinline__ type make(rs_f2 o) {
+        type r;
+        r.x = FirOut<FMT>::make(o.x);
+        r.y = FirOut<FMT>::make(o.y);
         return r;
     }
 };
@@ -76,14 +57,12 @@ __global__ __launch_bounds__(RESAMPLE_THREADS) void resample_kernel(const V *__r
     const int N = p.n, P = p.taps_per_phase, H = P - 1;
     const unsigned L = (unsigned)p.interp, M = (unsigned)p.decim;
     const V *x = in + (size_t)b * (size_t)p.in_stride;
-    const V *hist_old = p.fresh ? nullptr : reinterpret_cast<const V *>(p.hist_old) + (size_t)b * (size_t)H;
+    const V *hist_old = stream_history<V>(p.hist_old, b, H);
     out_t *orow = out + (size_t)b * (size_t)p.cap;
 
-    if ((int)blockIdx.x == p.n_tiles) {  // the new history (a call without samples keeps the old one) and the zero tail
-        if (N > 0)
-            carry_history<RESAMPLE_THREADS>(reinterpret_cast<V *>(p.hist_new) + (size_t)b * (size_t)H, hist_old, N, H, tid,
-                                            [&](int t) { return x[t]; });
-        for (int j = p.n_out + tid; j < p.cap; j += RESAMPLE_THREADS) orow[j] = out_t(0);
+    if ((int)blockIdx.x == p.n_tiles) {
+        close_stream<RESAMPLE_THREADS, 1>(p.hist_new, hist_old, b, N, H, orow, p.n_out, p.cap, tid,
+                                          [&](int t) { return x[t]; });
         return;
     }
 
@@ -169,7 +148,7 @@ hipError_t launch_resample(const void *in, int n_streams, const ResampleParams &
     // the last output's newest input is inside the frame: nothing is read past n
     if (p.n_out > 0 && (int64_t)p.q0 + ((int64_t)p.phi0 + (int64_t)(p.n_out - 1) * M) / L >= (int64_t)p.n)
         return hipErrorInvalidValue;
-    if (p.n > 0 && (!in || p.in_stride < p.n || (P > 1 && !p.hist_new) || (!p.fresh && P > 1 && !p.hist_old)))
+    if (p.n > 0 && (!in || p.in_stride < p.n || (P > 1 && !p.hist_new)))
         return hipErrorInvalidValue;
     // a value is loaded and stored whole: 4 or 8 bytes in, 2 to 8 bytes out
     const size_t in_align = sizeof(float) * (size_t)p.components;
@@ -177,7 +156,7 @@ hipError_t launch_resample(const void *in, int n_streams, const ResampleParams &
     if (reinterpret_cast<uintptr_t>(in) % in_align != 0 || reinterpret_cast<uintptr_t>(out) % out_align != 0 ||
         reinterpret_cast<uintptr_t>(p.hist_old) % in_align != 0 || reinterpret_cast<uintptr_t>(p.hist_new) % in_align != 0)
         return hipErrorInvalidValue;
-    p.n_tiles =(p.n_out + RESAMPLE_TILE - 1) / RESAMPLE_TILE;
+    p.n_tiles = (p.n_out + RESAMPLE_TILE - 1) / RESAMPLE_TILE;
     // LDS: P rows of min(tile, L) | 1 taps, then the widest window a tile has: its first and last outputs are
     // floor((tile - 1) M / L) or one more inputs apart, and the first reads P - 1 further back
     const int smp_at = (P * (std::min(RESAMPLE_TILE, L) | 1) + 3) & ~3;

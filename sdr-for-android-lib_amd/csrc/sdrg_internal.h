@@ -166,19 +166,28 @@ struct PeaksParams {
 hipError_t launch_peaks(const float *spectra, int n_streams, const PeaksParams &p, sdrg_peak *peaks,
                         sdrg_peaks_summary *summary, hipStream_t stream);
 
-// DDC stage (ddc.hip): per stream, out[j] = sum_k h[k] v[first + j decim - k], j in [0, n_out), v the frame's n raw
-// samples mixed by the NCO (phase inc * (g0_lo + t) at local index t) and, at t in [-(taps - 1), 0), hist_old
-// [n_streams][taps - 1][2] (nullptr: zeros).  Writes out [n_streams][cap][2] whole (zeros from n_out on), the mixed
-// samples at t in [n - (taps - 1), n) to hist_new, and the frame's phasors to `phasors` (scratch of n float2, all streams
-// share it).  tile, row, n_tiles and vec_ok are the launcher's.
-struct DdcParams {
+// What the stages in fir_tile.h's tile form share (DDC, demodulator's FIR, sideband): per stream, out[j] is a sum over
+// the values at t = first + j decim - k, k in [0, taps), j in [0, n_out); t in [0, n) is the call's frame and t in
+// [-(taps - 1), 0) the history hist_old [n_streams][taps - 1] values (nullptr: zeros, the call follows a restart).  The
+// call writes rows of cap outputs whole (zeros from n_out on) and the values at t in [n - (taps - 1), n) to hist_new.
+// The host fills all but the last line (engine.cpp: fir_tile_fill); fir_tile_plan (fir_tile.h) checks that and fills
+// the last line in the launcher.
+struct FirTileParams {
     int n, decim, taps, first, n_out, cap;
-    uint32_t inc, g0_lo;
-    const float *nco_tab;    // nco_tables() on the device
     const float *hist_old;
     float *hist_new;
+    int tile, row, n_tiles;
+};
+
+// DDC stage (ddc.hip): per stream, out[j] = sum_k h[k] v[first + j decim - k], v the frame's n raw samples mixed by the
+// NCO (phase inc * (g0_lo + t) at local index t); the history holds mixed samples, [taps - 1][2] per stream.  Writes
+// out [n_streams][cap][2] and the frame's phasors to `phasors` (scratch of n float2, all streams share it).  vec_ok is
+// the launcher's.
+struct DdcParams : FirTileParams {
+    uint32_t inc, g0_lo;
+    const float *nco_tab;    // nco_tables() on the device
     float *phasors;
-    int tile, row, n_tiles, vec_ok;
+    int vec_ok;
 };
 struct DdcTaps {
     float h[SDRG_DDC_MAX_TAPS];
@@ -189,19 +198,17 @@ hipError_t launch_ddc(const void *iq, int fmt, int n_streams, const DdcParams &p
 
 // Demodulator stage (demod.hip): per stream the n complex samples at chan + stream * in_stride (float2) through the
 // detector (mode, kf; the previous sample from state_old), the DC block and the de-emphasis (alpha, a; m and s from
-// state_old) in `scratch` [n_streams][scratch_stride] floats, then out[j] = gain * sum_k h[k] v[first + j decim - k],
-// j in [0, n_out), v at indices below 0 from hist_old [n_streams][taps - 1].  Writes out [n_streams][cap] whole (zeros
-// from n_out on, int16 or float by out_format), {wr, wi, m, s} per stream to state_new and the last taps - 1 values of
-// v to hist_new.  fresh: no previous sample, and state_old / hist_old read as zeros.  n = 0 writes out only.  tile, row
-// and n_tiles are the launcher's.
-struct DemodParams {
-    int n, in_stride, scratch_stride, decim, taps, first, n_out, cap;
+// state_old) in `scratch` [n_streams][scratch_stride] floats, then out[j] = gain * sum_k h[k] v[first + j decim - k];
+// the history holds values of v.  Writes out [n_streams][cap] (int16 or float by out_format), and, if n > 0, {wr, wi,
+// m, s} per stream to state_new and the history.  fresh: no previous sample, and state_old is not read (the FIR reads
+// hist_old, which is then nullptr).  n = 0 writes out only.
+struct DemodParams : FirTileParams {
+    int in_stride, scratch_stride;
     int mode, out_format, fresh;
     float kf, alpha, a, gain;
-    const float *state_old, *hist_old;
-    float *state_new, *hist_new;
+    const float *state_old;
+    float *state_new;
     float *scratch;
-    int tile, row, n_tiles;
 };
 struct DemodTaps {
     float h[SDRG_DEMOD_MAX_TAPS];
@@ -235,13 +242,13 @@ hipError_t launch_channelizer(const void *iq, int fmt, int n_streams, const Chan
 // Resampler stage (resample.hip): per stream and output j in [0, n_out), t = phi0 + j decim, q = q0 + t / interp,
 // phi = t mod interp, out[j] = gain * sum_k taps[phi][k] x[q - k], k in [0, taps_per_phase): x the n values at
 // in + stream * in_stride (floats, or float pairs at components 2) and, at indices in [-(taps_per_phase - 1), 0),
-// hist_old [n_streams][taps_per_phase - 1] values (fresh: zeros, not read).  Writes out [n_streams][cap] whole (zeros
+// hist_old [n_streams][taps_per_phase - 1] values (nullptr: zeros).  Writes out [n_streams][cap] whole (zeros
 // from n_out on; float or int16 by out_format, pairs at components 2) and, if n > 0, the values at
 // [n - (taps_per_phase - 1), n) to hist_new.  taps: [interp][taps_per_phase] floats in device memory.  n_tiles is the
 // launcher's.
 struct ResampleParams {
     int n, in_stride, interp, decim, taps_per_phase, q0, phi0, n_out, cap;
-    int components, out_format, fresh;
+    int components, out_format;
     float gain;
     const float *taps;
     const float *hist_old;
@@ -293,20 +300,17 @@ struct AgcParams : BlockParams {
 };
 hipError_t launch_agc(const float *chan, int n_streams, const AgcParams &p, float *out, hipStream_t stream);
 
-// Sideband stage (sideband.hip): per stream and output j in [0, n_out), A = sum_k cr[k] zr[first + j decim - k] and
-// Bm = sum_k ci[k] zi[first + j decim - k], z the n complex samples at chan + stream * in_stride (float2) and, at
-// indices in [-(taps - 1), 0), hist_old [n_streams][taps - 1][2] (fresh: zeros, not read); u = A - Bm, l = A + Bm.
-// Writes out [n_streams][cap] whole (u gain, l gain, or at mode BOTH the pairs of them; zeros from n_out on; float or
-// int16 by out_format) and, if n > 0, the samples at [n - (taps - 1), n) to hist_new.  taps_dev: [taps][2] floats
-// (cr, ci) in device memory.  tile, row, n_tiles, vec_ok and pair_ok are the launcher's.
-struct SidebandParams {
-    int n, in_stride, decim, taps, first, n_out, cap;
-    int mode, out_format, fresh;
+// Sideband stage (sideband.hip): per stream and output j, A = sum_k cr[k] zr[first + j decim - k] and Bm = sum_k ci[k]
+// zi[first + j decim - k], z the n complex samples at chan + stream * in_stride (float2); u = A - Bm, l = A + Bm.  The
+// history holds samples, [taps - 1][2] per stream.  Writes out [n_streams][cap] (u gain, l gain, or at mode BOTH the
+// pairs of them; float or int16 by out_format) and, if n > 0, the history.  taps_dev: [taps][2] floats (cr, ci) in
+// device memory.  vec_ok and pair_ok are the launcher's.
+struct SidebandParams : FirTileParams {
+    int in_stride;
+    int mode, out_format;
     float gain;
     const float *taps_dev;
-    const float *hist_old;
-    float *hist_new;
-    int tile, row, n_tiles, vec_ok, pair_ok;
+    int vec_ok, pair_ok;
 };
 int sideband_tile_outputs(int decim, int taps);  // outputs per workgroup
 hipError_t launch_sideband(const float *chan, int n_streams, const SidebandParams &p, void *out, hipStream_t stream);

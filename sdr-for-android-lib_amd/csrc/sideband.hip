@@ -6,8 +6,8 @@
 // and the history holds the last T - 1 samples of the stream.  The stage's own:
 //   the sums     Re(c * z) = cr zr - ci zi for the band-pass c = (cr, ci) around +fm, and cr zr + ci zi for its mirror
 //                around -fm.  So the two real sums A = sum cr[k] zr and Bm = sum ci[k] zi serve both sidebands: one
-//                packed multiply and one packed add per tap on the pair (polyphase_fir_pairwise), then u = A - Bm and
-//                l = A + Bm once per output.
+//                packed multiply and one packed add per tap on the pair (polyphase_fir with a tap per component),
+//                then u = A - Bm and l = A + Bm once per output.
 //   the taps     pairs (cr, ci) in device memory (2 x 511 floats do not fit a kernel's arguments beside the
 //                parameters), copied to LDS ahead of the window.
 //   the output   one value per lane and output, or the pair (u, l) interleaved; the gain and the quantisation follow.
@@ -40,64 +40,41 @@ struct SbSink {
     }
 };
 
-template <int FMT>
-struct SbOut;
-template <>
-struct SbOut<SDRG_SIDEBAND_OUT_F32> {
-    typedef float type;
-    typedef float2 pair;
-    static __device__ __forceinline__ float make(float o) { return o; }
-};
-template <>
-struct SbOut<SDRG_SIDEBAND_OUT_S16> {
-    typedef int16_t type;
-    typedef short2 pair;
-    static __device__ __forceinline__ int16_t make(float o) {
-        return (int16_t)rintf(fminf(fmaxf(o, -1.0f), 1.0f) * 32767.0f);
-    }
-};
-
 template <int MODE, int FMT>
 __global__ __launch_bounds__(SB_THREADS) void sideband_kernel(const float2 *__restrict__ chan, SidebandParams p,
                                                               void *__restrict__ out) {
-    typedef typename SbOut<FMT>::type out_t;
-    typedef typename SbOut<FMT>::pair pair_t;
+    typedef typename FirOut<FMT>::type out_t;
+    typedef typename FirOut<FMT>::pair pair_t;
     constexpr int W = MODE == SDRG_SIDEBAND_BOTH ? 2 : 1;  // values per output
     extern __shared__ __attribute__((aligned(16))) sb_f2 sb_lds[];
     const int tid = threadIdx.x, b = blockIdx.y;
     const int N = p.n, R = p.decim, T = p.taps, H = T - 1;
     const float2 *row = chan + (size_t)b * (size_t)p.in_stride;
-    const sb_f2 *hist_old = p.hist_old ? reinterpret_cast<const sb_f2 *>(p.hist_old) + (size_t)b * (size_t)H : nullptr;
+    const sb_f2 *hist_old = stream_history<sb_f2>(p.hist_old, b, H);
     out_t *orow = static_cast<out_t *>(out) + (size_t)b * (size_t)p.cap * W;
 
-    if ((int)blockIdx.x == p.n_tiles) {  // the new history (a call without samples keeps the old one) and the zero tail
-        if (N > 0) {
-            sb_f2 *hist_new = reinterpret_cast<sb_f2 *>(p.hist_new) + (size_t)b * (size_t)H;
-            carry_history<SB_THREADS>(hist_new, hist_old, N, H, tid, [&](int t) {
-                const float2 z = row[t];
-                return sb_f2{z.x, z.y};
-            });
-        }
-        for (int j = p.n_out * W + tid; j < p.cap * W; j += SB_THREADS) orow[j] = (out_t)0;
+    if ((int)blockIdx.x == p.n_tiles) {
+        close_stream<SB_THREADS, W>(p.hist_new, hist_old, b, N, H, orow, p.n_out, p.cap, tid,
+                                    [&](int t) {
+                                        const float2 z = row[t];
+                                        return sb_f2{z.x, z.y};
+                                    });
         return;
     }
 
-    const int j0 = (int)blockIdx.x * p.tile, nj = min(p.tile, p.n_out - j0);
-    const int w0 = p.first + j0 * R - H;  // local index of the window's first sample
-    const int count = (nj - 1) * R + T;   // samples in the window: w0 + count - 1 = the last output's newest sample
+    const FirWindow w(p, T);
     sb_f2 *tap_lds = sb_lds, *smp = sb_lds + SB_TAP_SLOTS;
-    const sb_f2 *taps = reinterpret_cast<const sb_f2 *>(p.taps_dev);
-    for (int i = tid; i < T; i += SB_THREADS) tap_lds[i] = taps[i];
-    stage_iq_window<SDRG_IQ_CF32, SB_THREADS>(reinterpret_cast<const char *>(row), hist_old, w0, count, H, p.vec_ok, tid,
-                                              SbSink{smp, R, p.row});
+    stage_taps<SB_THREADS>(tap_lds, reinterpret_cast<const sb_f2 *>(p.taps_dev), T, tid);
+    stage_iq_window<SDRG_IQ_CF32, SB_THREADS>(reinterpret_cast<const char *>(row), hist_old, w.w0, w.count, H, p.vec_ok,
+                                              tid, SbSink{smp, R, p.row});
     __syncthreads();
 
-    if (tid < nj) {
-        const sb_f2 acc = polyphase_fir_pairwise(tap_lds, smp, T, R, p.row, tid);
+    if (tid < w.nj) {
+        const sb_f2 acc = polyphase_fir(tap_lds, smp, T, R, p.row, tid);
         const float u = acc.x - acc.y, l = acc.x + acc.y;
-        const int j = j0 + tid;
+        const int j = w.j0 + tid;
         if constexpr (MODE == SDRG_SIDEBAND_BOTH) {
-            const out_t ou = SbOut<FMT>::make(u * p.gain), ol = SbOut<FMT>::make(l * p.gain);
+            const out_t ou = FirOut<FMT>::make(u * p.gain), ol = FirOut<FMT>::make(l * p.gain);
             if (p.pair_ok) {  // out aligned to a pair: one store
                 pair_t o;
                 o.x = ou, o.y = ol;
@@ -107,7 +84,7 @@ __global__ __launch_bounds__(SB_THREADS) void sideband_kernel(const float2 *__re
                 orow[2 * j + 1] = ol;
             }
         } else {
-            orow[j] = SbOut<FMT>::make((MODE == SDRG_SIDEBAND_UPPER ? u : l) * p.gain);
+            orow[j] = FirOut<FMT>::make((MODE == SDRG_SIDEBAND_UPPER ? u : l) * p.gain);
         }
     }
 }
@@ -125,21 +102,14 @@ int sideband_tile_outputs(int decim, int taps) { return fir_tile_outputs(SB_LDS_
 hipError_t launch_sideband(const float *chan, int n_streams, const SidebandParams &p0, void *out, hipStream_t stream) {
     if (n_streams <= 0) return hipSuccess;
     SidebandParams p = p0;
-    if (!out || !p.taps_dev || p.n < 0 || p.n > SDRG_SIDEBAND_MAX_IN || p.decim < 1 ||
-        p.decim > SDRG_SIDEBAND_MAX_DECIMATION || p.taps < 1 || p.taps > SDRG_SIDEBAND_MAX_TAPS || (p.taps & 1) == 0 ||
-        p.first < 0 || p.first >= p.decim || p.n_out < 0 || p.cap < 1 || p.n_out > p.cap ||
-        (p.n_out > 0 && (int64_t)p.first + (int64_t)(p.n_out - 1) * p.decim >= p.n) ||
+    if (!out || !p.taps_dev || p.n < 0 || p.n > SDRG_SIDEBAND_MAX_IN ||
         (p.mode != SDRG_SIDEBAND_UPPER && p.mode != SDRG_SIDEBAND_LOWER && p.mode != SDRG_SIDEBAND_BOTH) ||
         (p.out_format != SDRG_SIDEBAND_OUT_S16 && p.out_format != SDRG_SIDEBAND_OUT_F32) || n_streams > 65535)
         return hipErrorInvalidValue;
-    if (p.n > 0 && (!chan || p.in_stride < p.n || (p.taps > 1 && (!p.hist_new || (!p.fresh && !p.hist_old)))))
-        return hipErrorInvalidValue;
+    if (p.n > 0 && (!chan || p.in_stride < p.n || (p.taps > 1 && !p.hist_new))) return hipErrorInvalidValue;
     if (reinterpret_cast<uintptr_t>(chan) % sizeof(float) != 0) return hipErrorInvalidValue;
-    if (p.fresh) p.hist_old = nullptr;  // a restart passes the kernel no old history
-    p.tile = sideband_tile_outputs(p.decim, p.taps);
-    p.row = (p.tile - 1 + (p.taps + p.decim - 1) / p.decim) | 1;
-    p.n_tiles = (p.n_out + p.tile - 1) / p.tile;
-    if (p.tile < 1 || (int64_t)p.row * p.decim > SB_LDS_SAMPLES) return hipErrorInvalidValue;
+    if (!fir_tile_plan(&p, SB_LDS_SAMPLES, SB_THREADS, SDRG_SIDEBAND_MAX_DECIMATION, SDRG_SIDEBAND_MAX_TAPS))
+        return hipErrorInvalidValue;
     // rows of whole samples from a sample-aligned base: no sample straddles a 16-byte chunk
     p.vec_ok = reinterpret_cast<uintptr_t>(chan) % sizeof(float2) == 0;
     const size_t value = p.out_format == SDRG_SIDEBAND_OUT_F32 ? sizeof(float) : sizeof(int16_t);

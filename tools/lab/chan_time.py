@@ -8,6 +8,7 @@ yardstick / measured.  The last rows time what the library offered for 16 channe
 sdrg_engine_ddc_device calls with T = 127 and D = 16 on the same input, alternating with the (16, 8, 1) bank in three
 rounds.  Inputs: uniform noise over the format's whole range.  The lines go to stdout and, if named, to out.jsonl."""
 import ctypes
+import hashlib
 import json
 import os
 import sys
@@ -25,6 +26,12 @@ NAME = {sdrg.CS8: "CS8", sdrg.CS16: "CS16"}
 LIBRARY = os.path.basename(os.environ.get("SDRG_LIB_PATH", "product"))
 FS = 2_000_000
 results = []
+
+
+def sha256(t):
+    """The hash of a device tensor's bytes once the work on it is done: two libraries that compute the same agree on it."""
+    torch.cuda.synchronize()
+    return hashlib.sha256(t.cpu().numpy()).hexdigest()
 
 
 def emit(r):
@@ -95,7 +102,8 @@ class BankRun:
         r = dict(kind="channelizer", library=LIBRARY, streams=self.B, n=self.n, format=NAME[self.fmt], channels=self.M,
                  taps_per_channel=self.P, oversample=self.O, rows=self.rows, buffers=3, calls=K,
                  tile_outputs=sdrg.channelizer_tile_outputs(**self.cfg), us_per_launch=round(us, 2), in_bytes=in_bytes,
-                 out_bytes=out_bytes, read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1))
+                 out_bytes=out_bytes, read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1),
+                 out_sha256=sha256(self.out))
         if note:
             r["note"] = note
         results.append(r)
@@ -136,7 +144,7 @@ def bank_against_16_ddc_calls(B, n, fmt):
         us_ddc = timed(bank.work, sixteen, max(K // 8, 3), 2)
         results.append(dict(kind="ddc_x16", library=LIBRARY, streams=B, n=n, format=NAME[fmt], taps=127, decimation=16,
                             round=rnd, us_per_16_calls=round(us_ddc, 2), bank_us=round(us_bank, 2),
-                            ratio=round(us_ddc / us_bank, 2)))
+                            ratio=round(us_ddc / us_bank, 2), out_sha256=sha256(out)))
     eng.set_stream(None)
     eng.close()
     bank.close()

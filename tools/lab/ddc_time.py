@@ -6,6 +6,7 @@ sdrg_measure_hbm_copy's read + write rate (a float4 streaming copy) before and a
 shape is its input read plus its output write at the copy's rate (the mean of the two measurements); `share` is
 yardstick / measured.  Inputs: uniform noise over the format's whole range."""
 import ctypes
+import hashlib
 import json
 import os
 import sys
@@ -20,6 +21,12 @@ lib = sdrg.load()
 TORCH_DTYPE = {sdrg.CS8: torch.int8, sdrg.CS16: torch.int16}
 NAME = {sdrg.CS8: "CS8", sdrg.CS16: "CS16"}
 results = []
+
+
+def sha256(t):
+    """The hash of a device tensor's bytes once the work on it is done: two libraries that compute the same agree on it."""
+    torch.cuda.synchronize()
+    return hashlib.sha256(t.cpu().numpy()).hexdigest()
 
 
 def hbm():
@@ -69,7 +76,8 @@ def kernel_alone(B, n, fmt, taps, decimation, offset_hz=250_000.0):
     r = dict(kind="ddc", library=os.path.basename(os.environ.get("SDRG_LIB_PATH", "product")), streams=B, n=n,
              format=NAME[fmt], taps=taps, decimation=decimation, buffers=3, calls=K,
              tile_outputs=sdrg.ddc_tile_outputs(decimation, taps), us_per_launch=round(us, 2), in_bytes=in_bytes,
-             out_bytes=out_bytes, read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1))
+             out_bytes=out_bytes, read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1),
+             out_sha256=sha256(out))
     results.append(r)
     eng.set_stream(None)
     eng.close()

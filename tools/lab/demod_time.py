@@ -7,6 +7,7 @@ The yardstick of a shape is its input read plus its output write at the copy's r
 `share` is yardstick / measured.  Every shape is timed with both recurrences on and, for attribution, with both off (the
 recurrence kernel is then not launched: the difference is its time).  Inputs: uniform noise in (-1, 1), float output."""
 import ctypes
+import hashlib
 import json
 import os
 import sys
@@ -19,6 +20,12 @@ K = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 dev = torch.device("cuda", 0)
 lib = sdrg.load()
 results = []
+
+
+def sha256(t):
+    """The hash of a device tensor's bytes once the work on it is done: two libraries that compute the same agree on it."""
+    torch.cuda.synchronize()
+    return hashlib.sha256(t.cpu().numpy()).hexdigest()
 
 
 def hbm():
@@ -68,7 +75,7 @@ def kernel_alone(B, n, fc, R, T2, recurrences, mode=sdrg.DEMOD_FM):
     r = dict(kind="demod", library=os.path.basename(os.environ.get("SDRG_LIB_PATH", "product")), streams=B, n=n,
              mode="FM" if mode == sdrg.DEMOD_FM else "AM", decimation=R, taps=T2, recurrences=recurrences, buffers=3,
              calls=K, tile_outputs=tile, chunk=chunk, us_per_call=round(us, 2), in_bytes=in_bytes, out_bytes=out_bytes,
-             read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1))
+             read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1), out_sha256=sha256(out))
     results.append(r)
     eng.set_stream(None)
     eng.close()

@@ -6,6 +6,7 @@ launch), beside sdrg_measure_hbm_copy's read + write rate (a float4 streaming co
 The yardstick of a shape is its input read plus its output write at the copy's rate (the mean of the two measurements);
 `share` is yardstick / measured.  Inputs: uniform noise in (-1, 1), float output."""
 import ctypes
+import hashlib
 import json
 import os
 import sys
@@ -18,6 +19,12 @@ K = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 dev = torch.device("cuda", 0)
 lib = sdrg.load()
 results = []
+
+
+def sha256(t):
+    """The hash of a device tensor's bytes once the work on it is done: two libraries that compute the same agree on it."""
+    torch.cuda.synchronize()
+    return hashlib.sha256(t.cpu().numpy()).hexdigest()
 
 
 def hbm():
@@ -69,7 +76,7 @@ def kernel_alone(B, n, L, M, P, components):
                                                      gain=1.0, max_in=n),
              us_per_call=round(us, 2), in_bytes=in_bytes, out_bytes=out_bytes,
              macs=B * cap * P * components, gmacs_per_s=round(B * cap * P * components / (us * 1e-6) / 1e9, 1),
-             read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1))
+             read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1), out_sha256=sha256(out))
     results.append(r)
     eng.set_stream(None)
     eng.close()

@@ -8,6 +8,7 @@ yardstick / measured.  sdrg_engine_ddc_device is timed on the same CF32 rows wit
 two alternating over three rounds; each figure is the median of its three.  Inputs: uniform noise in (-1, 1), float
 output, UPPER and BOTH."""
 import ctypes
+import hashlib
 import json
 import os
 import statistics
@@ -24,6 +25,12 @@ FS = 2_000_000
 dev = torch.device("cuda", 0)
 lib = sdrg.load()
 results = []
+
+
+def sha256(t):
+    """The hash of a device tensor's bytes once the work on it is done: two libraries that compute the same agree on it."""
+    torch.cuda.synchronize()
+    return hashlib.sha256(t.cpu().numpy()).hexdigest()
 
 
 def hbm():
@@ -86,7 +93,7 @@ def shape(B, n, R, T, mode):
              us_rounds=[round(x, 2) for x in sb_us], ddc_us_per_call=round(d_us, 2),
              ddc_us_rounds=[round(x, 2) for x in ddc_us], sideband_over_ddc=round(us / d_us, 3), in_bytes=in_bytes,
              out_bytes=out_bytes, ddc_out_bytes=B * cap * 8,
-             read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1))
+             read_plus_write_gb_s=round((in_bytes + out_bytes) / (us * 1e-6) / 1e9, 1), out_sha256=sha256(out))
     results.append(r)
     eng.set_stream(None)
     eng.close()
