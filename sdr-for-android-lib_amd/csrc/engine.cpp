@@ -22,13 +22,13 @@
 #include <initializer_list>
 #include <map>
 #include <mutex>
-#include <set>
 #include <string>
-#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "decim_cursor.h"
 #include "design.h"
+#include "gather_ranges.h"
 #include "pulse_bank.h"
 #include "sdrg_internal.h"
 
@@ -122,28 +122,51 @@ struct PinnedVec {
     T &operator[](size_t i) { return p[i]; }
 };
 
-struct EvSet {
-    hipEvent_t t0 = nullptr, spec = nullptr, stats = nullptr, ssb0 = nullptr, ssb1 = nullptr, end = nullptr;
-    bool has_spec = false, has_stats = false, has_ssb = false, pending = false;
-    bool ssb_timed = false;  // ssb0 recorded: this call's SSB duration is measured from its own start marker
-    int64_t seq = -1;        // the call's number among ALL calls (pipelined SSB: interval to call seq - 1, if profiled)
-    bool stats_marked = false;  // `stats` recorded after the statistics (joined calls, whose `end` follows the join)
+// An event its owner creates where and with the flags it needs (once: a second create keeps the first) and that is
+// destroyed with its owner, in sdrg_engine_destroy with the engine's device current.  Reads as the hipEvent_t.
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    hipError_t create(unsigned flags) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }
+    operator hipEvent_t() const { return ev; }
 };
 
-// a device allocation of n values that only grows (ensure_device, ensure_device_keeping)
+// stream-to-stream ordering on one device: no timing, no system-scope fence
+constexpr unsigned EV_ORDER = hipEventDisableTiming | hipEventDisableSystemFence;
+
+// A device allocation of n values that only grows (ensure_device, ensure_device_keeping, upload_floats) and frees itself
+// with its owner (sdrg_engine_destroy: the engine's device current, its streams drained).  View says what p and n are
+// read as: an array, or the two halves of a stage's PingPong.
 template <typename T>
-struct DeviceBuf {
+struct DeviceArray {
     T *p = nullptr;
     size_t n = 0;
 };
 
-template <typename... Buf>  // DeviceBufs and PingPongs: freed (hipFree takes a null pointer) and empty again
-void release(Buf *...b) {
-    (((void)hipFree(b->p), *b = Buf{}), ...);
-}
+template <typename T, typename View = DeviceArray<T>>
+struct DeviceBuf : View {
+    DeviceBuf &operator=(DeviceBuf &&o) noexcept {  // of another buffer (copies are not made): what this held is freed
+        release();
+        std::swap<View>(*this, o);
+        return *this;
+    }
+    ~DeviceBuf() { release(); }
+    void release() {  // freed (hipFree takes a null pointer, and waits for the kernels that use it) and empty again
+        (void)hipFree(this->p);
+        static_cast<View &>(*this) = View{};
+    }
+};
+
+template <typename T>
+using DevicePingPong = DeviceBuf<T, PingPong<T>>;
 
 // The streaming stages' records: the configuration and whether one is set, the stream position, what the configuration
-// designs, and the device buffers, all of which free_buffers() releases (sdrg_engine_destroy calls the seven).
+// designs, and the device buffers.
 
 // DDC stage (sdrg_engine_set_ddc / ddc_device / ddc_host; ddc.hip)
 struct DdcStage {
@@ -151,7 +174,7 @@ struct DdcStage {
     bool set = false;
     DecimCursor cur;
     uint32_t fs = 0;        // the sample rate of the previous ddc call (0: none since set_ddc)
-    PingPong<float> hist;   // halves of [n_streams][taps - 1][2]: the mixed samples before the next frame
+    DevicePingPong<float> hist;  // halves of [n_streams][taps - 1][2]: the mixed samples before the next frame
     DeviceBuf<float> w;     // [N][2]: the phasors of the frame in flight, shared by the streams
     uint32_t taps_fs = 0;   // the sample rate taps was designed for (0: not designed)
     DdcTaps taps{};
@@ -160,7 +183,6 @@ struct DdcStage {
         cur.restart();
         fs = 0;
     }
-    void free_buffers() { release(&hist, &w); }
 };
 
 // demodulator stage (sdrg_engine_set_demod / demod_device / demod_host / ddc_demod_host; demod.hip)
@@ -170,11 +192,10 @@ struct DemodStage {
     DecimCursor cur;
     float kf = 0.0f, alpha = 0.0f, a = 0.0f;  // demod_design of cfg
     DemodTaps taps{};
-    PingPong<float> state;     // halves of {[n_streams][4]: wr, wi, m, s; [n_streams][T2 - 1]: v}
+    DevicePingPong<float> state;  // halves of {[n_streams][4]: wr, wi, m, s; [n_streams][T2 - 1]: v}
     DeviceBuf<float> scratch;  // [n_streams][max_in]: e, then v, of the call in flight
     int cap() const { return DecimCursor::cap(cfg.max_in, cfg.audio_decimation); }
     size_t half(int B) const { return (size_t)B * 4 + (size_t)B * (size_t)(cfg.audio_taps - 1); }
-    void free_buffers() { release(&state, &scratch); }
 };
 
 // channelizer stage (sdrg_engine_set_channelizer / channelizer_device / channelizer_host; channelizer.hip)
@@ -182,11 +203,10 @@ struct ChanStage {
     sdrg_channelizer_config cfg{};
     bool set = false;
     DecimCursor cur;
-    PingPong<float> hist;     // halves of [n_streams][L - 1][2]: the unpacked samples before the next frame
+    DevicePingPong<float> hist;  // halves of [n_streams][L - 1][2]: the unpacked samples before the next frame
     DeviceBuf<float> d_taps;  // [L] taps, then [CHAN_TWIDDLES][2]: written by set_channelizer
     int decim() const { return cfg.channels / cfg.oversample; }
     size_t half(int B) const { return (size_t)B * ((size_t)cfg.channels * (size_t)cfg.taps_per_channel - 1) * 2; }
-    void free_buffers() { release(&hist, &d_taps); }
 };
 
 // resampler stage (sdrg_engine_set_resample / resample_device / resample_host / ddc_demod_resample_host;
@@ -196,11 +216,10 @@ struct ResampleStage {
     bool set = false;
     ResampleCursor cur;
     std::vector<float> taps;  // resample_design of cfg: the prototype, [L P]
-    PingPong<float> hist;     // halves of [n_streams][P - 1][components]: the values before the next call's
+    DevicePingPong<float> hist;  // halves of [n_streams][P - 1][components]: the values before the next call's
     DeviceBuf<float> d_taps;  // the prototype in polyphase order [L][P]: written by set_resample
     int cap() const { return ResampleCursor::cap(cfg.max_in, cfg.interp, cfg.decim); }
     size_t half(int B) const { return (size_t)B * (size_t)(cfg.taps_per_phase - 1) * (size_t)cfg.components; }
-    void free_buffers() { release(&hist, &d_taps); }
 };
 
 // what a block stage (block_stage.h) keeps, whichever its law; Config has block, hang_blocks and max_in
@@ -209,10 +228,10 @@ struct BlockStage {
     Config cfg{};
     bool set = false;
     BlockCursor cur;
-    PingPong<float> state;  // halves of [n_streams][S + BLOCK_STATE_HEAD]: the law's four words, the block's powers so far
+    // halves of [n_streams][S + BLOCK_STATE_HEAD]: the law's four words, the block's powers so far
+    DevicePingPong<float> state;
     DeviceBuf<float> blk;   // [the most blocks a call completes][n_streams]: the blocks' statistics, then the law's words
     size_t half(int B) const { return (size_t)B * (size_t)(cfg.block + BLOCK_STATE_HEAD); }
-    void free_buffers() { release(&state, &blk); }
 };
 
 // squelch stage (sdrg_engine_set_squelch / squelch_device / squelch_host / ddc_squelch_demod_host; squelch.hip)
@@ -232,12 +251,194 @@ struct SidebandStage {
     bool set = false;
     DecimCursor cur;
     std::vector<float> cr, ci;  // sideband_design of cfg
-    PingPong<float> hist;       // halves of [n_streams][taps - 1][2]: the samples before the next call's
+    DevicePingPong<float> hist;  // halves of [n_streams][taps - 1][2]: the samples before the next call's
     DeviceBuf<float> d_taps;    // [taps][2]: (cr, ci), written by set_sideband
     int cap() const { return DecimCursor::cap(cfg.max_in, cfg.audio_decimation); }
     int width() const { return cfg.mode == SDRG_SIDEBAND_BOTH ? 2 : 1; }  // values per output
     size_t half(int B) const { return (size_t)B * (size_t)(cfg.taps - 1) * 2; }
-    void free_buffers() { release(&hist, &d_taps); }
+};
+
+// The stages that read spectra: the configuration and whether one is set, what the calls carry, the host calls' rows.
+
+// display stage (sdrg_engine_set_display / display_device / display_host; display.hip)
+struct DisplayStage {
+    sdrg_display_config cfg{};
+    bool set = false;
+    DeviceBuf<unsigned char> out;  // the host calls' rows
+};
+
+// integration stage (sdrg_engine_set_integration / integrate_device / integrate_host; integrate.hip)
+struct IntegrateStage {
+    sdrg_integrate_config cfg{};
+    bool set = false;
+    int64_t t = 0;      // integrate calls since the last reset
+    int32_t depth = 0;  // frames the last output integrates
+    bool seen = false;  // n, fs and fc hold the configuration at the previous integrate call
+    int n = 0;
+    int64_t fs = 0, fc = 0;
+    DeviceBuf<float> ring;  // MEAN / MAX: [period][integrate_slot_stride(n_streams * N)]
+    DeviceBuf<float> ema;   // EMA: y [n_streams][N]
+    DeviceBuf<float> out;   // integrate_host's rows (history, as the two above: ensure_device_keeping)
+    int out_n = 0;          // N of the rows the last integrate_host call left in out
+    void restart() { t = 0, depth = 0; }  // the integration history is forgotten
+};
+
+// peak table stage (sdrg_engine_set_peaks / peaks_device / peaks_host; peaks.hip)
+struct PeaksStage {
+    sdrg_peaks_config cfg{};
+    bool set = false;
+    DeviceBuf<unsigned char> out;  // the host calls' tables: [n_streams][max_peaks] sdrg_peak, then the summaries
+};
+
+// The records of what one call owes another.  Each owns its events: it creates them, and they go with it.
+
+template <size_t N>  // each handle on its own: a failed earlier attempt leaves no null behind in use
+int32_t create_events(Event (&evs)[N], unsigned flags) {
+    for (Event &ev : evs) HIP_TRY(ev.create(flags));
+    return SDRG_OK;
+}
+
+// sdrg_engine_gather runs on a stream of its own choosing after the outputs it reads; a later call that writes a buffer
+// still being gathered waits for the gather on the GPU first, so a caller rotating its output buffers never delays its
+// next call's kernels behind a gather.  Each gather's end sits in a ring; a range a gather read maps to that gather's
+// slot (gather_ranges.h), so a call that rewrites it waits for that gather only (waiting on the last gather instead
+// made call k + 3's spectrum wait for gather k + 2, and with it for call k + 2's asynchronous statistics).
+struct Gathers {
+    static constexpr int GRING = 8;
+    GatherRanges ranges;
+    Event ev_g[GRING];  // created at the slot's first gather
+    int64_t g_calls = 0;
+    hipEvent_t ev_gather = nullptr;       // the last gather's end, one of ev_g (wait_outputs)
+    hipStream_t s_last_gather = nullptr;  // the stream of the last gather
+
+    // a call is about to write [p, p + bytes) on `stream`: after the latest gather that reads any byte of it
+    int32_t wait_before_write(hipStream_t stream, const void *p, size_t bytes) const {
+        const int slot = ranges.latest(p, bytes);
+        if (slot >= 0) HIP_TRY(hipStreamWaitEvent(stream, ev_g[slot], 0));
+        return SDRG_OK;
+    }
+    void written(const void *p, size_t bytes) { ranges.retire(p, bytes); }  // and has enqueued that write
+
+    // A gather is about to run on s.  The focus staging buffer and RCCL's issue order: it follows the previous one
+    // even on another stream.
+    int32_t begin(hipStream_t s) {
+        HIP_TRY(ev_g[g_calls % GRING].create(EV_ORDER));
+        if (ev_gather && s != s_last_gather) HIP_TRY(hipStreamWaitEvent(s, ev_gather, 0));
+        s_last_gather = s;
+        return SDRG_OK;
+    }
+    // It is enqueued, and read these buffers, mapped to its slot; a slot re-recorded by a later gather still covers
+    // this one (gathers follow each other).
+    int32_t end(hipStream_t s, std::initializer_list<std::pair<const void *, size_t>> reads) {
+        const int slot = (int)(g_calls % GRING);
+        HIP_TRY(hipEventRecord(ev_g[slot], s));
+        ev_gather = ev_g[slot];
+        for (const auto &r : reads) ranges.record(r.first, r.second, slot, g_calls);
+        g_calls++;
+        return SDRG_OK;
+    }
+};
+
+// SDRG_PIPELINE_STATS_ASYNC: a pipelined call's statistics (+ spectral pulse detector) run on s_stats after its
+// spectrum, beside the next call's spectrum.  The engine keeps the spectra a call's statistics read intact: a call
+// that writes the same spectra buffer as the call before waits (on the GPU) for that call's statistics, and the host
+// waits for the statistics of the call two before (so a caller rotating two or more spectra buffers never waits on
+// the GPU).
+struct AsyncStats {
+    static constexpr int SA_RING = 3;
+    Event ev_spec_done;               // after a call's spectrum on its stream, waited by s_stats
+    Event ev_end[SA_RING];            // end of the statistics of call (calls - k) at slot % SA_RING
+    const float *spec[SA_RING] = {};  // the spectra buffer each of those calls' statistics read
+    bool live[SA_RING] = {};
+    int64_t calls = 0;
+    hipEvent_t last_end = nullptr;  // the last asynchronous statistics (signal_strength, wait_outputs, gather)
+
+    int32_t create() {  // sdrg_engine_set_pipelining with the bit
+        HIP_TRY(ev_spec_done.create(EV_ORDER));
+        return create_events(ev_end, EV_ORDER);
+    }
+    // Before a spectrum into `to` on sm, of a call whose own statistics will run on s_stats (`async`) or on sm: the
+    // host's wait, and the GPU's.
+    int32_t before_spectrum(hipStream_t sm, const float *to, bool async) const {
+        if (calls >= 2 && live[(calls - 2) % SA_RING]) HIP_TRY(hipEventSynchronize(ev_end[(calls - 2) % SA_RING]));
+        const int pv = (int)((calls + SA_RING - 1) % SA_RING);
+        if (calls >= 1 && live[pv] && (spec[pv] == to || !async)) HIP_TRY(hipStreamWaitEvent(sm, ev_end[pv], 0));
+        return SDRG_OK;
+    }
+    int32_t after_stats(hipStream_t st, const float *from) {  // the statistics of `from` are enqueued on st
+        const int k = (int)(calls % SA_RING);
+        HIP_TRY(hipEventRecord(ev_end[k], st));
+        spec[k] = from;
+        live[k] = true;
+        calls++;
+        last_end = ev_end[k];
+        return SDRG_OK;
+    }
+    // a write of count floats at dst on `stream` (in-place integration of a call's own spectra): after the statistics
+    // that may still read any of them
+    int32_t wait_before_write(hipStream_t stream, const float *dst, size_t count) const {
+        for (int k = 0; k < SA_RING; k++)
+            if (live[k] && spec[k] < dst + count && dst < spec[k] + count)
+                HIP_TRY(hipStreamWaitEvent(stream, ev_end[k], 0));
+        return SDRG_OK;
+    }
+};
+
+// The audio pulse detector (AudioPulseDetector::process after processSSB_opt, ssb_processor.cpp:109) runs on s_ap after
+// the call's SSB pipeline, so the SSB stream (the pipelined step's critical path) carries the SSB kernels alone.  Call
+// k's front end (inside its SSB kernel) writes energy-frame set k % NEW_SETS; before it does, the host waits for the
+// detector of call k - NEW_SETS, which read that set.
+struct AudioDetect {
+    Event ev_end[sdrg_pulse_bank::NEW_SETS];  // created with the engine
+    bool live[sdrg_pulse_bank::NEW_SETS] = {};
+    int64_t calls = 0;
+    hipEvent_t last_end = nullptr;  // the last detector (outputs, joins)
+
+    int set() const { return (int)(calls % sdrg_pulse_bank::NEW_SETS); }  // what the next call with the stage writes
+    int32_t detected(hipStream_t s_ap) {  // that call's detector is enqueued on s_ap
+        const int k = set();
+        HIP_TRY(hipEventRecord(ev_end[k], s_ap));
+        live[k] = true;
+        last_end = ev_end[k];
+        calls++;
+        return SDRG_OK;
+    }
+};
+
+struct EvSet {
+    Event t0, spec, stats, ssb0, ssb1, end;
+    bool has_spec = false, has_stats = false, has_ssb = false, pending = false;
+    bool ssb_timed = false;  // ssb0 recorded: this call's SSB duration is measured from its own start marker
+    int64_t seq = -1;        // the call's number among ALL calls (pipelined SSB: interval to call seq - 1, if profiled)
+    bool stats_marked = false;  // `stats` recorded after the statistics (joined calls, whose `end` follows the join)
+};
+
+// profiling: a ring of event sets so consecutive calls are timed without host synchronisation
+struct Profiler {
+    static constexpr int RING = 64;
+    EvSet ring[RING];
+    int next = 0, last = -1;
+    bool on = false;
+    sdrg_timings last_timings{};
+    double sum_spec = 0, sum_stats = 0, sum_ssb = 0, sum_total = 0;
+    int n_acc = 0, n_ssb = 0;
+    int64_t seq_reset = 0;  // seq of the first call after the last reset of the timing statistics
+
+    int32_t create();  // sdrg_engine_set_profiling(1): the first makes the events
+    int32_t fold_slot(int slot);
+    int32_t fold_all();
+    EvSet *begin(int64_t seq, bool do_spec, bool do_stats, bool do_ssb, bool early_fork, bool stats_async);
+    void commit() {  // the call of begin()'s slot is enqueued
+        ring[next].pending = true;
+        last = next;
+        next = (next + 1) % RING;
+    }
+    void reset(int64_t calls_total) {  // after fold_all
+        sum_spec = sum_stats = sum_ssb = sum_total = 0;
+        n_acc = n_ssb = 0;
+        // a pipelined call's SSB interval starts at the previous call's end marker: the window's first call has none
+        seq_reset = calls_total;
+    }
 };
 
 }  // namespace
@@ -257,90 +458,47 @@ struct sdrg_engine {
     // spectrum's; s_spec is forked from / joined into s_main per call like the SSB stream
     hipStream_t s_spec = nullptr;
     int spec_cus = 0;
-    hipEvent_t ev_fork_spec = nullptr, ev_join_spec = nullptr;
+    Event ev_fork_spec, ev_join_spec;
     hipStream_t s_own = nullptr;  // the engine's own main stream (s_main is it, or the caller's via set_stream)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Event ev_fork, ev_join;
     // input release: recorded after the last kernel of a call that reads its iq buffer on each stream (the
     // spectrum on s_main, the SSB pipeline on s_ssb); sdrg_engine_input_released / _wait_input_released
-    hipEvent_t ev_in_main = nullptr, ev_in_ssb = nullptr;
+    Event ev_in_main, ev_in_ssb;
     // the markers the last call recorded after its iq readers (ev_in_* or the profiling ring's events)
     hipEvent_t last_in_main = nullptr, last_in_ssb = nullptr;
-    // profiling: a ring of event sets so consecutive calls are timed without host synchronisation
-    static constexpr int RING = 64;
-    EvSet ring[RING];
-    bool ring_created = false;
-    int ring_next = 0, ring_last = -1;
-    bool profiling = false;
-    sdrg_timings last_timings{};
-    double sum_spec = 0, sum_stats = 0, sum_ssb = 0, sum_total = 0;
-    int n_acc = 0, n_ssb = 0;
+    Profiler prof;
     int64_t calls_total = 0;  // every enqueue, profiled or not: two calls are consecutive only if their seqs are
-    int64_t seq_reset = 0;    // seq of the first call after the last reset of the timing statistics
 
     // device state / buffers
-    StatsState *d_stats = nullptr;
-    SsbStreamState *d_ssb = nullptr;
-    float *d_twiddles = nullptr;
-    int tw_n = 0;
-    float *d_taps = nullptr;
-    int *d_chunk_table = nullptr;     // per SSB pipeline chunk: FIR outputs overlapping / completed
-    size_t chunk_table_elems = 0;
-    float *d_ssb_scratch = nullptr;
-    size_t ssb_scratch_elems = 0;
-    float *d_spec_scratch = nullptr;
-    size_t spec_scratch_elems = 0;
-    float *d_focus_stage = nullptr;   // sdrg_engine_gather: the focus-window slices, packed for ncclGather
-    size_t focus_stage_elems = 0;
-    // sdrg_engine_gather runs on a stream of its own after the outputs it reads; a later call that writes a buffer
-    // still being gathered (same pointer) waits for the gather on the GPU first, so a caller rotating its output
-    // buffers never delays its next call's kernels behind a gather
+    DeviceBuf<StatsState> d_stats;
+    DeviceBuf<SsbStreamState> d_ssb;
+    DeviceBuf<float> d_twiddles;
+    int tw_n = 0;  // the N d_twiddles holds the table of
+    DeviceBuf<float> d_taps;
+    DeviceBuf<int> d_chunk_table;  // per SSB pipeline chunk: FIR outputs overlapping / completed
+    DeviceBuf<float> d_ssb_scratch;
+    DeviceBuf<float> d_spec_scratch;
+    DeviceBuf<float> d_focus_stage;  // sdrg_engine_gather: the focus-window slices, packed for ncclGather
     bool last_async_stats = false;  // the last call with a statistics stage ran it on s_stats
     bool lab_ssb_first = false;     // lab SDRG_SSB_FIRST: host launch order of a forked SSB stage
     bool lab_stats_cus = false;     // lab SDRG_STATS_CUS: s_stats and s_spec on disjoint CU masks
-    hipStream_t s_gather = nullptr;   // lab (SDRG_GATHER_STREAM=1): the gathers on a stream of their own
-    hipStream_t s_last_gather = nullptr;  // the stream of the last gather
-    hipEvent_t ev_gather = nullptr;  // the last gather's end (wait_outputs, synchronize)
-    // each gather's end in a ring; a buffer a gather read maps to that gather's slot, so a call that rewrites it waits
-    // for that gather only (waiting on the last gather instead made call k + 3's spectrum wait for gather k + 2, and
-    // with it for call k + 2's asynchronous statistics)
-    static constexpr int GRING = 8;
-    hipEvent_t ev_g[GRING] = {};
-    int64_t g_calls = 0;
-    struct GBuf {
-        uintptr_t lo, hi;  // the byte range [lo, hi) a gather reads
-        int slot;
-        int64_t seq;       // g_calls of that gather (gathers run in call order: the latest covers the earlier ones)
-    };
-    std::vector<GBuf> g_bufs;  // byte ranges read by gathers no later call has yet waited for
-    // the event of the latest gather that reads any byte of [p, p + bytes) (ranges, not base pointers: an output
-    // written at an offset into, or as a slice of, a gathered allocation still waits)
-    hipEvent_t gathering(const void *p, size_t bytes) const {
-        if (!p || !bytes) return nullptr;
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(p), hi = lo + bytes;
-        const GBuf *best = nullptr;
-        for (const GBuf &g : g_bufs)
-            if (g.lo < hi && lo < g.hi && (!best || g.seq > best->seq)) best = &g;
-        return best ? ev_g[best->slot] : nullptr;
-    }
-    float *d_fft_scratch = nullptr;   // four-step intermediate (N > 16384)
-    size_t fft_scratch_elems = 0;
-    sdrg_frame_record *d_rec_scratch = nullptr;
-    float *d_pool = nullptr;          // statistics' pooled bins beyond the LDS bound (wide focus, N > 65536)
-    size_t pool_elems = 0;
+    hipStream_t s_gather = nullptr;  // lab (SDRG_GATHER_STREAM=1): the gathers on a stream of their own
+    Gathers gathers;
+    DeviceBuf<float> d_fft_scratch;  // four-step intermediate (N > 16384)
+    DeviceBuf<sdrg_frame_record> d_rec_scratch;
+    DeviceBuf<float> d_pool;  // statistics' pooled bins beyond the LDS bound (wide focus, N > 65536)
     // host-path staging
-    void *d_iq_stage = nullptr;
-    size_t iq_stage_bytes = 0;
-    float *d_spec_stage = nullptr;
-    size_t spec_stage_elems = 0;
+    DeviceBuf<char> d_iq_stage;
+    DeviceBuf<float> d_spec_stage;
+    int host_spec_n = 0;  // N of the spectra the last process_host call with SPECTRUM left in d_spec_stage
     // The caller's spectra, [n_streams][N], of signal_strength_host, display_host, integrate_host and peaks_host.
     // Not d_spec_stage: that one carries each stream's never-written bin N-1 of an odd N from one process_host call
     // to the next (fft_process.cpp:92-97), which a caller's spectra must not replace.  One buffer serves the four:
     // each of them waits on s_main before it returns, so no two uses overlap, and a call that fails after its copy
     // was enqueued leaves that copy ordered on s_main before whatever the next call enqueues there.
     DeviceBuf<float> spec_in;
-    sdrg_frame_record *d_rec_stage = nullptr;
-    int16_t *d_pcm_stage = nullptr;
-    size_t pcm_stage_elems = 0;
+    DeviceBuf<sdrg_frame_record> d_rec_stage;
+    DeviceBuf<int16_t> d_pcm_stage;
     PinnedVec<float> h_spec;
     PinnedVec<sdrg_frame_record> h_rec;
     PinnedVec<int16_t> h_pcm;
@@ -354,64 +512,29 @@ struct sdrg_engine {
     bool cf_changed_pending = false;
     bool pipelined = false;  // sdrg_engine_set_pipelining: no join of the SSB stream per call
     bool inputs_ready = false;  // SDRG_PIPELINE_INPUTS_READY: no fork wait on the main stream either
-    // SDRG_PIPELINE_STATS_ASYNC: a pipelined call's statistics (+ spectral pulse detector) run on s_stats after its
-    // spectrum, beside the next call's spectrum.  The engine keeps the spectra a call's statistics read intact:
-    // a call that writes the same spectra buffer as the call before waits (on the GPU) for that call's statistics,
-    // and the host waits for the statistics of the call two before (so a caller rotating two or more spectra
-    // buffers never waits on the GPU).
-    bool stats_async = false;
+    bool stats_async = false;  // SDRG_PIPELINE_STATS_ASYNC (AsyncStats)
     hipStream_t s_stats = nullptr;
-    hipEvent_t ev_spec_done = nullptr;  // after a call's spectrum on s_main, waited by s_stats
-    static constexpr int SA_RING = 3;
-    hipEvent_t ev_stats_end[SA_RING] = {};  // end of the statistics of call (sa_calls - k) at slot % SA_RING
-    const float *sa_spec[SA_RING] = {};     // the spectra buffer each of those calls' statistics read
-    bool sa_live[SA_RING] = {};
-    int64_t sa_calls = 0;
-    hipEvent_t last_stats_end = nullptr;    // the last asynchronous statistics (wait_outputs, synchronize)
-    // the audio pulse detector (AudioPulseDetector::process after processSSB_opt, ssb_processor.cpp:109) runs on s_ap
-    // after the call's SSB pipeline, so the SSB stream (the pipelined step's critical path) carries the SSB kernels
-    // alone.  Call k's front end (inside its SSB kernel) writes energy-frame set k % NEW_SETS; before it does, the host
-    // waits for the detector of call k - NEW_SETS, which read that set.
-    hipStream_t s_ap = nullptr;
-    hipEvent_t ev_ap_end[sdrg_pulse_bank::NEW_SETS] = {};
-    bool ap_live[sdrg_pulse_bank::NEW_SETS] = {};
-    int64_t ap_calls = 0;
-    hipEvent_t last_ap_end = nullptr;       // the last detector (outputs, joins)
+    AsyncStats sa;
+    hipStream_t s_ap = nullptr;  // the audio pulse detector's (AudioDetect)
+    AudioDetect ap;
     // NCO/short-FIR SSB variant (sdrg_engine_set_ssb_variant; a build extension, off by default)
     double nco_hz = 0.0;
     int fir_taps = 0;            // 0: the reference's 255
     uint32_t nco_phase = 0;      // phase of the next call's first sample (advances by inc * samp_count)
-    float *d_nco_tab = nullptr;  // nco_tables(), uploaded once
+    DeviceBuf<float> d_nco_tab;  // nco_tables(), uploaded once
     int upper = 1;
     bool has_cbs = false;
     sdrg_callbacks cbs{};
-    // display stage (sdrg_engine_set_display / display_device / display_host; display.hip)
-    sdrg_display_config disp{};
-    bool disp_set = false;
-    DeviceBuf<unsigned char> disp_out;  // the host calls' rows
-    int host_spec_n = 0;          // N of the spectra the last process_host call with SPECTRUM left in d_spec_stage
     // The device calls of the stages below (display, integration, peaks, DDC, demodulator, channelizer, resampler,
     // squelch, AGC, sideband) write their outputs on s_main after the last process call's end marker, which is all a
-    // stream other than s_main follows.  Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs on s_main for that stream
-    // to wait on.
-    hipEvent_t ev_outputs = nullptr;
+    // stream other than s_main follows.  Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs
+    // on s_main for that stream to wait on.
+    Event ev_outputs;  // created at the first such wait
     bool outputs_unmarked = false;
-    // integration stage (sdrg_engine_set_integration / integrate_device / integrate_host; integrate.hip)
-    sdrg_integrate_config integ{};
-    bool integ_set = false;
-    int64_t integ_t = 0;       // integrate calls since the last reset
-    int32_t integ_depth = 0;   // frames the last output integrates
-    bool integ_seen = false;   // integ_n / _fs / _fc hold the configuration at the previous integrate call
-    int integ_n = 0;
-    int64_t integ_fs = 0, integ_fc = 0;
-    DeviceBuf<float> integ_ring;  // MEAN / MAX: [period][integrate_slot_stride(n_streams * N)]
-    DeviceBuf<float> integ_ema;   // EMA: y [n_streams][N]
-    DeviceBuf<float> integ_out;   // integrate_host's rows (history, as the two above: ensure_device_keeping)
-    int integ_out_n = 0;          // N of the rows the last integrate_host call left in integ_out
-    // peak table stage (sdrg_engine_set_peaks / peaks_device / peaks_host; peaks.hip)
-    sdrg_peaks_config peaks{};
-    bool peaks_set = false;
-    DeviceBuf<unsigned char> peaks_out;  // the host calls' tables: [n_streams][max_peaks] sdrg_peak, then the summaries
+    // the stages that read spectra (DisplayStage, IntegrateStage, PeaksStage above)
+    DisplayStage disp;
+    IntegrateStage integ;
+    PeaksStage peaks;
     // the streaming stages (DdcStage ... AgcStage above)
     DdcStage ddc;
     DemodStage demod;
@@ -470,27 +593,21 @@ hipError_t memset_sync(void *p, int v, size_t bytes) {
 
 // Growth of a buffer that holds nothing across calls (staging, outputs, scratch): the old allocation is freed first,
 // so the two never exist together, and a call that cannot have the new one leaves the buffer empty
-template <typename T>
-int32_t ensure_device(T **p, size_t *have, size_t need, bool zero = false) {
-    if (*have >= need && *p) return SDRG_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
+// `zero`: filled with zeros when allocated or regrown, and only then.
+template <typename T, typename View>
+int32_t ensure_device(DeviceBuf<T, View> *b, size_t need, bool zero = false) {
+    if (b->n >= need && b->p) return SDRG_OK;
+    b->release();
     if (need == 0) return SDRG_OK;
-    const hipError_t er = hipMalloc(reinterpret_cast<void **>(p), need * sizeof(T));
+    const hipError_t er = hipMalloc(reinterpret_cast<void **>(&b->p), need * sizeof(T));
     if (er == hipErrorOutOfMemory) {  // for every growth policy: each allocates here
         (void)hipGetLastError();
         return fail(SDRG_E_NOMEM, "hipMalloc of %zu bytes failed", need * sizeof(T));
     }
     HIP_TRY(er);
-    if (zero) HIP_TRY(memset_sync(*p, 0, need * sizeof(T)));
-    *have = need;
+    if (zero) HIP_TRY(memset_sync(b->p, 0, need * sizeof(T)));
+    b->n = need;
     return SDRG_OK;
-}
-
-template <typename T>
-int32_t ensure_device(DeviceBuf<T> *b, size_t need) {
-    return ensure_device(&b->p, &b->n, need);
 }
 
 // Growth of a buffer that holds history (the integration stage's ring, EMA rows and output rows): the new buffer
@@ -501,16 +618,15 @@ int32_t ensure_device_keeping(DeviceBuf<T> *b, size_t need) {
     DeviceBuf<T> grown;
     const int32_t rc = ensure_device(&grown, need);
     if (rc) return rc;
-    if (b->p) (void)hipFree(b->p);  // synchronises with the kernels that use it
-    *b = grown;
+    *b = std::move(grown);  // frees the old one, which synchronises with the kernels that use it
     return SDRG_OK;
 }
 
 // Both halves of a decimating stage's ping-pong buffer.  Only another configuration asks for more, and setting one
 // restarts the streams: nothing to keep.  Never empty: a launcher wants a pointer even to a history of no values.
 template <typename T>
-int32_t ensure_device(PingPong<T> *b, size_t half_elems) {
-    return ensure_device(&b->p, &b->n, std::max<size_t>(2 * half_elems, 2));
+int32_t ensure_halves(DevicePingPong<T> *b, size_t half_elems) {
+    return ensure_device(b, std::max<size_t>(2 * half_elems, 2));
 }
 
 // The two ends of a streaming stage's or a chain's host call on the main stream: the caller's `in` into stream_in, with
@@ -531,31 +647,25 @@ int32_t host_end(sdrg_engine *e, void *out, size_t out_bytes) {
     return SDRG_OK;
 }
 
-// These host floats become the device buffer *d (`what` taps: a stage's name, for the message).  They go into a buffer
-// of their own, so a failed copy leaves the old one in force; the old one is freed afterwards, which waits for the
-// calls that still read it.
+// These host floats become the device buffer *d (`what`: whose they are, for the message).  They go into a buffer of
+// their own, so a failed copy leaves the old one in force; the old one is freed afterwards, which waits for the calls
+// that still read it.
 int32_t upload_floats(DeviceBuf<float> *d, const std::vector<float> &host, const char *what) {
     DeviceBuf<float> fresh;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&fresh.p), sizeof(float) * host.size()));
+    const int32_t rc = ensure_device(&fresh, host.size());
+    if (rc) return rc;
     const hipError_t er = hipMemcpy(fresh.p, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
-    if (er != hipSuccess) {
-        (void)hipFree(fresh.p);
-        return fail(SDRG_E_HIP, "%s taps upload: %s", what, hipGetErrorString(er));
-    }
-    fresh.n = host.size();
-    release(d);
-    *d = fresh;
+    if (er != hipSuccess) return fail(SDRG_E_HIP, "%s upload: %s", what, hipGetErrorString(er));
+    *d = std::move(fresh);
     return SDRG_OK;
 }
 
 // nco_tables() on the device, uploaded once: the SSB variant's mixer and the DDC's read the same table
 int32_t ensure_nco_table(sdrg_engine *e) {
-    if (e->d_nco_tab) return SDRG_OK;
+    if (e->d_nco_tab.p) return SDRG_OK;
     std::vector<float> tab(4096);
     nco_tables(tab.data());
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_nco_tab), sizeof(float) * tab.size()));
-    HIP_TRY(hipMemcpy(e->d_nco_tab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    return SDRG_OK;
+    return upload_floats(&e->d_nco_tab, tab, "NCO table");
 }
 
 // ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband -------------------------
@@ -683,7 +793,7 @@ static int32_t block_resolve(const sdrg_engine *e, const Stage &s, const char *s
 
 template <typename Stage>
 static int32_t block_reserve(sdrg_engine *e, Stage *s) {
-    const int32_t rc = ensure_device(&s->state, s->half(e->n_streams));
+    const int32_t rc = ensure_halves(&s->state, s->half(e->n_streams));
     const size_t blocks = (size_t)BlockCursor::cap(s->cfg.max_in, s->cfg.block);
     return rc ? rc : ensure_device(&s->blk, (size_t)e->n_streams * blocks);
 }
@@ -717,23 +827,23 @@ static int32_t block_launch(sdrg_engine *e, Stage *s, const StageCall &c, Params
 // to spec_in is owed, which spectra_round_trip makes.
 int32_t resolve_spectra(const sdrg_engine *e, const float *spectra, int n, const float **d_rows) {
     if (spectra) return SDRG_OK;
-    if (!e->d_spec_stage || e->host_spec_n == 0)
+    if (!e->d_spec_stage.p || e->host_spec_n == 0)
         return fail(SDRG_E_INVALID, "no spectra on the device: no sdrg_engine_process_host call with SDRG_STAGE_SPECTRUM yet");
     if (e->host_spec_n != n)
         return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the spectra on the device were computed",
                     e->host_spec_n, n);
-    *d_rows = e->d_spec_stage;
+    *d_rows = e->d_spec_stage.p;
     return SDRG_OK;
 }
 
 // The rows the last integrate_host call left on the device, if they are N = n bins wide
 int32_t resolve_integrated(const sdrg_engine *e, int n, const float **d_rows) {
-    if (!e->integ_out.p || e->integ_out_n == 0)
+    if (!e->integ.out.p || e->integ.out_n == 0)
         return fail(SDRG_E_INVALID, "no integrated rows on the device: no sdrg_engine_integrate_host call yet");
-    if (e->integ_out_n != n)
+    if (e->integ.out_n != n)
         return fail(SDRG_E_INVALID, "samples_per_reading changed (%d -> %d) since the rows on the device were integrated",
-                    e->integ_out_n, n);
-    *d_rows = e->integ_out.p;
+                    e->integ.out_n, n);
+    *d_rows = e->integ.out.p;
     return SDRG_OK;
 }
 
@@ -760,14 +870,14 @@ int32_t spectra_round_trip(sdrg_engine *e, const float *spectra, const float *d_
 }
 
 int32_t upload_twiddles(sdrg_engine *e, int n) {
-    if (e->tw_n == n && e->d_twiddles) return SDRG_OK;
+    if (e->tw_n == n && e->d_twiddles.p) return SDRG_OK;
     std::vector<float> tw(spectrum_twiddle_floats(n));
     spectrum_fill_twiddles(n, tw.data());
-    if (e->d_twiddles) (void)hipFree(e->d_twiddles);
-    e->d_twiddles = nullptr;
+    e->d_twiddles.release();  // whatever its size: the free waits for the spectra that read the old table
     e->tw_n = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_twiddles), tw.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(e->d_twiddles, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
+    const int32_t rc = ensure_device(&e->d_twiddles, tw.size());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(e->d_twiddles.p, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
     e->tw_n = n;
     return SDRG_OK;
 }
@@ -777,8 +887,8 @@ int64_t ssb_frozen_or(const sdrg_engine *e) {
 }
 
 // Resolve one ring slot's events into timings and add them to the running sums.
-int32_t fold_slot(sdrg_engine *e, int slot) {
-    EvSet &ev = e->ring[slot];
+int32_t Profiler::fold_slot(int slot) {
+    EvSet &ev = ring[slot];
     if (!ev.pending) return SDRG_OK;
     HIP_TRY(hipEventSynchronize(ev.end));
     sdrg_timings t{};
@@ -802,9 +912,9 @@ int32_t fold_slot(sdrg_engine *e, int slot) {
     } else if (ev.has_ssb) {
         // pipelined: no start marker (it would sit on the SSB stream, the step's critical path); the call's SSB
         // stream time is the interval from the previous call's SSB end marker to its own.  The previous slot still
-        // holds that marker while its seq is this call's - 1 (enqueue folds a slot's successor before reusing it).
-        const EvSet &pv = e->ring[(slot + sdrg_engine::RING - 1) % sdrg_engine::RING];
-        if (pv.seq == ev.seq - 1 && pv.has_ssb && ev.seq > e->seq_reset) {
+        // holds that marker while its seq is this call's - 1 (begin folds a slot's successor before reusing it).
+        const EvSet &pv = ring[(slot + RING - 1) % RING];
+        if (pv.seq == ev.seq - 1 && pv.has_ssb && ev.seq > seq_reset) {
             HIP_TRY(hipEventSynchronize(ev.ssb1));
             HIP_TRY(hipEventElapsedTime(&ms, pv.ssb1, ev.ssb1));
             t.ssb_ms = ms;
@@ -814,25 +924,52 @@ int32_t fold_slot(sdrg_engine *e, int slot) {
     HIP_TRY(hipEventElapsedTime(&ms, ev.t0, ev.end));
     t.total_ms = ms;
     ev.pending = false;
-    if (slot == e->ring_last) e->last_timings = t;
-    e->sum_spec += t.spectrum_ms;
-    e->sum_stats += t.stats_ms;
+    if (slot == last) last_timings = t;
+    sum_spec += t.spectrum_ms;
+    sum_stats += t.stats_ms;
     if (ssb_measured) {
-        e->sum_ssb += t.ssb_ms;
-        e->n_ssb++;
+        sum_ssb += t.ssb_ms;
+        n_ssb++;
     }
-    e->sum_total += t.total_ms;
-    e->n_acc++;
+    sum_total += t.total_ms;
+    n_acc++;
     return SDRG_OK;
 }
 
-int32_t fold_all(sdrg_engine *e) {
-    // oldest first
-    for (int k = 0; k < sdrg_engine::RING; k++) {
-        int32_t rc = fold_slot(e, (e->ring_next + k) % sdrg_engine::RING);
-        if (rc) return rc;
-    }
+int32_t Profiler::fold_all() {
+    for (int k = 0; k < RING; k++)  // oldest first
+        if (int32_t rc = fold_slot((next + k) % RING)) return rc;
     return SDRG_OK;
+}
+
+int32_t Profiler::create() {
+    // timing only: no system-scope fence (its cache writeback would widen the gaps it measures)
+    for (EvSet &r : ring)
+        for (Event *p : {&r.t0, &r.spec, &r.stats, &r.ssb0, &r.ssb1, &r.end}) HIP_TRY(p->create(hipEventDisableSystemFence));
+    return SDRG_OK;
+}
+
+// The slot of call `seq` (every enqueue counts), folded and filled with what the call will record; null if folding fails.
+// early_fork: the call is pipelined and not joined.
+EvSet *Profiler::begin(int64_t seq, bool do_spec, bool do_stats, bool do_ssb, bool early_fork, bool stats_async) {
+    // the next slot's call measures its pipelined SSB interval from this slot's end marker, about to be reused
+    if (fold_slot(next) || fold_slot((next + 1) % RING)) return nullptr;
+    EvSet *ev = &ring[next];
+    ev->has_spec = do_spec;
+    ev->has_stats = do_stats;
+    ev->has_ssb = do_ssb;
+    // the SSB start marker sits on the SSB stream between the fork and the pipeline; pipelined, that stream is
+    // the step's critical path, so a call carries one only when its SSB time cannot be measured from the previous
+    // call's SSB end marker to its own (fold_slot): the previous call (seq - 1) was not a profiled SSB call of this
+    // timing window
+    const EvSet &pv = ring[(next + RING - 1) % RING];
+    const bool chained = pv.seq == seq - 1 && pv.has_ssb && seq > seq_reset;
+    ev->ssb_timed = do_ssb && (!early_fork || !chained);
+    ev->seq = seq;
+    // a joined call's end marker follows the wait for the SSB stream, and asynchronous statistics end on a
+    // stream of their own: the statistics get a marker of their own
+    ev->stats_marked = do_stats && (!early_fork || stats_async);
+    return ev;
 }
 
 // processSSB_opt's per-call control logic (:223-282) -> kernel parameters.  Works on copies of the engine's
@@ -858,7 +995,7 @@ int32_t prepare_ssb(sdrg_engine *e, SsbControl &c, uint32_t &nco_phase, SsbParam
         c.rf_init = true;
     }
     const int decim = ssb_decim(fs);
-    if (c.taps_samp != c.samp_count || c.taps_decim != decim || c.taps_req != e->fir_taps || !e->d_taps) {
+    if (c.taps_samp != c.samp_count || c.taps_decim != decim || c.taps_req != e->fir_taps || !e->d_taps.p) {
         // an earlier call's SSB kernels may still read the taps and the chunk table (non-blocking streams)
         HIP_TRY(hipStreamSynchronize(e->s_ssb));
         // the device tables change now, before this call commits its SSB state: the committed key no longer
@@ -867,8 +1004,9 @@ int32_t prepare_ssb(sdrg_engine *e, SsbControl &c, uint32_t &nco_phase, SsbParam
         float h[256];
         c.n_taps = design_fir(c.samp_count, decim, 0.45f, h, e->fir_taps);
         c.taps_req = e->fir_taps;
-        if (!e->d_taps) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_taps), 256 * sizeof(float)));
-        HIP_TRY(hipMemcpy(e->d_taps, h, sizeof(float) * (size_t)c.n_taps, hipMemcpyHostToDevice));
+        int32_t rc = ensure_device(&e->d_taps, sizeof(h) / sizeof(h[0]));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(e->d_taps.p, h, sizeof(float) * (size_t)c.n_taps, hipMemcpyHostToDevice));
         c.taps_samp = c.samp_count;
         c.taps_decim = decim;
         // FIR output ranges per pipeline chunk (the kernel then needs no integer division):
@@ -889,9 +1027,9 @@ int32_t prepare_ssb(sdrg_engine *e, SsbControl &c, uint32_t &nco_phase, SsbParam
             tab[4 * ch + 2] = dn_lo;
             tab[4 * ch + 3] = dn_hi;
         }
-        int32_t rc = ensure_device(&e->d_chunk_table, &e->chunk_table_elems, tab.size());
+        rc = ensure_device(&e->d_chunk_table, tab.size());
         if (rc) return rc;
-        HIP_TRY(hipMemcpy(e->d_chunk_table, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->d_chunk_table.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     if (!c.eq_init) {
         design_highpass(48000.0f, 1200.0f, 0.7f, c.hp);
@@ -919,23 +1057,12 @@ int32_t prepare_ssb(sdrg_engine *e, SsbControl &c, uint32_t &nco_phase, SsbParam
         p->nco_on = 1;
         p->nco_inc = nco_increment(e->nco_hz, fs);
         p->nco_phase = nco_phase;
-        p->nco_tab = e->d_nco_tab;
+        p->nco_tab = e->d_nco_tab.p;
         nco_phase += p->nco_inc * (uint32_t)c.samp_count;  // phase-continuous across calls
     }
     return SDRG_OK;
 }
 
-int32_t alloc_state(sdrg_engine *e) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_stats), sizeof(StatsState) * (size_t)e->n_streams));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_ssb), sizeof(SsbStreamState) * (size_t)e->n_streams));
-    HIP_TRY(memset_sync(e->d_stats, 0, sizeof(StatsState) * (size_t)e->n_streams));
-    HIP_TRY(memset_sync(e->d_ssb, 0, sizeof(SsbStreamState) * (size_t)e->n_streams));
-    return SDRG_OK;
-}
-
-// FFTProcessor::configure (fft_process.cpp:33-35): maxPeakAndFrequency = {-130, cf} on first configure.
-// The device state starts zeroed; max_peak_set = 0 makes the kernel seed it at the first frame with the
-// centre frequency of that frame's configuration, which is what configure() stored.
 int32_t bytes_per_sample(int fmt) {
     switch (fmt) {
     case SDRG_IQ_CF32: return 8;
@@ -944,6 +1071,39 @@ int32_t bytes_per_sample(int fmt) {
     case SDRG_IQ_CU8: return 2;
     default: return 0;
     }
+}
+
+// The SSB section of a call, on s_ssb, and the audio detector behind it on s_ap: a joined call's fork, the pipeline with
+// the detector's front end in it, the stream's end marker mk_end, the detector.  ev: the profiling slot, or null.
+int32_t enqueue_ssb(sdrg_engine *e, const void *iq, int32_t fmt, const SsbParams &sp, int16_t *pcm, size_t pcm_bytes,
+                    bool do_ap, bool early_fork, const EvSet *ev, hipEvent_t mk_end) {
+    if (!early_fork) {  // fork
+        HIP_TRY(hipEventRecord(e->ev_fork, e->s_main));
+        HIP_TRY(hipStreamWaitEvent(e->s_ssb, e->ev_fork, 0));
+    }
+    if (int32_t rc = e->gathers.wait_before_write(e->s_ssb, pcm, pcm_bytes)) return rc;  // still being gathered
+    if (ev && ev->ssb_timed) HIP_TRY(hipEventRecord(ev->ssb0, e->s_ssb));
+    // AudioPulseDetector::process(pcm) after processSSB_opt (ssb_processor.cpp:109): its per-sample front
+    // end runs inside the SSB kernel on the PCM it produces, the detector right after
+    AudioFront af;
+    const int ap_set = e->ap.set();
+    if (do_ap) {
+        if (e->ap.live[ap_set]) HIP_TRY(hipEventSynchronize(e->ap.ev_end[ap_set]));  // the detector that read the set
+        if (int32_t rc = pulse_bank_audio_front(&e->audio_bank, sp.pcm_len, &af, e->s_ssb, ap_set)) return rc;
+    }
+    // the SSB stream's end marker: input release (the SSB pipeline, an iq reader, is done), join, timing, and
+    // the audio detector's start -- completed by the pipeline kernel's own launch where launch_ssb can
+    bool end_recorded = false;
+    HIP_TRY(launch_ssb(iq, fmt, e->n_streams, sp, e->d_taps.p, e->d_chunk_table.p, e->d_ssb.p, e->d_ssb_scratch.p, pcm,
+                       do_ap ? &af : nullptr, e->s_ssb, mk_end, &end_recorded));
+    if (!end_recorded) HIP_TRY(hipEventRecord(mk_end, e->s_ssb));
+    if (do_ap) {
+        HIP_TRY(hipStreamWaitEvent(e->s_ap, mk_end, 0));
+        int32_t rc = pulse_bank_audio_detect(&e->audio_bank, e->audio_bank.d_out, e->s_ap, ap_set);
+        if (!rc) rc = e->ap.detected(e->s_ap);
+        if (rc) return rc;
+    }
+    return SDRG_OK;
 }
 
 int32_t enqueue(sdrg_engine *e, const void *iq, int32_t fmt, int32_t stages, float *spectra,
@@ -963,32 +1123,28 @@ int32_t enqueue(sdrg_engine *e, const void *iq, int32_t fmt, int32_t stages, flo
                do_ssb = stages & SDRG_STAGE_SSB, do_sp = stages & SDRG_STAGE_SPECTRAL_PULSE,
                do_ap = stages & SDRG_STAGE_AUDIO_PULSE;
     if (do_sp && !e->spec_bank_live) {
-        int32_t rc = pulse_bank_init(&e->spec_bank, SDRG_PULSE_SPECTRAL, &e->spec_pulse_cfg, B, e->device);
-        if (rc) return rc;
+        if (int32_t rc = pulse_bank_init(&e->spec_bank, SDRG_PULSE_SPECTRAL, &e->spec_pulse_cfg, B, e->device)) return rc;
         e->spec_bank_live = true;
     }
     if (do_ap && !e->audio_bank_live) {
-        int32_t rc = pulse_bank_init(&e->audio_bank, SDRG_PULSE_AUDIO, &e->audio_pulse_cfg, B, e->device);
-        if (rc) return rc;
+        if (int32_t rc = pulse_bank_init(&e->audio_bank, SDRG_PULSE_AUDIO, &e->audio_pulse_cfg, B, e->device)) return rc;
         e->audio_bank_live = true;
     }
     if (do_spec && !spectrum_supported(n))
         return fail(SDRG_E_UNSUPPORTED, "spectrum for N=%d not supported by this build", n);
 
+    // allocations
     float *spec = spectra;
     if (do_spec && !spec) {
         // zeroed: for odd N the reference never writes power_shifted[N-1] (fft_process.cpp:92-97), which keeps the
         // value its vector held -- 0 for a fresh vector, the same stream's last value afterwards
-        int32_t rc = ensure_device(&e->d_spec_scratch, &e->spec_scratch_elems, (size_t)B * n, true);
-        if (rc) return rc;
-        spec = e->d_spec_scratch;
+        if (int32_t rc = ensure_device(&e->d_spec_scratch, (size_t)B * n, true)) return rc;
+        spec = e->d_spec_scratch.p;
     }
     sdrg_frame_record *recs = records;
     if (do_stats && !recs) {
-        size_t have = e->d_rec_scratch ? (size_t)B : 0;
-        int32_t rc = ensure_device(&e->d_rec_scratch, &have, (size_t)B);
-        if (rc) return rc;
-        recs = e->d_rec_scratch;
+        if (int32_t rc = ensure_device(&e->d_rec_scratch, (size_t)B)) return rc;
+        recs = e->d_rec_scratch.p;
     }
     // the byte ranges this call writes (checked against the ranges pending gathers read)
     const size_t spec_bytes = (size_t)B * (size_t)n * sizeof(float), rec_bytes = (size_t)B * sizeof(sdrg_frame_record);
@@ -1000,71 +1156,26 @@ int32_t enqueue(sdrg_engine *e, const void *iq, int32_t fmt, int32_t stages, flo
         const int plen = ssb_pcm_len(samp, (uint32_t)e->cfg.sample_rate, e->fir_taps);
         if (!pcm && plen > 0) return fail(SDRG_E_INVALID, "null pcm with SSB stage");
         pcm_bytes = (size_t)B * (size_t)(plen > 0 ? plen : 0) * sizeof(int16_t);
-        int32_t rc = ensure_device(&e->d_ssb_scratch, &e->ssb_scratch_elems, (size_t)B * ((size_t)samp + (size_t)plen));
-        if (rc) return rc;
+        if (int32_t rc = ensure_device(&e->d_ssb_scratch, (size_t)B * ((size_t)samp + (size_t)plen))) return rc;
     }
     if (do_spec) {
-        int32_t rc = upload_twiddles(e, n);
-        if (rc) return rc;
-        rc = ensure_device(&e->d_fft_scratch, &e->fft_scratch_elems, spectrum_scratch_floats(n, B));
-        if (rc) return rc;
+        if (int32_t rc = upload_twiddles(e, n)) return rc;
+        if (int32_t rc = ensure_device(&e->d_fft_scratch, spectrum_scratch_floats(n, B))) return rc;
     }
-
     StatsGeometry geo{};
     if (do_stats) {
         if (e->fft_fs == 0) return fail(SDRG_E_INVALID, "the statistics' sample rate is 0");
         geo = stats_geometry(e->fft_fs, e->fft_fc, n, e->fft_focus);
         geo.cf_changed = e->cf_changed_pending ? 1 : 0;
-        int32_t rc = ensure_device(&e->d_pool, &e->pool_elems, stats_global_pool_floats(geo, B));
-        if (rc) return rc;
+        if (int32_t rc = ensure_device(&e->d_pool, stats_global_pool_floats(geo, B))) return rc;
     }
 
     // last of the checks and allocations: the SSB control statics of this call (committed at the end)
     SsbControl ssb_next = e->ssb;
     uint32_t nco_next = e->nco_phase;
-    if (do_ssb) {
-        int32_t rc = prepare_ssb(e, ssb_next, nco_next, &sp);
-        if (rc) return rc;
-    }
+    if (do_ssb)
+        if (int32_t rc = prepare_ssb(e, ssb_next, nco_next, &sp)) return rc;
 
-    const bool prof = e->profiling;
-    const int64_t seq = e->calls_total++;
-    EvSet *ev = nullptr;
-    if (prof) {
-        const int slot = e->ring_next;
-        if (e->ring[slot].pending) {
-            int32_t rc = fold_slot(e, slot);
-            if (rc) return rc;
-        }
-        // the next slot's call measures its pipelined SSB interval from this slot's end marker, about to be reused
-        const int nx = (slot + 1) % sdrg_engine::RING;
-        if (e->ring[nx].pending) {
-            int32_t rc = fold_slot(e, nx);
-            if (rc) return rc;
-        }
-        ev = &e->ring[slot];
-        ev->has_spec = do_spec;
-        ev->has_stats = do_stats;
-        ev->has_ssb = do_ssb;
-        // the SSB start marker sits on the SSB stream between the fork and the pipeline; pipelined, that stream is
-        // the step's critical path, so a call carries one only when its SSB time cannot be measured from the previous
-        // call's SSB end marker to its own (fold_slot): the previous call (seq - 1, every enqueue counts) was not a
-        // profiled SSB call of this timing window
-        const EvSet &pv = e->ring[(slot + sdrg_engine::RING - 1) % sdrg_engine::RING];
-        const bool chained = pv.seq == seq - 1 && pv.has_ssb && seq > e->seq_reset;
-        ev->ssb_timed = do_ssb && (!(e->pipelined && !join) || !chained);
-        ev->seq = seq;
-        // a joined call's end marker follows the wait for the SSB stream, and asynchronous statistics end on a
-        // stream of their own: the statistics get a marker of their own
-        ev->stats_marked = do_stats && (!(e->pipelined && !join) || e->stats_async);
-    }
-    // Markers: every event recorded between two kernels of a stream costs that stream a gap (several us
-    // measured), so a call records at most one at its start on the main stream (the SSB fork and the timing
-    // origin), one after the spectrum (timing only), and one at the end of each stream's work (input release,
-    // join, timing).  Profiling uses the ring's timing events for these; otherwise untimed ones.
-    hipEvent_t mk_start = prof ? ev->t0 : e->ev_fork;
-    hipEvent_t mk_main_end = prof ? ev->end : e->ev_in_main;
-    hipEvent_t mk_ssb_end = prof ? ev->ssb1 : e->ev_in_ssb;
     // The spectrum kernel runs alone on the whole chip first (it is HBM-bound and persistent, two
     // workgroups per CU); the SSB pipeline (latency-bound, one workgroup per CU) then runs beside the
     // statistics kernel on a forked stream.  Measured: the same step time as running the spectrum beside
@@ -1073,6 +1184,20 @@ int32_t enqueue(sdrg_engine *e, const void *iq, int32_t fmt, int32_t stages, flo
     // joined at its end, so this call's SSB pipeline and the next call's spectrum share the chip as the
     // other's workgroups retire (steady state measured in tools/overlap_lab.py).
     const bool early_fork = e->pipelined && !join;
+
+    const bool prof = e->prof.on;
+    const int64_t seq = e->calls_total++;
+    EvSet *ev = nullptr;  // the profiling slot
+    if (prof && !(ev = e->prof.begin(seq, do_spec, do_stats, do_ssb, early_fork, e->stats_async))) return SDRG_E_HIP;  // fold_slot's
+
+    // the launches
+    // Markers: every event recorded between two kernels of a stream costs that stream a gap (several us
+    // measured), so a call records at most one at its start on the main stream (the SSB fork and the timing
+    // origin), one after the spectrum (timing only), and one at the end of each stream's work (input release,
+    // join, timing).  Profiling uses the ring's timing events for these; otherwise untimed ones.
+    hipEvent_t mk_start = prof ? ev->t0 : e->ev_fork;
+    hipEvent_t mk_main_end = prof ? ev->end : e->ev_in_main;
+    hipEvent_t mk_ssb_end = prof ? ev->ssb1 : e->ev_in_ssb;
     // the fork: the SSB stage waits for what the caller enqueued on the main stream before this call (its
     // producer work on iq) -- unless the caller declared its inputs complete at call time
     // (SDRG_PIPELINE_INPUTS_READY), which saves the SSB stream a cross-stream wait per call (measured ~20 us)
@@ -1086,23 +1211,16 @@ int32_t enqueue(sdrg_engine *e, const void *iq, int32_t fmt, int32_t stages, flo
         HIP_TRY(hipEventRecord(e->ev_fork_spec, e->s_main));
         HIP_TRY(hipStreamWaitEvent(e->s_spec, e->ev_fork_spec, 0));
     }
-    // asynchronous statistics (SDRG_PIPELINE_STATS_ASYNC): the statistics of earlier calls may still read their
-    // spectra on s_stats.  The host waits for the call two before; a spectrum that overwrites the buffer the
-    // previous call's statistics read waits for them on the GPU.
     const bool async = e->stats_async && early_fork && do_stats && do_spec && (!split || e->lab_stats_cus);
-    if (e->stats_async && do_spec) {
-        const int64_t c = e->sa_calls;
-        if (c >= 2 && e->sa_live[(c - 2) % sdrg_engine::SA_RING])
-            HIP_TRY(hipEventSynchronize(e->ev_stats_end[(c - 2) % sdrg_engine::SA_RING]));
-        const int pv = (int)((c + sdrg_engine::SA_RING - 1) % sdrg_engine::SA_RING);
-        if (c >= 1 && e->sa_live[pv] && (e->sa_spec[pv] == spec || !async))
-            HIP_TRY(hipStreamWaitEvent(sm, e->ev_stats_end[pv], 0));
-    }
-    if (hipEvent_t g = do_spec ? e->gathering(spec, spec_bytes) : nullptr) HIP_TRY(hipStreamWaitEvent(sm, g, 0));  // being gathered
+    if (e->stats_async && do_spec)  // earlier calls' statistics may still read their spectra on s_stats
+        if (int32_t rc = e->sa.before_spectrum(sm, spec, async)) return rc;
+    if (do_spec)
+        if (int32_t rc = e->gathers.wait_before_write(sm, spec, spec_bytes)) return rc;  // being gathered
     auto enqueue_spectrum = [&]() -> int32_t {
         if (do_spec) {
-            HIP_TRY(launch_spectrum(iq, fmt, n, B, e->d_twiddles, spec, e->d_fft_scratch, sm, do_ssb && early_fork && !split,
-                                    split ? e->spec_cus : 0, do_stats && stats_uses_wide(geo)));
+            HIP_TRY(launch_spectrum(iq, fmt, n, B, e->d_twiddles.p, spec, e->d_fft_scratch.p, sm,
+                                    do_ssb && early_fork && !split, split ? e->spec_cus : 0,
+                                    do_stats && stats_uses_wide(geo)));
             if (prof) HIP_TRY(hipEventRecord(ev->spec, sm));
         }
         return SDRG_OK;
@@ -1112,63 +1230,27 @@ int32_t enqueue(sdrg_engine *e, const void *iq, int32_t fmt, int32_t stages, flo
     const bool ssb_first = e->lab_ssb_first && do_ssb && early_fork;
     if (!ssb_first)
         if (int32_t rc = enqueue_spectrum()) return rc;
-    if (do_ssb) {  // fork
-        if (!early_fork) {
-            HIP_TRY(hipEventRecord(e->ev_fork, e->s_main));
-            HIP_TRY(hipStreamWaitEvent(e->s_ssb, e->ev_fork, 0));
-        }
-        if (hipEvent_t g = e->gathering(pcm, pcm_bytes)) HIP_TRY(hipStreamWaitEvent(e->s_ssb, g, 0));  // still being gathered
-        if (prof && ev->ssb_timed) HIP_TRY(hipEventRecord(ev->ssb0, e->s_ssb));
-        // AudioPulseDetector::process(pcm) after processSSB_opt (ssb_processor.cpp:109): its per-sample front
-        // end runs inside the SSB kernel on the PCM it produces, the detector right after
-        AudioFront af;
-        const int ap_set = (int)(e->ap_calls % sdrg_pulse_bank::NEW_SETS);
-        if (do_ap) {
-            if (e->ap_live[ap_set]) HIP_TRY(hipEventSynchronize(e->ev_ap_end[ap_set]));
-            int32_t rc = pulse_bank_audio_front(&e->audio_bank, sp.pcm_len, &af, e->s_ssb, ap_set);
-            if (rc) return rc;
-        }
-        // the SSB stream's end marker: input release (the SSB pipeline, an iq reader, is done), join, timing, and
-        // the audio detector's start -- completed by the pipeline kernel's own launch where launch_ssb can
-        bool end_recorded = false;
-        HIP_TRY(launch_ssb(iq, fmt, B, sp, e->d_taps, e->d_chunk_table, e->d_ssb, e->d_ssb_scratch, pcm,
-                           do_ap ? &af : nullptr, e->s_ssb, mk_ssb_end, &end_recorded));
-        if (!end_recorded) HIP_TRY(hipEventRecord(mk_ssb_end, e->s_ssb));
-        if (do_ap) {
-            HIP_TRY(hipStreamWaitEvent(e->s_ap, mk_ssb_end, 0));
-            int32_t rc = pulse_bank_audio_detect(&e->audio_bank, e->audio_bank.d_out, e->s_ap, ap_set);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(e->ev_ap_end[ap_set], e->s_ap));
-            e->ap_live[ap_set] = true;
-            e->last_ap_end = e->ev_ap_end[ap_set];
-            e->ap_calls++;
-        }
-    }
+    if (do_ssb)
+        if (int32_t rc = enqueue_ssb(e, iq, fmt, sp, pcm, pcm_bytes, do_ap, early_fork, ev, mk_ssb_end)) return rc;
     if (ssb_first)
         if (int32_t rc = enqueue_spectrum()) return rc;
     if (do_stats) {
         hipStream_t st = sm;
         if (async) {  // after this call's spectrum, beside the next call's
-            HIP_TRY(hipEventRecord(e->ev_spec_done, sm));
-            HIP_TRY(hipStreamWaitEvent(e->s_stats, e->ev_spec_done, 0));
+            HIP_TRY(hipEventRecord(e->sa.ev_spec_done, sm));
+            HIP_TRY(hipStreamWaitEvent(e->s_stats, e->sa.ev_spec_done, 0));
             st = e->s_stats;
         }
-        if (hipEvent_t g = e->gathering(recs, rec_bytes)) HIP_TRY(hipStreamWaitEvent(st, g, 0));  // still being gathered
-        HIP_TRY(launch_stats(spec, B, geo, now_ms, e->d_stats, recs, e->d_pool, st));
-        if (do_sp) {  // spectralPulseDetector.process(best1kHzSnrSigma, best1kHzCenterFreqHz) (:477-479)
-            int32_t rc = pulse_bank_spectral(&e->spec_bank, &recs->best1khz_snr_sigma, &recs->best1khz_center_freq_hz,
-                                             (int)sizeof(sdrg_frame_record), e->spec_bank.d_out, st);
-            if (rc) return rc;
-        }
+        int32_t rc = e->gathers.wait_before_write(st, recs, rec_bytes);  // still being gathered
+        if (rc) return rc;
+        HIP_TRY(launch_stats(spec, B, geo, now_ms, e->d_stats.p, recs, e->d_pool.p, st));
+        // spectralPulseDetector.process(best1kHzSnrSigma, best1kHzCenterFreqHz) (:477-479)
+        if (do_sp) rc = pulse_bank_spectral(&e->spec_bank, &recs->best1khz_snr_sigma, &recs->best1khz_center_freq_hz,
+                                            (int)sizeof(sdrg_frame_record), e->spec_bank.d_out, st);
+        if (rc) return rc;
         if (prof && ev->stats_marked) HIP_TRY(hipEventRecord(ev->stats, st));
-        if (async) {
-            const int k = (int)(e->sa_calls % sdrg_engine::SA_RING);
-            HIP_TRY(hipEventRecord(e->ev_stats_end[k], st));
-            e->sa_spec[k] = spec;
-            e->sa_live[k] = true;
-            e->sa_calls++;
-            e->last_stats_end = e->ev_stats_end[k];
-        }
+        if (async) rc = e->sa.after_stats(st, spec);
+        if (rc) return rc;
     }
     // the main stream's end marker: input release (the spectrum reads iq), timing; joined calls place it after
     // the join, so total_ms spans both streams
@@ -1178,32 +1260,20 @@ int32_t enqueue(sdrg_engine *e, const void *iq, int32_t fmt, int32_t stages, flo
     }
     if (do_ssb && !early_fork) {  // join
         HIP_TRY(hipStreamWaitEvent(e->s_main, mk_ssb_end, 0));
-        if (do_ap) HIP_TRY(hipStreamWaitEvent(e->s_main, e->last_ap_end, 0));
+        if (do_ap) HIP_TRY(hipStreamWaitEvent(e->s_main, e->ap.last_end, 0));
     }
     if (do_spec || prof) HIP_TRY(hipEventRecord(mk_main_end, e->s_main));
-    if (prof) {
-        ev->pending = true;
-        e->ring_last = e->ring_next;
-        e->ring_next = (e->ring_next + 1) % sdrg_engine::RING;
-    }
+
     // every launch of the call is enqueued: commit its host-side state
+    if (prof) e->prof.commit();
     if (do_ssb) {
         e->ssb = ssb_next;
         e->nco_phase = nco_next;
     }
     if (do_stats) e->cf_changed_pending = false;
-    // a gathered range this call wrote whole was waited for on a stream ordered after the gathers: no longer pending
-    // (ranges it wrote only in part, and the other gathered ranges, stay pending until a call writes them whole)
-    const std::pair<const void *, size_t> written[] = {{do_spec ? (const void *)spec : nullptr, spec_bytes},
-                                                       {do_stats ? (const void *)recs : nullptr, rec_bytes},
-                                                       {do_ssb ? (const void *)pcm : nullptr, pcm_bytes}};
-    for (const auto &w : written)
-        if (w.first) {
-            const uintptr_t lo = reinterpret_cast<uintptr_t>(w.first), hi = lo + w.second;
-            e->g_bufs.erase(std::remove_if(e->g_bufs.begin(), e->g_bufs.end(),
-                                           [lo, hi](const sdrg_engine::GBuf &g) { return lo <= g.lo && g.hi <= hi; }),
-                            e->g_bufs.end());
-        }
+    if (do_spec) e->gathers.written(spec, spec_bytes);
+    if (do_stats) e->gathers.written(recs, rec_bytes);
+    if (do_ssb) e->gathers.written(pcm, pcm_bytes);
     if (do_spec) e->last_in_main = mk_main_end;
     if (do_ssb) e->last_in_ssb = mk_ssb_end;
     if (do_spec || do_stats) e->last_async_stats = do_stats && async;
@@ -1380,8 +1450,8 @@ int32_t sdrg_engine_create(const sdrg_config *cfg, int32_t n_streams, int32_t de
             e->s_ssb = nullptr;
             if (hipExtStreamCreateWithCUMask(&e->s_ssb, (uint32_t)ma.size(), ma.data()) != hipSuccess ||
                 hipExtStreamCreateWithCUMask(&e->s_spec, (uint32_t)mb.size(), mb.data()) != hipSuccess ||
-                hipEventCreateWithFlags(&e->ev_fork_spec, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&e->ev_join_spec, hipEventDisableTiming) != hipSuccess)
+                e->ev_fork_spec.create(hipEventDisableTiming) != hipSuccess ||
+                e->ev_join_spec.create(hipEventDisableTiming) != hipSuccess)
                 return cleanup(fail(SDRG_E_HIP, "CU-masked stream creation failed"));
             e->spec_cus = ncu - ncu / 2;
         }
@@ -1422,20 +1492,21 @@ int32_t sdrg_engine_create(const sdrg_config *cfg, int32_t n_streams, int32_t de
             e->s_stats = nullptr;
             if (hipExtStreamCreateWithCUMask(&e->s_stats, (uint32_t)ms.size(), ms.data()) != hipSuccess ||
                 hipExtStreamCreateWithCUMask(&e->s_spec, (uint32_t)mf.size(), mf.data()) != hipSuccess ||
-                hipEventCreateWithFlags(&e->ev_fork_spec, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&e->ev_join_spec, hipEventDisableTiming) != hipSuccess)
+                e->ev_fork_spec.create(hipEventDisableTiming) != hipSuccess ||
+                e->ev_join_spec.create(hipEventDisableTiming) != hipSuccess)
                 return cleanup(fail(SDRG_E_HIP, "CU-masked stream creation failed"));
             e->spec_cus = ncu - taken;
             e->lab_stats_cus = true;
         }
     }
-    hipEvent_t *evs[] = {&e->ev_fork, &e->ev_join, &e->ev_in_main, &e->ev_in_ssb, &e->ev_ap_end[0], &e->ev_ap_end[1],
-                         &e->ev_ap_end[2]};
-    static_assert(sdrg_pulse_bank::NEW_SETS == 3, "ev_ap_end creation");
-    for (auto p : evs)
-        if (hipEventCreateWithFlags(p, ev_flags) != hipSuccess)
-            return cleanup(fail(SDRG_E_HIP, "hipEventCreate failed"));
-    rc = alloc_state(e);
+    for (Event *p : {&e->ev_fork, &e->ev_join, &e->ev_in_main, &e->ev_in_ssb})
+        if (p->create(ev_flags) != hipSuccess) return cleanup(fail(SDRG_E_HIP, "hipEventCreate failed"));
+    if (create_events(e->ap.ev_end, ev_flags)) return cleanup(fail(SDRG_E_HIP, "hipEventCreate failed"));
+    // FFTProcessor::configure (fft_process.cpp:33-35): maxPeakAndFrequency = {-130, cf} on first configure.
+    // The device state starts zeroed; max_peak_set = 0 makes the kernel seed it at the first frame with the
+    // centre frequency of that frame's configuration, which is what configure() stored.
+    rc = ensure_device(&e->d_stats, (size_t)n_streams, true);
+    if (!rc) rc = ensure_device(&e->d_ssb, (size_t)n_streams, true);
     if (rc) return cleanup(rc);
     *out = e;
     return SDRG_OK;
@@ -1451,35 +1522,8 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     if (e->s_ap) (void)hipStreamSynchronize(e->s_ap);
     e->spec_bank.last_stream = e->audio_bank.last_stream = nullptr;  // drained above
     e->spec_bank.detect_stream = e->audio_bank.detect_stream = nullptr;
-    void *bufs[] = {e->d_stats, e->d_ssb, e->d_twiddles, e->d_taps, e->d_nco_tab, e->d_chunk_table, e->d_ssb_scratch,
-                    e->d_spec_scratch, e->d_fft_scratch, e->d_pool, e->d_rec_scratch, e->d_iq_stage, e->d_spec_stage,
-                    e->spec_in.p, e->d_rec_stage, e->d_pcm_stage, e->d_focus_stage, e->disp_out.p, e->integ_ring.p,
-                    e->integ_ema.p, e->integ_out.p, e->peaks_out.p, e->stream_in.p, e->stream_out.p,
-                    e->chain_chan.p, e->chain_audio.p};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    e->ddc.free_buffers();
-    e->demod.free_buffers();
-    e->chan.free_buffers();
-    e->rs.free_buffers();
-    e->sq.free_buffers();
-    e->agc.free_buffers();
-    e->sb.free_buffers();
     if (e->s_spec) (void)hipStreamSynchronize(e->s_spec);
-    for (hipEvent_t ev : e->ev_stats_end)
-        if (ev) (void)hipEventDestroy(ev);
     if (e->s_gather) (void)hipStreamSynchronize(e->s_gather);
-    hipEvent_t evs[] = {e->ev_fork, e->ev_join, e->ev_in_main, e->ev_in_ssb, e->ev_fork_spec, e->ev_join_spec,
-                        e->ev_spec_done, e->ev_ap_end[0], e->ev_ap_end[1], e->ev_ap_end[2], e->ev_outputs};
-    for (hipEvent_t ev : evs)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->ev_g)  // ev_gather is one of these
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto &r : e->ring) {
-        hipEvent_t rev[] = {r.t0, r.spec, r.stats, r.ssb0, r.ssb1, r.end};
-        for (hipEvent_t ev : rev)
-            if (ev) (void)hipEventDestroy(ev);
-    }
     pulse_bank_release(&e->spec_bank);  // also what a failed lazy init left behind (null-safe)
     pulse_bank_release(&e->audio_bank);
     if (e->s_own) (void)hipStreamDestroy(e->s_own);
@@ -1488,7 +1532,7 @@ int32_t sdrg_engine_destroy(sdrg_engine *e) {
     if (e->s_stats) (void)hipStreamDestroy(e->s_stats);
     if (e->s_ap) (void)hipStreamDestroy(e->s_ap);
     if (e->s_gather) (void)hipStreamDestroy(e->s_gather);
-    delete e;
+    delete e;  // the buffers and the events, each freed by its owner: the engine's device is current, its streams drained
     return SDRG_OK;
 }
 
@@ -1558,13 +1602,12 @@ int32_t sdrg_engine_wait_outputs(sdrg_engine *e, void *hip_stream) {
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : e->s_main;
     if (e->last_in_main && s != e->s_main) HIP_TRY(hipStreamWaitEvent(s, e->last_in_main, 0));  // spectra
     if (e->last_in_ssb) HIP_TRY(hipStreamWaitEvent(s, e->last_in_ssb, 0));                    // PCM
-    if (e->last_ap_end) HIP_TRY(hipStreamWaitEvent(s, e->last_ap_end, 0));                    // audio pulse
-    if (e->stats_async && e->last_stats_end) HIP_TRY(hipStreamWaitEvent(s, e->last_stats_end, 0));  // records
-    if (e->ev_gather) HIP_TRY(hipStreamWaitEvent(s, e->ev_gather, 0));  // the gathered outputs on the root
+    if (e->ap.last_end) HIP_TRY(hipStreamWaitEvent(s, e->ap.last_end, 0));                    // audio pulse
+    if (e->stats_async && e->sa.last_end) HIP_TRY(hipStreamWaitEvent(s, e->sa.last_end, 0));  // records
+    if (e->gathers.ev_gather) HIP_TRY(hipStreamWaitEvent(s, e->gathers.ev_gather, 0));  // the gathered outputs on the root
     if (s != e->s_main) {  // the later stages' outputs: enqueued on the main stream after the call's own end marker
         if (e->outputs_unmarked) {
-            if (!e->ev_outputs)
-                HIP_TRY(hipEventCreateWithFlags(&e->ev_outputs, hipEventDisableTiming | hipEventDisableSystemFence));
+            HIP_TRY(e->ev_outputs.create(EV_ORDER));
             HIP_TRY(hipEventRecord(e->ev_outputs, e->s_main));
             e->outputs_unmarked = false;
         }
@@ -1638,15 +1681,14 @@ int32_t sdrg_engine_reset_state(sdrg_engine *e) {
     HIP_TRY(hipStreamSynchronize(e->s_ssb));
     if (e->s_stats) HIP_TRY(hipStreamSynchronize(e->s_stats));
     HIP_TRY(hipStreamSynchronize(e->s_ap));
-    HIP_TRY(memset_sync(e->d_stats, 0, sizeof(StatsState) * (size_t)e->n_streams));
-    HIP_TRY(memset_sync(e->d_ssb, 0, sizeof(SsbStreamState) * (size_t)e->n_streams));
+    HIP_TRY(memset_sync(e->d_stats.p, 0, sizeof(StatsState) * (size_t)e->n_streams));
+    HIP_TRY(memset_sync(e->d_ssb.p, 0, sizeof(SsbStreamState) * (size_t)e->n_streams));
     e->ssb = SsbControl{};
     e->nco_phase = 0;
     e->cf_changed_pending = false;
     e->spec_bank.reset_pending = true;
     e->audio_bank.reset_pending = true;
-    e->integ_t = 0;  // the integration history
-    e->integ_depth = 0;
+    e->integ.restart();
     return SDRG_OK;
 }
 
@@ -1663,16 +1705,13 @@ int32_t sdrg_engine_set_pipelining(sdrg_engine *e, int32_t on) {
     if (e->pipelined && !mode) {  // re-join what is in flight so later work on s_main follows it
         HIP_TRY(hipEventRecord(e->ev_join, e->s_ssb));
         HIP_TRY(hipStreamWaitEvent(e->s_main, e->ev_join, 0));
-        if (e->last_ap_end) HIP_TRY(hipStreamWaitEvent(e->s_main, e->last_ap_end, 0));
+        if (e->ap.last_end) HIP_TRY(hipStreamWaitEvent(e->s_main, e->ap.last_end, 0));
     }
-    if (e->stats_async && !async && e->last_stats_end)  // the asynchronous statistics in flight, likewise
-        HIP_TRY(hipStreamWaitEvent(e->s_main, e->last_stats_end, 0));
+    if (e->stats_async && !async && e->sa.last_end)  // the asynchronous statistics in flight, likewise
+        HIP_TRY(hipStreamWaitEvent(e->s_main, e->sa.last_end, 0));
     if (async) {  // created lazily, each handle on its own: a failed earlier attempt leaves no null behind in use
-        const unsigned fl = hipEventDisableTiming | hipEventDisableSystemFence;
         if (!e->s_stats) HIP_TRY(create_engine_stream(&e->s_stats, 4, e->device));
-        if (!e->ev_spec_done) HIP_TRY(hipEventCreateWithFlags(&e->ev_spec_done, fl));
-        for (hipEvent_t &ev : e->ev_stats_end)
-            if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, fl));
+        if (int32_t rc = e->sa.create()) return rc;
     }
     e->pipelined = mode != SDRG_PIPELINE_OFF;
     e->inputs_ready = mode == SDRG_PIPELINE_INPUTS_READY;
@@ -1751,12 +1790,12 @@ static int32_t signal_strength(sdrg_engine *e, const float *spectra, sdrg_frame_
     if (e->fft_fs == 0) return fail(SDRG_E_INVALID, "the statistics' sample rate is 0");
     StatsGeometry geo = stats_geometry(e->fft_fs, e->fft_fc, n, e->fft_focus);
     geo.cf_changed = e->cf_changed_pending ? 1 : 0;
-    int32_t rc = ensure_device(&e->d_pool, &e->pool_elems, stats_global_pool_floats(geo, B));
+    int32_t rc = ensure_device(&e->d_pool, stats_global_pool_floats(geo, B));
     if (rc) return rc;
     // asynchronous statistics of an earlier pipelined call (SDRG_PIPELINE_STATS_ASYNC) may still run on s_stats and
     // read / write the same stream state (d_stats) and pool scratch: this launch follows them
-    if (e->stats_async && e->last_stats_end) HIP_TRY(hipStreamWaitEvent(e->s_main, e->last_stats_end, 0));
-    HIP_TRY(launch_stats(spectra, B, geo, now_ms, e->d_stats, records, e->d_pool, e->s_main));
+    if (e->stats_async && e->sa.last_end) HIP_TRY(hipStreamWaitEvent(e->s_main, e->sa.last_end, 0));
+    HIP_TRY(launch_stats(spectra, B, geo, now_ms, e->d_stats.p, records, e->d_pool.p, e->s_main));
     e->cf_changed_pending = false;
     return SDRG_OK;
 }
@@ -1778,12 +1817,12 @@ int32_t sdrg_engine_signal_strength_host(sdrg_engine *e, const float *spectra, s
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     const size_t B = (size_t)e->n_streams;
-    if (!e->d_rec_stage)
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_rec_stage), sizeof(sdrg_frame_record) * B));
+    const int32_t rc = ensure_device(&e->d_rec_stage, B);
+    if (rc) return rc;
     return spectra_round_trip(
         e, spectra, nullptr, B * (size_t)e->cfg.samples_per_reading,
-        [&](const float *src) { return signal_strength(e, src, e->d_rec_stage, now_ms); },
-        {{records, e->d_rec_stage, sizeof(sdrg_frame_record) * B}});
+        [&](const float *src) { return signal_strength(e, src, e->d_rec_stage.p, now_ms); },
+        {{records, e->d_rec_stage.p, sizeof(sdrg_frame_record) * B}});
 }
 
 int32_t sdrg_engine_synchronize(sdrg_engine *e) {
@@ -1812,34 +1851,27 @@ int32_t sdrg_engine_process_host(sdrg_engine *e, const void *iq, int32_t format,
     const int n = e->cfg.samples_per_reading;
     const int B = e->n_streams;
     const size_t iq_bytes = (size_t)B * n * bps;
-    if (e->iq_stage_bytes < iq_bytes) {
-        size_t have = e->iq_stage_bytes;
-        char *p = static_cast<char *>(e->d_iq_stage);
-        int32_t rc = ensure_device(&p, &have, iq_bytes);
-        if (rc) return rc;
-        e->d_iq_stage = p;
-        e->iq_stage_bytes = have;
-    }
+    int32_t rc = ensure_device(&e->d_iq_stage, iq_bytes);
+    if (rc) return rc;
     const bool want_cb = e->has_cbs;
     const bool do_spec = stages & SDRG_STAGE_SPECTRUM, do_stats = stages & SDRG_STAGE_STATS,
                do_ssb = stages & SDRG_STAGE_SSB;
     if (do_spec) {
         e->host_spec_n = 0;  // until this call's spectra are enqueued
-        int32_t rc = ensure_device(&e->d_spec_stage, &e->spec_stage_elems, (size_t)B * n, true);  // see enqueue
-        if (rc) return rc;
+        rc = ensure_device(&e->d_spec_stage, (size_t)B * n, true);  // see enqueue
     }
-    if (do_stats && !e->d_rec_stage)
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_rec_stage), sizeof(sdrg_frame_record) * (size_t)B));
+    if (!rc && do_stats) rc = ensure_device(&e->d_rec_stage, (size_t)B);
+    if (rc) return rc;
     int pcm_len = 0;
     if (do_ssb) {
         // pcm length is known before the call: frozen (or about-to-be frozen) size and current fs
         pcm_len = ssb_pcm_len(ssb_frozen_or(e), (uint32_t)e->cfg.sample_rate, e->fir_taps);
-        int32_t rc = ensure_device(&e->d_pcm_stage, &e->pcm_stage_elems, (size_t)B * (pcm_len > 0 ? pcm_len : 1));
+        rc = ensure_device(&e->d_pcm_stage, (size_t)B * (pcm_len > 0 ? pcm_len : 1));
         if (rc) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(e->d_iq_stage, iq, iq_bytes, hipMemcpyHostToDevice, e->s_main));
-    int32_t rc = enqueue(e, e->d_iq_stage, format, stages, do_spec ? e->d_spec_stage : nullptr,
-                         do_stats ? e->d_rec_stage : nullptr, do_ssb ? e->d_pcm_stage : nullptr, now_ms, true);
+    HIP_TRY(hipMemcpyAsync(e->d_iq_stage.p, iq, iq_bytes, hipMemcpyHostToDevice, e->s_main));
+    rc = enqueue(e, e->d_iq_stage.p, format, stages, do_spec ? e->d_spec_stage.p : nullptr,
+                 do_stats ? e->d_rec_stage.p : nullptr, do_ssb ? e->d_pcm_stage.p : nullptr, now_ms, true);
     if (rc) return rc;
     if (do_spec) e->host_spec_n = n;  // sdrg_engine_display_host(spectra = NULL) reads these spectra
     float *h_spec = spectra;
@@ -1856,12 +1888,12 @@ int32_t sdrg_engine_process_host(sdrg_engine *e, const void *iq, int32_t format,
         if (do_ssb && !h_pcm) h_pcm = e->h_pcm.data();
     }
     if (do_spec && h_spec)
-        HIP_TRY(hipMemcpyAsync(h_spec, e->d_spec_stage, sizeof(float) * (size_t)B * n, hipMemcpyDeviceToHost, e->s_main));
+        HIP_TRY(hipMemcpyAsync(h_spec, e->d_spec_stage.p, sizeof(float) * (size_t)B * n, hipMemcpyDeviceToHost, e->s_main));
     if (do_stats && h_rec)
-        HIP_TRY(hipMemcpyAsync(h_rec, e->d_rec_stage, sizeof(sdrg_frame_record) * (size_t)B, hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(h_rec, e->d_rec_stage.p, sizeof(sdrg_frame_record) * (size_t)B, hipMemcpyDeviceToHost,
                                e->s_main));
     if (do_ssb && h_pcm && pcm_len > 0)
-        HIP_TRY(hipMemcpyAsync(h_pcm, e->d_pcm_stage, sizeof(int16_t) * (size_t)B * pcm_len, hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(h_pcm, e->d_pcm_stage.p, sizeof(int16_t) * (size_t)B * pcm_len, hipMemcpyDeviceToHost,
                                e->s_main));
     if (want_cb && (stages & SDRG_STAGE_SPECTRAL_PULSE)) {
         HIP_TRY(hipMemcpyAsync(e->h_pspec.data(), e->spec_bank.d_out, sizeof(sdrg_pulse_output) * (size_t)B,
@@ -1922,15 +1954,15 @@ int32_t sdrg_engine_set_display(sdrg_engine *e, const sdrg_display_config *cfg) 
         return fail(SDRG_E_INVALID, "display span: first_bin %d must be >= 0 and n_bins %d >= 1", cfg->first_bin, cfg->n_bins);
     if (cfg->format == SDRG_DISPLAY_U8 && !display_db_range_ok(cfg->db_min, cfg->db_max))
         return fail(SDRG_E_INVALID, "display db_min / db_max must be finite, db_max > db_min");
-    e->disp = *cfg;
-    e->disp_set = true;
+    e->disp.cfg = *cfg;
+    e->disp.set = true;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_get_display(const sdrg_engine *e, sdrg_display_config *out) {
     if (!e || !out) return fail(SDRG_E_INVALID, "null argument");
-    if (!e->disp_set) return fail(SDRG_E_INVALID, "no display configuration set");
-    *out = e->disp;
+    if (!e->disp.set) return fail(SDRG_E_INVALID, "no display configuration set");
+    *out = e->disp.cfg;
     return SDRG_OK;
 }
 
@@ -1961,8 +1993,8 @@ static int32_t resolve_span(const sdrg_engine *e, const char *what, int32_t span
 
 // the configuration in force resolved against the current N and focus window
 static int32_t display_params(const sdrg_engine *e, DisplayParams *p) {
-    if (!e->disp_set) return fail(SDRG_E_INVALID, "no display configuration set (sdrg_engine_set_display)");
-    const sdrg_display_config &c = e->disp;
+    if (!e->disp.set) return fail(SDRG_E_INVALID, "no display configuration set (sdrg_engine_set_display)");
+    const sdrg_display_config &c = e->disp.cfg;
     int n, lo, nb;
     const int32_t rc = resolve_span(e, "display", c.span, c.first_bin, c.n_bins, &n, &lo, &nb);
     if (rc) return rc;
@@ -2007,15 +2039,15 @@ static int32_t display_to_host(sdrg_engine *e, const DisplayParams &p, const flo
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     const size_t B = (size_t)e->n_streams, out_bytes = B * display_row_bytes(p);
-    const int32_t rc = ensure_device(&e->disp_out, out_bytes);
+    const int32_t rc = ensure_device(&e->disp.out, out_bytes);
     if (rc) return rc;
     return spectra_round_trip(
         e, spectra, d_rows, B * (size_t)p.n,
         [&](const float *src) -> int32_t {
-            HIP_TRY(launch_display(src, e->n_streams, p, e->disp_out.p, e->s_main));
+            HIP_TRY(launch_display(src, e->n_streams, p, e->disp.out.p, e->s_main));
             return SDRG_OK;
         },
-        {{out, e->disp_out.p, out_bytes}});
+        {{out, e->disp.out.p, out_bytes}});
 }
 
 int32_t sdrg_engine_display_host(sdrg_engine *e, const float *spectra, void *out) {
@@ -2042,62 +2074,58 @@ int32_t sdrg_engine_set_integration(sdrg_engine *e, const sdrg_integrate_config 
     } else {
         return fail(SDRG_E_INVALID, "unknown integration mode %d", cfg->mode);
     }
-    e->integ = *cfg;
-    e->integ_set = true;
-    e->integ_t = 0;
-    e->integ_depth = 0;
+    e->integ.cfg = *cfg;
+    e->integ.set = true;
+    e->integ.restart();
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_get_integration(const sdrg_engine *e, sdrg_integrate_config *cfg_out, int32_t *depth_out) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (cfg_out && !e->integ_set) return fail(SDRG_E_INVALID, "no integration configuration set");
-    if (cfg_out) *cfg_out = e->integ;
-    if (depth_out) *depth_out = e->integ_depth;
+    if (cfg_out && !e->integ.set) return fail(SDRG_E_INVALID, "no integration configuration set");
+    if (cfg_out) *cfg_out = e->integ.cfg;
+    if (depth_out) *depth_out = e->integ.depth;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_integrate_reset(sdrg_engine *e) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    e->integ_t = 0;
-    e->integ_depth = 0;
+    e->integ.restart();
     return SDRG_OK;
 }
 
 // one integrate call on the main stream: src, dst device [n_streams][N], dst may be src
 static int32_t integrate_enqueue(sdrg_engine *e, const float *src, float *dst) {
-    const sdrg_integrate_config &c = e->integ;
+    IntegrateStage &s = e->integ;
+    const sdrg_integrate_config &c = s.cfg;
     const int n = e->cfg.samples_per_reading;
     const size_t count = (size_t)e->n_streams * (size_t)n, stride = integrate_slot_stride(count);
     // a resize or a retune since the previous call: the bins mean other frequencies, the history is forgotten
-    const bool moved = e->integ_seen && (n != e->integ_n || e->cfg.sample_rate != e->integ_fs ||
-                                         e->cfg.center_frequency != e->integ_fc);
-    const int64_t t = moved ? 0 : e->integ_t;
+    const bool moved = s.seen && (n != s.n || e->cfg.sample_rate != s.fs || e->cfg.center_frequency != s.fc);
+    const int64_t t = moved ? 0 : s.t;
     IntegrateParams p{c.mode, 1, 0, (int)std::min<int64_t>(t + 1, INT32_MAX), c.alpha};
     int32_t rc;
     if (c.mode == SDRG_INTEGRATE_EMA) {
-        rc = ensure_device_keeping(&e->integ_ema, count);
+        rc = ensure_device_keeping(&s.ema, count);
     } else {
         p.period = c.period;
         p.slot = (int)(t % c.period);
         p.depth = (int)std::min<int64_t>(t + 1, c.period);
-        rc = ensure_device_keeping(&e->integ_ring, (size_t)c.period * stride);
+        rc = ensure_device_keeping(&s.ring, (size_t)c.period * stride);
     }
     if (rc) return rc;
     // SDRG_PIPELINE_STATS_ASYNC: statistics of earlier calls may still read their spectra on s_stats; a dst that
     // overlaps such a buffer (in-place integration of the call's own spectra) is written after them
-    if (e->stats_async)
-        for (int k = 0; k < sdrg_engine::SA_RING; k++)
-            if (e->sa_live[k] && e->sa_spec[k] < dst + count && dst < e->sa_spec[k] + count)
-                HIP_TRY(hipStreamWaitEvent(e->s_main, e->ev_stats_end[k], 0));
-    HIP_TRY(launch_integrate(src, count, p, e->integ_ring.p, stride, e->integ_ema.p, dst, e->s_main));
-    e->integ_t = t + 1;
-    e->integ_depth = p.depth;
-    e->integ_seen = true;
-    e->integ_n = n;
-    e->integ_fs = e->cfg.sample_rate;
-    e->integ_fc = e->cfg.center_frequency;
-    if (dst == e->integ_out.p) e->integ_out_n = n;  // integrate_host's rows: the _integrated_host calls read them
+    if (e->stats_async) rc = e->sa.wait_before_write(e->s_main, dst, count);
+    if (rc) return rc;
+    HIP_TRY(launch_integrate(src, count, p, s.ring.p, stride, s.ema.p, dst, e->s_main));
+    s.t = t + 1;
+    s.depth = p.depth;
+    s.seen = true;
+    s.n = n;
+    s.fs = e->cfg.sample_rate;
+    s.fc = e->cfg.center_frequency;
+    if (dst == s.out.p) s.out_n = n;  // integrate_host's rows: the _integrated_host calls read them
     e->outputs_unmarked = true;
     return SDRG_OK;
 }
@@ -2105,7 +2133,7 @@ static int32_t integrate_enqueue(sdrg_engine *e, const float *src, float *dst) {
 int32_t sdrg_engine_integrate_device(sdrg_engine *e, const float *spectra, float *out) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!spectra || !out) return fail(SDRG_E_INVALID, "null spectra or out");
-    if (!e->integ_set) return fail(SDRG_E_INVALID, "no integration configuration set (sdrg_engine_set_integration)");
+    if (!e->integ.set) return fail(SDRG_E_INVALID, "no integration configuration set (sdrg_engine_set_integration)");
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     return integrate_enqueue(e, spectra, out);
@@ -2113,7 +2141,7 @@ int32_t sdrg_engine_integrate_device(sdrg_engine *e, const float *spectra, float
 
 int32_t sdrg_engine_integrate_host(sdrg_engine *e, const float *spectra, float *out) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!e->integ_set) return fail(SDRG_E_INVALID, "no integration configuration set (sdrg_engine_set_integration)");
+    if (!e->integ.set) return fail(SDRG_E_INVALID, "no integration configuration set (sdrg_engine_set_integration)");
     const int n = e->cfg.samples_per_reading;
     const float *d_rows = nullptr;
     int32_t rc = resolve_spectra(e, spectra, n, &d_rows);
@@ -2121,12 +2149,12 @@ int32_t sdrg_engine_integrate_host(sdrg_engine *e, const float *spectra, float *
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     const size_t count = (size_t)e->n_streams * (size_t)n;
-    rc = ensure_device_keeping(&e->integ_out, count);
+    rc = ensure_device_keeping(&e->integ.out, count);
     if (rc) return rc;
     return spectra_round_trip(
         e, spectra, d_rows, count,
-        [&](const float *src) { return integrate_enqueue(e, src, e->integ_out.p); },
-        {{out, e->integ_out.p, sizeof(float) * count}});
+        [&](const float *src) { return integrate_enqueue(e, src, e->integ.out.p); },
+        {{out, e->integ.out.p, sizeof(float) * count}});
 }
 
 int32_t sdrg_engine_display_integrated_host(sdrg_engine *e, void *rows_out) {
@@ -2161,22 +2189,22 @@ int32_t sdrg_engine_set_peaks(sdrg_engine *e, const sdrg_peaks_config *cfg) {
         return fail(SDRG_E_INVALID, "min_separation %d outside [1, %d]", cfg->min_separation, SDRG_PEAKS_MAX_SEPARATION);
     if (std::isnan(cfg->threshold_db) || cfg->threshold_db == INFINITY)
         return fail(SDRG_E_INVALID, "threshold_db must be finite or -inf");
-    e->peaks = *cfg;
-    e->peaks_set = true;
+    e->peaks.cfg = *cfg;
+    e->peaks.set = true;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_get_peaks(const sdrg_engine *e, sdrg_peaks_config *out) {
     if (!e || !out) return fail(SDRG_E_INVALID, "null argument");
-    if (!e->peaks_set) return fail(SDRG_E_INVALID, "no peaks configuration set");
-    *out = e->peaks;
+    if (!e->peaks.set) return fail(SDRG_E_INVALID, "no peaks configuration set");
+    *out = e->peaks.cfg;
     return SDRG_OK;
 }
 
 // the configuration in force resolved against the current N and focus window
 static int32_t peaks_params(const sdrg_engine *e, PeaksParams *p) {
-    if (!e->peaks_set) return fail(SDRG_E_INVALID, "no peaks configuration set (sdrg_engine_set_peaks)");
-    const sdrg_peaks_config &c = e->peaks;
+    if (!e->peaks.set) return fail(SDRG_E_INVALID, "no peaks configuration set (sdrg_engine_set_peaks)");
+    const sdrg_peaks_config &c = e->peaks.cfg;
     int n, lo, nb;
     const int32_t rc = resolve_span(e, "peaks", c.span, c.first_bin, c.n_bins, &n, &lo, &nb);
     if (rc) return rc;
@@ -2204,10 +2232,10 @@ static int32_t peaks_to_host(sdrg_engine *e, const PeaksParams &p, const float *
     HIP_TRY(dscope.error());
     const size_t B = (size_t)e->n_streams, pk_bytes = B * (size_t)p.max_peaks * sizeof(sdrg_peak),
                  sm_bytes = B * sizeof(sdrg_peaks_summary);
-    const int32_t rc = ensure_device(&e->peaks_out, pk_bytes + sm_bytes);
+    const int32_t rc = ensure_device(&e->peaks.out, pk_bytes + sm_bytes);
     if (rc) return rc;
-    sdrg_peak *d_pk = reinterpret_cast<sdrg_peak *>(e->peaks_out.p);
-    sdrg_peaks_summary *d_sm = reinterpret_cast<sdrg_peaks_summary *>(e->peaks_out.p + pk_bytes);
+    sdrg_peak *d_pk = reinterpret_cast<sdrg_peak *>(e->peaks.out.p);
+    sdrg_peaks_summary *d_sm = reinterpret_cast<sdrg_peaks_summary *>(e->peaks.out.p + pk_bytes);
     return spectra_round_trip(
         e, spectra, d_rows, B * (size_t)p.n,
         [&](const float *src) -> int32_t {
@@ -2325,7 +2353,7 @@ static int32_t ddc_resolve(const sdrg_engine *e, int32_t fmt, DdcCall *c) {
 
 static int32_t ddc_reserve(sdrg_engine *e, const DdcCall &c) {
     DdcStage &s = e->ddc;
-    int32_t rc = ensure_device(&s.hist, s.half(e->n_streams));
+    int32_t rc = ensure_halves(&s.hist, s.half(e->n_streams));
     if (rc) return rc;
     // a longer frame than any before: hipFree waits for the calls that read the old row
     rc = ensure_device(&s.w, 2 * (size_t)c.n);
@@ -2346,7 +2374,7 @@ static int32_t ddc_launch(sdrg_engine *e, const DdcCall &c, const void *iq, void
     fir_tile_fill(&p, c.cur, s.cfg.decimation, s.cfg.taps, c, s.hist, s.half(e->n_streams));
     p.inc = nco_increment(s.cfg.offset_hz, c.fs);
     p.g0_lo = (uint32_t)c.cur.g;
-    p.nco_tab = e->d_nco_tab;
+    p.nco_tab = e->d_nco_tab.p;
     p.phasors = s.w.p;
     HIP_TRY(launch_ddc(iq, c.fmt, e->n_streams, p, s.taps, static_cast<float *>(out), e->s_main));
     s.cur = c.cur;
@@ -2440,7 +2468,7 @@ static int32_t demod_resolve(const sdrg_engine *e, int32_t n, StageCall *c) {
 }
 
 static int32_t demod_reserve(sdrg_engine *e, const StageCall &) {
-    const int32_t rc = ensure_device(&e->demod.state, e->demod.half(e->n_streams));
+    const int32_t rc = ensure_halves(&e->demod.state, e->demod.half(e->n_streams));
     return rc ? rc : ensure_device(&e->demod.scratch, (size_t)e->n_streams * (size_t)e->demod.cfg.max_in);
 }
 
@@ -2510,7 +2538,7 @@ int32_t sdrg_engine_set_channelizer(sdrg_engine *e, const sdrg_channelizer_confi
         }
         DeviceScope dscope(e->device);
         HIP_TRY(dscope.error());
-        const int32_t rc = upload_floats(&e->chan.d_taps, host, "channelizer");
+        const int32_t rc = upload_floats(&e->chan.d_taps, host, "channelizer taps");
         if (rc) return rc;
         e->chan.cfg = *cfg;
     }
@@ -2557,7 +2585,7 @@ static int32_t chan_resolve(const sdrg_engine *e, int32_t fmt, ChanCall *c) {
     return SDRG_OK;
 }
 
-static int32_t chan_reserve(sdrg_engine *e, const ChanCall &) { return ensure_device(&e->chan.hist, e->chan.half(e->n_streams)); }
+static int32_t chan_reserve(sdrg_engine *e, const ChanCall &) { return ensure_halves(&e->chan.hist, e->chan.half(e->n_streams)); }
 
 // one channelizer call on the main stream: iq, out in device memory
 static int32_t chan_launch(sdrg_engine *e, const ChanCall &c, const void *iq, void *out) {
@@ -2634,7 +2662,7 @@ int32_t sdrg_engine_set_resample(sdrg_engine *e, const sdrg_resample_config *cfg
             for (int k = 0; k < P; k++) poly[(size_t)phi * (size_t)P + (size_t)k] = h[(size_t)phi + (size_t)k * (size_t)L];
         DeviceScope dscope(e->device);
         HIP_TRY(dscope.error());
-        const int32_t rc = upload_floats(&e->rs.d_taps, poly, "resample");
+        const int32_t rc = upload_floats(&e->rs.d_taps, poly, "resample taps");
         if (rc) return rc;
         e->rs.taps.swap(h);
         e->rs.cfg = *cfg;
@@ -2681,7 +2709,7 @@ static int32_t rs_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, St
     return SDRG_OK;
 }
 
-static int32_t rs_reserve(sdrg_engine *e, const StageCall &) { return ensure_device(&e->rs.hist, e->rs.half(e->n_streams)); }
+static int32_t rs_reserve(sdrg_engine *e, const StageCall &) { return ensure_halves(&e->rs.hist, e->rs.half(e->n_streams)); }
 
 // one resample call on the main stream: in (rows of in_stride values), out in device memory
 static int32_t rs_launch(sdrg_engine *e, const StageCall &c, const void *in, void *out) {
@@ -2904,7 +2932,7 @@ int32_t sdrg_engine_set_sideband(sdrg_engine *e, const sdrg_sideband_config *cfg
         for (size_t k = 0; k < T; k++) pairs[2 * k] = cr[k], pairs[2 * k + 1] = ci[k];
         DeviceScope dscope(e->device);
         HIP_TRY(dscope.error());
-        const int32_t rc = upload_floats(&s.d_taps, pairs, "sideband");
+        const int32_t rc = upload_floats(&s.d_taps, pairs, "sideband taps");
         if (rc) return rc;
         s.cr.swap(cr);
         s.ci.swap(ci);
@@ -2954,7 +2982,7 @@ static int32_t sb_resolve(const sdrg_engine *e, int32_t n, StageCall *c) {
     return SDRG_OK;
 }
 
-static int32_t sb_reserve(sdrg_engine *e, const StageCall &) { return ensure_device(&e->sb.hist, e->sb.half(e->n_streams)); }
+static int32_t sb_reserve(sdrg_engine *e, const StageCall &) { return ensure_halves(&e->sb.hist, e->sb.half(e->n_streams)); }
 
 // one sideband call on the main stream: chan (rows of in_stride complex samples), out in device memory
 static int32_t sb_launch(sdrg_engine *e, const StageCall &c, const void *chan, void *out) {
@@ -3125,41 +3153,33 @@ int32_t sdrg_engine_set_profiling(sdrg_engine *e, int32_t enabled) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
-    if (enabled && !e->ring_created) {
-        for (auto &r : e->ring) {
-            // timing only: no system-scope fence (its cache writeback would widen the gaps it measures)
-            hipEvent_t *rev[] = {&r.t0, &r.spec, &r.stats, &r.ssb0, &r.ssb1, &r.end};
-            for (hipEvent_t *p : rev) HIP_TRY(hipEventCreateWithFlags(p, hipEventDisableSystemFence));
-        }
-        e->ring_created = true;
-    }
+    if (enabled)
+        if (int32_t rc = e->prof.create()) return rc;
     // calls made while profiling was off break the chain of SSB end markers (their seqs are not profiled), so the first
-    // profiled call after re-enabling takes a start marker of its own (enqueue's `chained`)
-    e->profiling = enabled != 0;
+    // profiled call after re-enabling takes a start marker of its own (Profiler::begin's `chained`)
+    e->prof.on = enabled != 0;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_get_timings(const sdrg_engine *ce, sdrg_timings *out) {
     if (!ce || !out) return fail(SDRG_E_INVALID, "null argument");
-    sdrg_engine *e = const_cast<sdrg_engine *>(ce);
-    if (e->ring_last < 0) return fail(SDRG_E_INVALID, "no profiled call yet");
-    int32_t rc = fold_slot(e, e->ring_last);
-    if (rc) return rc;
-    *out = e->last_timings;
+    Profiler &p = const_cast<sdrg_engine *>(ce)->prof;
+    if (p.last < 0) return fail(SDRG_E_INVALID, "no profiled call yet");
+    if (int32_t rc = p.fold_slot(p.last)) return rc;
+    *out = p.last_timings;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_get_timing_stats(const sdrg_engine *ce, sdrg_timings *mean, int32_t *count) {
     if (!ce || !mean) return fail(SDRG_E_INVALID, "null argument");
-    sdrg_engine *e = const_cast<sdrg_engine *>(ce);
-    int32_t rc = fold_all(e);
-    if (rc) return rc;
-    const double k = e->n_acc > 0 ? 1.0 / e->n_acc : 0.0;
-    mean->spectrum_ms = (float)(e->sum_spec * k);
-    mean->stats_ms = (float)(e->sum_stats * k);
-    mean->ssb_ms = (float)(e->n_ssb > 0 ? e->sum_ssb / e->n_ssb : 0.0);
-    mean->total_ms = (float)(e->sum_total * k);
-    if (count) *count = e->n_acc;
+    Profiler &p = const_cast<sdrg_engine *>(ce)->prof;
+    if (int32_t rc = p.fold_all()) return rc;
+    const double k = p.n_acc > 0 ? 1.0 / p.n_acc : 0.0;
+    mean->spectrum_ms = (float)(p.sum_spec * k);
+    mean->stats_ms = (float)(p.sum_stats * k);
+    mean->ssb_ms = (float)(p.n_ssb > 0 ? p.sum_ssb / p.n_ssb : 0.0);
+    mean->total_ms = (float)(p.sum_total * k);
+    if (count) *count = p.n_acc;
     return SDRG_OK;
 }
 
@@ -3189,59 +3209,36 @@ int32_t sdrg_engine_gather(sdrg_engine *e, sdrg_dist *d, int32_t root, const sdr
     if (g_foc) {
         geo = stats_geometry(e->fft_fs, e->fft_fc, n, e->fft_focus);
         if (geo.focus_len <= 0) return fail(SDRG_E_INVALID, "the focus window is empty (focus wider than the band)");
-        int32_t rc = ensure_device(&e->d_focus_stage, &e->focus_stage_elems, B * (size_t)geo.focus_len);
+        int32_t rc = ensure_device(&e->d_focus_stage, B * (size_t)geo.focus_len);
         if (rc) return rc;
     }
     if (!(g_rec || g_foc || g_spec || g_pcm)) return SDRG_OK;
-    const int slot = (int)(e->g_calls % sdrg_engine::GRING);
-    if (!e->ev_g[slot]) HIP_TRY(hipEventCreateWithFlags(&e->ev_g[slot], hipEventDisableTiming | hipEventDisableSystemFence));
     const bool on_stats = !g_pcm && e->last_async_stats && !e->s_gather;
     hipStream_t s = e->s_gather ? e->s_gather : g_pcm ? e->s_ap : on_stats ? e->s_stats : e->s_main;
-    if (e->s_gather) {  // lab: waits for every producer
+    if (e->s_gather || g_pcm) {  // on the lab's stream or the detector's: waits for every producer
         if ((g_rec || g_foc || g_spec) && e->last_in_main) HIP_TRY(hipStreamWaitEvent(s, e->last_in_main, 0));
-        if (g_rec && e->last_stats_end) HIP_TRY(hipStreamWaitEvent(s, e->last_stats_end, 0));
+        if (g_rec && e->sa.last_end) HIP_TRY(hipStreamWaitEvent(s, e->sa.last_end, 0));  // any async records
         if (g_pcm && e->last_in_ssb) HIP_TRY(hipStreamWaitEvent(s, e->last_in_ssb, 0));
-    } else if (g_pcm) {
-        if ((g_rec || g_foc || g_spec) && e->last_in_main) HIP_TRY(hipStreamWaitEvent(s, e->last_in_main, 0));
-        if (g_rec && e->last_stats_end) HIP_TRY(hipStreamWaitEvent(s, e->last_stats_end, 0));  // any async records
-        if (e->last_in_ssb) HIP_TRY(hipStreamWaitEvent(s, e->last_in_ssb, 0));
     }
     // records an earlier call's asynchronous statistics wrote (the last call ran no statistics there)
-    if (!e->s_gather && !g_pcm && !on_stats && g_rec && e->last_stats_end)
-        HIP_TRY(hipStreamWaitEvent(s, e->last_stats_end, 0));
-    // the focus staging buffer and RCCL's issue order: a gather follows the previous one even on another stream
-    if (e->ev_gather && s != e->s_last_gather) HIP_TRY(hipStreamWaitEvent(s, e->ev_gather, 0));
-    e->s_last_gather = s;
+    if (!e->s_gather && !g_pcm && !on_stats && g_rec && e->sa.last_end)
+        HIP_TRY(hipStreamWaitEvent(s, e->sa.last_end, 0));
+    if (int32_t rc = e->gathers.begin(s)) return rc;
     GatherItem items[4];
     int k = 0;
     if (g_rec) items[k++] = {b->records, b->records_out, B * sizeof(sdrg_frame_record)};
     if (g_foc) {
-        HIP_TRY(launch_focus_pack(b->focus_spectra, (int)B, n, geo.focus_lo, geo.focus_len, e->d_focus_stage, s));
-        items[k++] = {e->d_focus_stage, b->focus_out, B * (size_t)geo.focus_len * sizeof(float)};
+        HIP_TRY(launch_focus_pack(b->focus_spectra, (int)B, n, geo.focus_lo, geo.focus_len, e->d_focus_stage.p, s));
+        items[k++] = {e->d_focus_stage.p, b->focus_out, B * (size_t)geo.focus_len * sizeof(float)};
     }
     if (g_spec) items[k++] = {b->spectra, b->spectra_out, B * (size_t)n * sizeof(float)};
     if (g_pcm) items[k++] = {b->pcm, b->pcm_out, B * (size_t)plen * sizeof(int16_t)};
     int32_t rc = dist_gather(d, items, k, root, s);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(e->ev_g[slot], s));
-    e->ev_gather = e->ev_g[slot];
-    e->g_calls++;
-    // the buffers this gather reads, mapped to its slot; a slot re-recorded by a later gather still covers this one
-    // (gathers follow each other)
-    const std::pair<const void *, size_t> read[] = {
-        {g_rec ? (const void *)b->records : nullptr, B * sizeof(sdrg_frame_record)},
-        {g_foc ? (const void *)b->focus_spectra : nullptr, B * (size_t)n * sizeof(float)},
-        {g_spec ? (const void *)b->spectra : nullptr, B * (size_t)n * sizeof(float)},
-        {g_pcm ? (const void *)b->pcm : nullptr, B * (size_t)plen * sizeof(int16_t)}};
-    for (const auto &r : read) {
-        if (!r.first || !r.second) continue;
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(r.first), hi = lo + r.second;
-        bool found = false;
-        for (sdrg_engine::GBuf &g : e->g_bufs)
-            if (g.lo == lo && g.hi == hi) g.slot = slot, g.seq = e->g_calls - 1, found = true;
-        if (!found) e->g_bufs.push_back({lo, hi, slot, e->g_calls - 1});
-    }
-    return SDRG_OK;
+    return e->gathers.end(s, {{g_rec ? (const void *)b->records : nullptr, B * sizeof(sdrg_frame_record)},
+                               {g_foc ? (const void *)b->focus_spectra : nullptr, B * (size_t)n * sizeof(float)},
+                               {g_spec ? (const void *)b->spectra : nullptr, B * (size_t)n * sizeof(float)},
+                               {g_pcm ? (const void *)b->pcm : nullptr, B * (size_t)plen * sizeof(int16_t)}});
 }
 
 int32_t sdrg_engine_gather_records(sdrg_engine *e, sdrg_dist *d, int32_t root, const sdrg_frame_record *records,
@@ -3280,12 +3277,8 @@ int32_t sdrg_engine_gather_pcm(sdrg_engine *e, sdrg_dist *d, int32_t root, const
 
 int32_t sdrg_engine_reset_timing_stats(sdrg_engine *e) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    int32_t rc = fold_all(e);
-    if (rc) return rc;
-    e->sum_spec = e->sum_stats = e->sum_ssb = e->sum_total = 0;
-    e->n_acc = e->n_ssb = 0;
-    // a pipelined call's SSB interval starts at the previous call's end marker: the window's first call has none
-    e->seq_reset = e->calls_total;
+    if (int32_t rc = e->prof.fold_all()) return rc;
+    e->prof.reset(e->calls_total);
     return SDRG_OK;
 }
 
