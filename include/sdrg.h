@@ -1286,6 +1286,111 @@ int32_t sdrg_engine_listen_sideband_host(sdrg_engine *eng, int32_t steps, const 
                                          int32_t *n_out, sdrg_squelch_record *squelch_records,
                                          sdrg_agc_record *agc_records);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the IQ correction stage, the DC offset and the gain / phase imbalance of a
+ * receiver's quadrature mixer estimated and removed per stream, ahead of every other stage.  Per stream, the n raw
+ * samples of a call, in any of the four formats (the format may change from call to call), are cut into blocks of S
+ * samples at the global indices that are multiples of S.  Each completed block's moments move a DC estimate (dr, di)
+ * and a balance estimate (wr, wi); block k is corrected under a ramp from the parameters after block k - 2 to those after
+ * block k - 1, so there is no step at a block seam and no decision reaches back into the block that produced it: the
+ * stage adds no delay and out has one CF32 sample per input sample.  Over the whole life of a stream (the calls'
+ * samples concatenated, whatever their lengths) the result is that of one call.  All arithmetic is float, every
+ * product, sum and quotient rounded on its own, unless "double" is stated; denormals are kept.  A non-finite sample
+ * makes that stream's outputs and records unspecified from then on.  The balance rule is the blind estimate for
+ * x = K1 z + K2 conj(z) with circular z: E[x^2] / E|x|^2 = 2 w / (1 + |w|^2) with w = K2 / conj(K1), and
+ * y = x - w conj(x) cancels the image.  The balance is one complex number per stream: it does not depend on frequency.
+ *   config     dc_tau_blocks, balance_tau_blocks finite, >= 0; floor_db finite; mode SDRG_IQCORR_DC, SDRG_IQCORR_BALANCE
+ *              or both (0 and other bits are refused); block S a power of two in [SDRG_IQCORR_MIN_BLOCK,
+ *              SDRG_IQCORR_MAX_BLOCK]; max_in in [1, 2^20]: every call's n <= in_stride <= max_in.  A rejected
+ *              set_iqcorr changes nothing; an accepted one, and sdrg_engine_iqcorr_reset, restart every stream: g = 0
+ *              and the state dr, di, wr, wi, A, B, P, seeded all zero.
+ *   design     sdrg_iqcorr_design, in double, each result rounded to float once: beta_x = 1 - exp(-1 / tau_x), and
+ *              exactly 1.0f at tau_x = 0; floor_thr = 10^(floor_db / 10), refused unless it is a finite positive float.
+ *   sample     z = (zr, zi) is the format's scaled value, as the DDC reads it: CS8 v / 128, CU8 (v - 127.4f) * (1 /
+ *              128), CS16 v / 32768, CF32 as it lies.
+ *   moments    T(.) is the adjacent-pair tree over a block's S values in order: q'[i] = q[2 i] + q[2 i + 1] until one
+ *              value is left; r = 1 / S.  Per sample q1 = zr zr, q2 = zi zi, e = q1 - q2, s = q1 + q2, c = zr zi.  Per
+ *              block mr = T(zr) r, mi = T(zi) r, E = T(e) r, W = T(s) r, C = T(c) r, and, centred on the block's own
+ *              mean, a = E - (mr mr - mi mi), b = C - mr mi, p = W - (mr mr + mi mi).  A block's moments depend on its
+ *              own samples only.
+ *   step       for each completed block, in order.  With SDRG_IQCORR_DC: dr = dr + beta_dc (mr - dr), or dr = mr when
+ *              beta_dc is 1; the same for di with mi.  With SDRG_IQCORR_BALANCE: if p < floor_thr the block is held
+ *              (nothing of the balance moves, held counts one); otherwise, if not yet seeded, (A, B, P) = (a, b, p) and
+ *              seeded = 1, else A = A + beta_bal (a - A) and the same for B with b and P with p (also at beta_bal = 1);
+ *              then cr = A / P, ci = (2 B) / P, m = cr cr + ci ci; if m <= 0.25f, d = 1 + sqrtf(1 - m), wr = cr / d,
+ *              wi = ci / d; if m > 0.25f the block is held: wr and wi stay where they are and held counts one.
+ *              theta_k = (dr, di, wr, wi) after global block k; theta_-1 = theta_-2 = 0.
+ *   output     the sample at in-block index i of global block k: t = (float)(i + 1) * r; each of the four parameters is
+ *              theta_(k-2) + (theta_(k-1) - theta_(k-2)) * t; ur = zr - dr, ui = zi - di; yr = ur - (wr ur + wi ui),
+ *              yi = ui - (wi ur - wr ui).  With DC only the w terms are still evaluated, with w = +0; with BALANCE only
+ *              dr = di = +0.  out [n_streams][in_stride][2] float, 8-byte aligned: every byte is written by every
+ *              call, zero from n on.  out may be iq itself only when fmt is CF32; any other overlap is undefined.  n = 0
+ *              is a valid call: it writes out and the records and leaves the state where it is.
+ *   records    sdrg_iqcorr_record [n_streams], written by every call: dc_re, dc_im, w_re, w_im are theta after the last
+ *              block completed so far; power is P; image_db = 10.0f * log10f(wr wr + wi wi + 1e-20f) with glibc's
+ *              log10f bit for bit (the squelch's); held_blocks is how many of the blocks this call completed were held;
+ *              seeded is the state's flag.  *n_blocks = floor((g + n) / S) - floor(g / S) is set on the host before the
+ *              call returns.
+ *   state      per stream the scaled samples of the block in progress (S - 1 pairs of floats), the two last theta, A,
+ *              B, P and seeded, in device memory (allocated at the first iqcorr call), in two halves a call reads and
+ *              writes in turn; per engine g, advanced by n once the call's launches have been issued: a failed call
+ *              commits nothing.  Calls shorter than a block accumulate; any number of calls may share one block.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_IQCORR_DC 1
+#define SDRG_IQCORR_BALANCE 2
+#define SDRG_IQCORR_MIN_BLOCK 64
+#define SDRG_IQCORR_MAX_BLOCK 1024
+#define SDRG_IQCORR_MAX_IN 1048576
+typedef struct sdrg_iqcorr_config {
+    double dc_tau_blocks;
+    double balance_tau_blocks;
+    double floor_db;       /* blocks whose centred power is under 10^(floor_db / 10) do not move the balance */
+    int32_t mode;
+    int32_t block;
+    int32_t max_in;
+} sdrg_iqcorr_config;
+
+typedef struct sdrg_iqcorr_record {
+    float dc_re, dc_im, w_re, w_im;
+    float power;
+    float image_db;
+    int32_t held_blocks;
+    int32_t seeded;
+} sdrg_iqcorr_record;
+
+/* Host-only, no device.  After the checks of set_iqcorr: the three design values above; any of the three pointers may
+ * be NULL. */
+int32_t sdrg_iqcorr_design(const sdrg_iqcorr_config *cfg, float *beta_dc, float *beta_bal, float *floor_thr);
+/* Host-only: *tile = max(512, block), how many consecutive samples one workgroup takes: of the moments kernel those of
+ * the global indices [k tile, (k + 1) tile), of the pass kernel those of the call's indices [k tile, (k + 1) tile). */
+int32_t sdrg_iqcorr_geometry(int32_t block, int32_t *tile);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the stage.  An iqcorr call while it is off returns SDRG_E_INVALID and
+ * writes nothing. */
+int32_t sdrg_engine_set_iqcorr(sdrg_engine *eng, const sdrg_iqcorr_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its three design values and g, the samples every stream has
+ * consumed since the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_iqcorr(const sdrg_engine *eng, sdrg_iqcorr_config *cfg, float *beta_dc, float *beta_bal,
+                               float *floor_thr, uint64_t *samples_consumed);
+int32_t sdrg_engine_iqcorr_reset(sdrg_engine *eng);
+/* iq: n_streams rows of in_stride raw samples in fmt, aligned as the format's components, of which the first n of every
+ * row are this call's (0 <= n <= in_stride <= max_in); out [n_streams][in_stride][2] float; records [n_streams] or
+ * NULL; all in device memory.  Stream rules and waiting as sdrg_engine_squelch_device.  To correct ahead of the DDC or
+ * the channelizer, pass out to their _device calls as SDRG_IQ_CF32. */
+int32_t sdrg_engine_iqcorr_device(sdrg_engine *eng, const void *iq, int32_t fmt, int32_t in_stride, int32_t n, void *out,
+                                  sdrg_iqcorr_record *records, int32_t *n_blocks);
+/* Host buffers of the same shapes, synchronous; all n_streams * in_stride samples of iq are copied. */
+int32_t sdrg_engine_iqcorr_host(sdrg_engine *eng, const void *iq, int32_t fmt, int32_t in_stride, int32_t n, void *out,
+                                sdrg_iqcorr_record *records, int32_t *n_blocks);
+/* Correct, then look and listen: one frame per stream (n = in_stride = samples_per_reading) is corrected into a device
+ * buffer the engine owns, sdrg_engine_process_host's stages run on those rows as SDRG_IQ_CF32, and what process_host
+ * copies back comes back, plus iq_records [n_streams] unless NULL.  SDRG_E_INVALID, with no stage moved, if the stage
+ * is off or its max_in is smaller than the frame, and under sdrg_engine_process_host's own conditions.
+ * sdrg_engine_process_host itself never corrects, whether or not the stage is set. */
+int32_t sdrg_engine_iqcorr_process_host(sdrg_engine *eng, const void *iq, int32_t fmt, int32_t stages, float *spectra,
+                                        sdrg_frame_record *records, int16_t *pcm, int64_t now_ms,
+                                        sdrg_iqcorr_record *iq_records);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

@@ -371,6 +371,30 @@ void squelch_design(const sdrg_squelch_config &c, float *open_thr, float *close_
     if (beta) *beta = c.tau_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.tau_blocks)) : 1.0f;
 }
 
+// The IQ correction stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *iqcorr_check(const sdrg_iqcorr_config &c) {
+    if (!(c.dc_tau_blocks >= 0.0) || !std::isfinite(c.dc_tau_blocks)) return "dc_tau_blocks must be >= 0 and finite";
+    if (!(c.balance_tau_blocks >= 0.0) || !std::isfinite(c.balance_tau_blocks))
+        return "balance_tau_blocks must be >= 0 and finite";
+    if (!std::isfinite(c.floor_db)) return "floor_db must be finite";
+    if (c.mode == 0 || (c.mode & ~(SDRG_IQCORR_DC | SDRG_IQCORR_BALANCE)) != 0)
+        return "mode must be SDRG_IQCORR_DC, SDRG_IQCORR_BALANCE or both";
+    if (c.block < SDRG_IQCORR_MIN_BLOCK || c.block > SDRG_IQCORR_MAX_BLOCK || (c.block & (c.block - 1)) != 0)
+        return "block must be a power of two in [64, 1024]";
+    if (c.max_in < 1 || c.max_in > SDRG_IQCORR_MAX_IN) return "max_in outside [1, 2^20]";
+    float floor_thr;
+    iqcorr_design(c, nullptr, nullptr, &floor_thr);
+    if (!std::isfinite(floor_thr) || !(floor_thr > 0.0f)) return "10^(floor_db / 10) is not a finite, positive float";
+    return nullptr;
+}
+
+// The IQ correction stage's constants (sdrg.h), in double, each rounded to float once
+void iqcorr_design(const sdrg_iqcorr_config &c, float *beta_dc, float *beta_bal, float *floor_thr) {
+    if (beta_dc) *beta_dc = c.dc_tau_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.dc_tau_blocks)) : 1.0f;
+    if (beta_bal) *beta_bal = c.balance_tau_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.balance_tau_blocks)) : 1.0f;
+    if (floor_thr) *floor_thr = (float)std::pow(10.0, c.floor_db / 10.0);
+}
+
 // The AGC stage's configuration rules (sdrg.h): nullptr, or what is wrong
 const char *agc_check(const sdrg_agc_config &c) {
     if (!std::isfinite(c.target) || !std::isfinite((float)c.target) || !((float)c.target > 0.0f))

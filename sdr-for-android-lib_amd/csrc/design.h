@@ -37,6 +37,10 @@ bool resample_ratio(uint64_t in_num, uint64_t in_den, uint64_t out_hz, int *inte
 // Squelch stage: the configuration rules (nullptr = valid) and open_thr, close_thr and beta (any pointer may be null)
 const char *squelch_check(const sdrg_squelch_config &cfg);
 void squelch_design(const sdrg_squelch_config &cfg, float *open_thr, float *close_thr, float *beta);
+// IQ correction stage: the configuration rules (nullptr = valid) and beta_dc, beta_bal and floor_thr (any pointer may
+// be null)
+const char *iqcorr_check(const sdrg_iqcorr_config &cfg);
+void iqcorr_design(const sdrg_iqcorr_config &cfg, float *beta_dc, float *beta_bal, float *floor_thr);
 // AGC stage: the configuration rules (nullptr = valid) and the five design values (any pointer may be null)
 struct AgcDesign {
     float max_gain, init_gain, floor_thr, alpha_a, alpha_d;

@@ -245,6 +245,22 @@ struct AgcStage : BlockStage<sdrg_agc_config> {
     AgcDesign des{};      // agc_design of cfg
 };
 
+// IQ correction stage (sdrg_engine_set_iqcorr / iqcorr_device / iqcorr_host / iqcorr_process_host; iqcorr.hip)
+struct IqcorrStage {
+    sdrg_iqcorr_config cfg{};
+    bool set = false;
+    BlockCursor cur;
+    float beta_dc = 0.0f, beta_bal = 0.0f, floor_thr = 0.0f;  // iqcorr_design of cfg
+    // halves of [n_streams][2 S + IQCORR_STATE_HEAD]: the twelve words, the block's scaled samples so far
+    DevicePingPong<float> state;
+    DeviceBuf<float> blk;  // [the most blocks a call completes]: [5][n_streams] moments, then as many [4][n_streams] theta
+    // iqcorr_process_host's: the corrected frame, [n_streams][samples_per_reading][2], and the records
+    DeviceBuf<float> rows;
+    DeviceBuf<sdrg_iqcorr_record> rec;
+    size_t half(int B) const { return (size_t)B * (size_t)(2 * cfg.block + IQCORR_STATE_HEAD); }
+    size_t blocks() const { return (size_t)BlockCursor::cap(cfg.max_in, cfg.block); }
+};
+
 // sideband stage (sdrg_engine_set_sideband / sideband_device / sideband_host / listen_sideband_host; sideband.hip)
 struct SidebandStage {
     sdrg_sideband_config cfg{};
@@ -526,7 +542,7 @@ struct sdrg_engine {
     bool has_cbs = false;
     sdrg_callbacks cbs{};
     // The device calls of the stages below (display, integration, peaks, DDC, demodulator, channelizer, resampler,
-    // squelch, AGC, sideband) write their outputs on s_main after the last process call's end marker, which is all a
+    // squelch, AGC, sideband, IQ correction) write their outputs on s_main after the last process call's end marker, which is all a
     // stream other than s_main follows.  Each sets outputs_unmarked; sdrg_engine_wait_outputs then records ev_outputs
     // on s_main for that stream to wait on.
     Event ev_outputs;  // created at the first such wait
@@ -543,8 +559,9 @@ struct sdrg_engine {
     SquelchStage sq;
     AgcStage agc;
     SidebandStage sb;
+    IqcorrStage iqc;
     // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host,
-    // squelch_host, agc_host and the chains), as bytes: the caller's input, and the rows it gets back (with the squelch's
+    // squelch_host, agc_host, iqcorr_host and the chains), as bytes: the caller's input, and the rows it gets back (with the squelch's
     // and the AGC's records behind them).  One pair serves them all, as spec_in does its
     // four: each of them waits on s_main before it returns, so no two uses overlap, and a call that fails after its
     // copy was enqueued leaves that copy ordered on s_main before whatever the next call enqueues there.
@@ -668,7 +685,7 @@ int32_t ensure_nco_table(sdrg_engine *e) {
     return upload_floats(&e->d_nco_tab, tab, "NCO table");
 }
 
-// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband -------------------------
+// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband, IQ correction ----------
 //
 // A call of a stage goes through three steps.  x_resolve makes every refusal and touches nothing; what it finds goes
 // into the stage's XCall.  x_reserve does everything that can fail without a launch (the stage's device buffers, the
@@ -1840,18 +1857,152 @@ int32_t sdrg_engine_synchronize(sdrg_engine *e) {
     return SDRG_OK;
 }
 
-int32_t sdrg_engine_process_host(sdrg_engine *e, const void *iq, int32_t format, int32_t stages, float *spectra,
-                                 sdrg_frame_record *records, int16_t *pcm, int64_t now_ms) {
+// ---- IQ correction stage (iqcorr.hip) ------------------------------------------------------------------------------
+
+int32_t sdrg_iqcorr_design(const sdrg_iqcorr_config *cfg, float *beta_dc, float *beta_bal, float *floor_thr) {
+    if (!cfg) return fail(SDRG_E_INVALID, "null iqcorr config");
+    if (const char *bad = iqcorr_check(*cfg)) return fail(SDRG_E_INVALID, "iqcorr: %s", bad);
+    iqcorr_design(*cfg, beta_dc, beta_bal, floor_thr);
+    return SDRG_OK;
+}
+
+int32_t sdrg_iqcorr_geometry(int32_t block, int32_t *tile) {
+    if (!tile) return fail(SDRG_E_INVALID, "null tile");
+    if (block < IQCORR_MIN_BLOCK || block > BLOCK_MAX || (block & (block - 1)) != 0)
+        return fail(SDRG_E_INVALID, "iqcorr: block must be a power of two in [64, 1024]");
+    *tile = block_tile(block);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_iqcorr(sdrg_engine *e, const sdrg_iqcorr_config *cfg) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!iq) return fail(SDRG_E_INVALID, "null iq");
+    IqcorrStage &s = e->iqc;
+    if (cfg) {
+        if (const char *bad = iqcorr_check(*cfg)) return fail(SDRG_E_INVALID, "iqcorr: %s", bad);
+        s.cfg = *cfg;
+        iqcorr_design(*cfg, &s.beta_dc, &s.beta_bal, &s.floor_thr);
+    }
+    s.set = cfg != nullptr;
+    s.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_iqcorr(const sdrg_engine *e, sdrg_iqcorr_config *cfg, float *beta_dc, float *beta_bal,
+                               float *floor_thr, uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    const IqcorrStage &s = e->iqc;
+    if (!s.set) return fail(SDRG_E_INVALID, "no iqcorr configuration set");
+    if (cfg) *cfg = s.cfg;
+    if (beta_dc) *beta_dc = s.beta_dc;
+    if (beta_bal) *beta_bal = s.beta_bal;
+    if (floor_thr) *floor_thr = s.floor_thr;
+    if (samples_consumed) *samples_consumed = s.cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_iqcorr_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->iqc.cur.restart();
+    return SDRG_OK;
+}
+
+struct IqcorrCall : StageCall {
+    int fmt = 0;
+};
+
+static int32_t iqc_resolve(const sdrg_engine *e, int32_t fmt, int32_t in_stride, int32_t n, sdrg_iqcorr_record *records,
+                           IqcorrCall *c) {
+    const IqcorrStage &s = e->iqc;
+    if (int32_t rc = require_set(s.set, "iqcorr")) return rc;
+    const int bps = bytes_per_sample(fmt);
+    if (!bps) return fail(SDRG_E_INVALID, "unknown iq format %d", fmt);
+    if (n < 0 || n > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "iqcorr: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
+    if (in_stride < std::max(n, 1) || in_stride > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "iqcorr: in_stride %d outside [max(n, 1) = %d, max_in = %d]", in_stride,
+                    std::max(n, 1), s.cfg.max_in);
+    c->fmt = fmt;
+    c->n = n;
+    c->in_stride = in_stride;
+    c->cap = in_stride;
+    c->n_out = s.cur.blocks(n, s.cfg.block);
+    c->in_bytes = (size_t)e->n_streams * (size_t)in_stride * (size_t)bps;
+    c->out_bytes = (size_t)e->n_streams * (size_t)in_stride * 2 * sizeof(float);
+    c->aux = records;
+    c->aux_bytes = (size_t)e->n_streams * sizeof(*records);
+    return SDRG_OK;
+}
+
+static int32_t iqc_reserve(sdrg_engine *e, const IqcorrCall &) {
+    IqcorrStage &s = e->iqc;
+    const int32_t rc = ensure_halves(&s.state, s.half(e->n_streams));
+    return rc ? rc : ensure_device(&s.blk, (size_t)e->n_streams * s.blocks() * 9);
+}
+
+// The three launches on the main stream, the cursor left where it is: iq (rows of in_stride raw samples), out (rows of
+// in_stride complex samples) and c.aux, the records or null, in device memory.
+static int32_t iqc_enqueue(sdrg_engine *e, const IqcorrCall &c, const void *iq, void *out) {
+    IqcorrStage &s = e->iqc;
+    const size_t half = s.half(e->n_streams);
+    IqcorrParams p{};
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.block = s.cfg.block;
+    p.mode = s.cfg.mode;
+    p.off = s.cur.offset(s.cfg.block);
+    p.n_blocks = c.n_out;
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.beta_dc = s.beta_dc;
+    p.beta_bal = s.beta_bal;
+    p.floor_thr = s.floor_thr;
+    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    p.state_new = s.state.next(s.cur, half);
+    p.mom = s.blk.p;
+    p.theta = s.blk.p + (size_t)e->n_streams * s.blocks() * 5;
+    p.records = static_cast<sdrg_iqcorr_record *>(c.aux);
+    HIP_TRY(launch_iqcorr(iq, c.fmt, e->n_streams, p, static_cast<float *>(out), e->s_main));
+    return SDRG_OK;
+}
+
+static void iqc_commit(sdrg_engine *e, const IqcorrCall &c) {
+    e->iqc.cur.advance(c.n);  // a call without samples wrote out and the records only: the state stays where it is
+    e->outputs_unmarked = true;
+}
+
+static int32_t iqc_launch(sdrg_engine *e, const IqcorrCall &c, const void *iq, void *out) {
+    const int32_t rc = iqc_enqueue(e, c, iq, out);
+    if (!rc) iqc_commit(e, c);
+    return rc;
+}
+
+static constexpr auto iqc_stage =
+    &stage_call<IqcorrCall, iqc_resolve, iqc_reserve, iqc_launch, int32_t, int32_t, int32_t, sdrg_iqcorr_record *>;
+
+int32_t sdrg_engine_iqcorr_device(sdrg_engine *e, const void *iq, int32_t fmt, int32_t in_stride, int32_t n, void *out,
+                                  sdrg_iqcorr_record *records, int32_t *n_blocks) {
+    return iqc_stage(e, "iq", iq, out, n_blocks, false, fmt, in_stride, n, records);
+}
+
+int32_t sdrg_engine_iqcorr_host(sdrg_engine *e, const void *iq, int32_t fmt, int32_t in_stride, int32_t n, void *out,
+                                sdrg_iqcorr_record *records, int32_t *n_blocks) {
+    return iqc_stage(e, "iq", iq, out, n_blocks, true, fmt, in_stride, n, records);
+}
+
+// sdrg_engine_process_host, and sdrg_engine_iqcorr_process_host with `corr`, the resolved correction of the frame: the
+// stages then read the corrected rows in e->iqc.rows as CF32, and the correction's cursor moves once they are enqueued.
+static int32_t process_host_frames(sdrg_engine *e, const void *iq, int32_t format, int32_t stages, float *spectra,
+                                   sdrg_frame_record *records, int16_t *pcm, int64_t now_ms, IqcorrCall *corr,
+                                   sdrg_iqcorr_record *iq_records) {
     const int bps = bytes_per_sample(format);
-    if (!bps) return fail(SDRG_E_INVALID, "unknown iq format %d", format);
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     const int n = e->cfg.samples_per_reading;
     const int B = e->n_streams;
     const size_t iq_bytes = (size_t)B * n * bps;
     int32_t rc = ensure_device(&e->d_iq_stage, iq_bytes);
+    if (!rc && corr) rc = iqc_reserve(e, *corr);
+    if (!rc && corr) rc = ensure_device(&e->iqc.rows, (size_t)B * n * 2);
+    if (!rc && corr) rc = ensure_device(&e->iqc.rec, (size_t)B);
     if (rc) return rc;
     const bool want_cb = e->has_cbs;
     const bool do_spec = stages & SDRG_STAGE_SPECTRUM, do_stats = stages & SDRG_STAGE_STATS,
@@ -1870,9 +2021,23 @@ int32_t sdrg_engine_process_host(sdrg_engine *e, const void *iq, int32_t format,
         if (rc) return rc;
     }
     HIP_TRY(hipMemcpyAsync(e->d_iq_stage.p, iq, iq_bytes, hipMemcpyHostToDevice, e->s_main));
-    rc = enqueue(e, e->d_iq_stage.p, format, stages, do_spec ? e->d_spec_stage.p : nullptr,
+    const void *frames = e->d_iq_stage.p;
+    if (corr) {
+        corr->aux = e->iqc.rec.p;
+        rc = iqc_enqueue(e, *corr, e->d_iq_stage.p, e->iqc.rows.p);
+        if (rc) return rc;
+        frames = e->iqc.rows.p;
+        format = SDRG_IQ_CF32;
+    }
+    rc = enqueue(e, frames, format, stages, do_spec ? e->d_spec_stage.p : nullptr,
                  do_stats ? e->d_rec_stage.p : nullptr, do_ssb ? e->d_pcm_stage.p : nullptr, now_ms, true);
     if (rc) return rc;
+    if (corr) {
+        iqc_commit(e, *corr);
+        if (iq_records)
+            HIP_TRY(hipMemcpyAsync(iq_records, e->iqc.rec.p, sizeof(sdrg_iqcorr_record) * (size_t)B, hipMemcpyDeviceToHost,
+                                   e->s_main));
+    }
     if (do_spec) e->host_spec_n = n;  // sdrg_engine_display_host(spectra = NULL) reads these spectra
     float *h_spec = spectra;
     sdrg_frame_record *h_rec = records;
@@ -1912,6 +2077,28 @@ int32_t sdrg_engine_process_host(sdrg_engine *e, const void *iq, int32_t format,
         dispatch_callbacks(e, stages, pcm_len);
     }
     return SDRG_OK;
+}
+
+int32_t sdrg_engine_process_host(sdrg_engine *e, const void *iq, int32_t format, int32_t stages, float *spectra,
+                                 sdrg_frame_record *records, int16_t *pcm, int64_t now_ms) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq) return fail(SDRG_E_INVALID, "null iq");
+    if (!bytes_per_sample(format)) return fail(SDRG_E_INVALID, "unknown iq format %d", format);
+    return process_host_frames(e, iq, format, stages, spectra, records, pcm, now_ms, nullptr, nullptr);
+}
+
+int32_t sdrg_engine_iqcorr_process_host(sdrg_engine *e, const void *iq, int32_t fmt, int32_t stages, float *spectra,
+                                        sdrg_frame_record *records, int16_t *pcm, int64_t now_ms,
+                                        sdrg_iqcorr_record *iq_records) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq) return fail(SDRG_E_INVALID, "null iq");
+    if (int32_t rc = require_set(e->iqc.set, "iqcorr")) return rc;
+    const int n = e->cfg.samples_per_reading;
+    if (e->iqc.cfg.max_in < n)
+        return fail(SDRG_E_INVALID, "iqcorr max_in %d smaller than the frame's %d samples", e->iqc.cfg.max_in, n);
+    IqcorrCall c;
+    if (int32_t rc = iqc_resolve(e, fmt, n, n, nullptr, &c)) return rc;
+    return process_host_frames(e, iq, fmt, stages, spectra, records, pcm, now_ms, &c, iq_records);
 }
 
 // ---- display stage (display.hip) ----------------------------------------------------------------------------------

@@ -300,6 +300,30 @@ struct AgcParams : BlockParams {
 };
 hipError_t launch_agc(const float *chan, int n_streams, const AgcParams &p, float *out, hipStream_t stream);
 
+// IQ correction stage (iqcorr.hip): per stream the n raw samples at iq + stream * in_stride (in fmt) are the positions
+// [off, off + n) of a run of blocks of `block` samples, as the block stages' are.  state_old / state_new [n_streams]
+// [2 block + IQCORR_STATE_HEAD] floats: {dr, di, wr, wi} after the last completed block, the same after the one before,
+// {A, B, P, seeded (int bits)}, then the scaled samples so far of the block in progress; fresh: state_old is not read
+// (zeros, and off is 0).  mom [blocks][5][n_streams] and theta [blocks][4][n_streams] floats are scratch: the completed
+// blocks' moments, and the four parameters after each.  Writes out [n_streams][in_stride][2] whole (zeros from n on; out
+// may be iq at CF32), and, if n > 0, state_new; records [n_streams] unless nullptr.  n_streams, log2_block, tile and
+// inv_block are the launcher's.
+struct IqcorrParams {
+    int n, in_stride, block, mode, off, n_blocks, fresh;
+    float beta_dc, beta_bal, floor_thr;
+    const float *state_old;
+    float *state_new;
+    float *mom, *theta;
+    sdrg_iqcorr_record *records;
+    int n_streams, log2_block, tile;
+    float inv_block;
+};
+constexpr int IQCORR_STATE_HEAD = 12;
+constexpr int IQCORR_MIN_BLOCK = SDRG_IQCORR_MIN_BLOCK;
+static_assert(SDRG_IQCORR_MAX_BLOCK == BLOCK_MAX && SDRG_IQCORR_MAX_IN == BLOCK_MAX_IN && IQCORR_MIN_BLOCK >= 64,
+              "the block stages' positions and butterfly: a block is at least a wave's 32 pairs");
+hipError_t launch_iqcorr(const void *iq, int fmt, int n_streams, IqcorrParams p, float *out, hipStream_t stream);
+
 // Sideband stage (sideband.hip): per stream and output j, A = sum_k cr[k] zr[first + j decim - k] and Bm = sum_k ci[k]
 // zi[first + j decim - k], z the n complex samples at chan + stream * in_stride (float2); u = A - Bm, l = A + Bm.  The
 // history holds samples, [taps - 1][2] per stream.  Writes out [n_streams][cap] (u gain, l gain, or at mode BOTH the

@@ -150,6 +150,9 @@ EXPORTS = [
     "sdrg_sideband_design", "sdrg_sideband_geometry", "sdrg_engine_set_sideband", "sdrg_engine_get_sideband",
     "sdrg_engine_sideband_reset", "sdrg_engine_sideband_max_out", "sdrg_engine_sideband_device",
     "sdrg_engine_sideband_host", "sdrg_engine_listen_sideband_host",
+    "sdrg_iqcorr_design", "sdrg_iqcorr_geometry", "sdrg_engine_set_iqcorr", "sdrg_engine_get_iqcorr",
+    "sdrg_engine_iqcorr_reset", "sdrg_engine_iqcorr_device", "sdrg_engine_iqcorr_host",
+    "sdrg_engine_iqcorr_process_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -247,6 +250,20 @@ class SquelchConfig(ctypes.Structure):
 
 # sdrg_squelch_record
 SquelchRecord = np.dtype([("level", "<f4"), ("level_db", "<f4"), ("open", "<i4"), ("open_blocks", "<i4")])
+
+
+class IqcorrConfig(ctypes.Structure):
+    """sdrg_iqcorr_config: the IQ correction stage's two time constants, floor, mode, block length and row length
+    (include/sdrg.h)."""
+    _fields_ = [("dc_tau_blocks", ctypes.c_double), ("balance_tau_blocks", ctypes.c_double),
+                ("floor_db", ctypes.c_double), ("mode", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("max_in", ctypes.c_int32)]
+
+
+# sdrg_iqcorr_record
+IqcorrRecord = np.dtype([("dc_re", "<f4"), ("dc_im", "<f4"), ("w_re", "<f4"), ("w_im", "<f4"), ("power", "<f4"),
+                         ("image_db", "<f4"), ("held_blocks", "<i4"), ("seeded", "<i4")])
+IQCORR_DC, IQCORR_BALANCE = 1, 2
 
 
 class AgcConfig(ctypes.Structure):
@@ -510,6 +527,16 @@ def load() -> ctypes.CDLL:
         "sdrg_squelch_design": (_I32, [ctypes.POINTER(SquelchConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
                                        ctypes.POINTER(_F)]),
         "sdrg_squelch_geometry": (_I32, [_I32, ctypes.POINTER(_I32)]),
+        "sdrg_iqcorr_design": (_I32, [ctypes.POINTER(IqcorrConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
+                                      ctypes.POINTER(_F)]),
+        "sdrg_iqcorr_geometry": (_I32, [_I32, ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_iqcorr": (_I32, [P, ctypes.POINTER(IqcorrConfig)]),
+        "sdrg_engine_get_iqcorr": (_I32, [P, ctypes.POINTER(IqcorrConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
+                                          ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_iqcorr_reset": (_I32, [P]),
+        "sdrg_engine_iqcorr_device": (_I32, [P, P, _I32, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_iqcorr_host": (_I32, [P, P, _I32, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_iqcorr_process_host": (_I32, [P, P, _I32, _I32, P, P, P, _I64, P]),
         "sdrg_engine_set_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig)]),
         "sdrg_engine_get_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
                                            ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_uint64)]),
@@ -801,6 +828,24 @@ def squelch_geometry(block: int) -> int:
     (by the call's index) for a block length."""
     t = _I32()
     _check(load().sdrg_squelch_geometry(block, ctypes.byref(t)), "squelch_geometry")
+    return t.value
+
+
+def iqcorr_design(**fields) -> dict:
+    """The IQ correction stage's design for a configuration (host-side, no device): beta_dc, beta_bal and floor_thr as
+    np.float32.  The fields are sdrg_iqcorr_config's (fields left out are 0)."""
+    c = _filled(IqcorrConfig, "iqcorr", fields)
+    bd, bb, fl = _F(), _F(), _F()
+    _check(load().sdrg_iqcorr_design(ctypes.byref(c), ctypes.byref(bd), ctypes.byref(bb), ctypes.byref(fl)),
+           "iqcorr_design")
+    return {"beta_dc": np.float32(bd.value), "beta_bal": np.float32(bb.value), "floor_thr": np.float32(fl.value)}
+
+
+def iqcorr_geometry(block: int) -> int:
+    """tile: consecutive samples per workgroup of the IQ correction's moments kernel (by global index) and of its pass
+    kernel (by the call's index) for a block length."""
+    t = _I32()
+    _check(load().sdrg_iqcorr_geometry(block, ctypes.byref(t)), "iqcorr_geometry")
     return t.value
 
 
@@ -1397,6 +1442,60 @@ class Engine:
         audio, the records)."""
         return self._chain_with_records(load().sdrg_engine_ddc_squelch_demod_resample_host,
                                         "ddc_squelch_demod_resample_host", iq, fmt, self._resample_out)
+
+    # ---- IQ correction stage ----------------------------------------------------------------------
+    def set_iqcorr(self, **fields) -> None:
+        """sdrg_engine_set_iqcorr: dc_tau_blocks, balance_tau_blocks, floor_db, mode, block, max_in (fields left out
+        are 0); set_iqcorr(off=True) switches the stage off."""
+        self._set_stage(IqcorrConfig, "iqcorr", fields)
+
+    def iqcorr_config(self) -> dict:
+        """The configuration in force, plus its design (beta_dc, beta_bal, floor_thr as np.float32) and
+        samples_consumed."""
+        c, bd, bb, fl, g = IqcorrConfig(), _F(), _F(), _F(), ctypes.c_uint64()
+        _check(load().sdrg_engine_get_iqcorr(self._h, ctypes.byref(c), ctypes.byref(bd), ctypes.byref(bb),
+                                             ctypes.byref(fl), ctypes.byref(g)), "get_iqcorr")
+        return dict(_as_dict(c), beta_dc=np.float32(bd.value), beta_bal=np.float32(bb.value),
+                    floor_thr=np.float32(fl.value), samples_consumed=g.value)
+
+    def iqcorr_reset(self) -> None:
+        _check(load().sdrg_engine_iqcorr_reset(self._h), "iqcorr_reset")
+
+    def iqcorr_device(self, iq_ptr: int, fmt: int, in_stride: int, n: int, out_ptr: int,
+                      records_ptr: int | None = None) -> int:
+        """Device path: iq [n_streams][in_stride] raw samples in fmt (the first n of every row are the call's), the
+        corrected rows [n_streams][in_stride] complex64 out (out_ptr may be iq_ptr at CF32 only) and, unless
+        records_ptr is None, [n_streams] IqcorrRecord; asynchronous on the main stream.  Returns n_blocks."""
+        return self._i32_call(load().sdrg_engine_iqcorr_device, "iqcorr_device", iq_ptr, fmt, in_stride, n, out_ptr,
+                              records_ptr)
+
+    def iqcorr_host(self, iq: np.ndarray, fmt: int = CS8, want_records: bool = True):
+        """Host path: iq is [n_streams][n * 2] raw samples in the type of fmt, n <= max_in.  Returns (the corrected
+        complex64 [n_streams][n], the records [n_streams] IqcorrRecord or None, n_blocks)."""
+        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
+        iq = iq.reshape(self.n_streams, iq.size // self.n_streams)
+        n = iq.shape[1] // 2
+        rows = iq if n else np.zeros((self.n_streams, 2), iq.dtype)  # a call without samples still wants rows
+        out = np.empty((self.n_streams, rows.shape[1] // 2), np.complex64)
+        rec = np.empty(self.n_streams, IqcorrRecord) if want_records else None
+        n_blocks = self._i32_call(load().sdrg_engine_iqcorr_host, "iqcorr_host", _ptr(rows), fmt, rows.shape[1] // 2, n,
+                                  _ptr(out), _ptr(rec))
+        return out[:, :n], rec, n_blocks
+
+    def iqcorr_process(self, iq: np.ndarray, fmt: int = CS8, stages: int = STAGE_ALL, now_ms: int = 0):
+        """Correct, then look and listen: process() on the frame corrected on the device.  Returns (spectra, records,
+        pcm, the correction's records [n_streams] IqcorrRecord)."""
+        n = self.cfg.samplesPerReading
+        iq = self._iq(iq, fmt)
+        plen = self.pcm_len
+        spec = np.empty((self.n_streams, n), np.float32) if stages & STAGE_SPECTRUM else None
+        recs = np.zeros(self.n_streams, RECORD_DTYPE) if stages & STAGE_STATS else None
+        pcm = np.empty((self.n_streams, max(plen, 0)), np.int16) if stages & STAGE_SSB else None
+        iq_rec = np.empty(self.n_streams, IqcorrRecord)
+        _check(load().sdrg_engine_iqcorr_process_host(self._h, _ptr(iq), fmt, stages, _ptr(spec), _ptr(recs),
+                                                      _ptr(pcm) if plen > 0 else None, now_ms, _ptr(iq_rec)),
+               "iqcorr_process_host")
+        return spec, recs, pcm, iq_rec
 
     # ---- AGC stage --------------------------------------------------------------------------------
     def set_agc(self, **fields) -> None:
