@@ -1391,6 +1391,117 @@ int32_t sdrg_engine_iqcorr_process_host(sdrg_engine *eng, const void *iq, int32_
                                         sdrg_frame_record *records, int16_t *pcm, int64_t now_ms,
                                         sdrg_iqcorr_record *iq_records);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the noise blanker stage, impulse noise (ignition, switching supplies,
+ * radar sidelobes: pulses of a few samples far over everything else) zeroed per stream in the wideband samples, ahead of
+ * the first filter.  Per stream, the n raw samples of a call, in any of the four formats (the format may change from call
+ * to call), are cut into blocks of S samples at the global indices that are multiples of S.  Each completed block gives
+ * a floor F, the least of its sub-blocks' mean powers, which a pulse leaves alone; the floors move a level L, and a
+ * sample whose power is over ratio times the level of the block before its own is a hit.  A hit blanks itself, the lead
+ * samples before it and the tail samples after it, so the stage delays the stream by exactly lead samples; out has one
+ * CF32 sample per input sample.  Over the whole life of a stream (the calls' samples concatenated, whatever their
+ * lengths) the result is that of one call.  All arithmetic is float, every product and sum rounded on its own, unless
+ * "double" is stated; denormals are kept.  A non-finite sample makes that stream's outputs and records unspecified from
+ * then on.
+ *   config     tau_blocks finite, >= 0; threshold_db and floor_db finite; block S a power of two in
+ *              [SDRG_BLANKER_MIN_BLOCK, SDRG_BLANKER_MAX_BLOCK]; lead in [0, SDRG_BLANKER_MAX_LEAD]; tail in [0,
+ *              SDRG_BLANKER_MAX_TAIL]; max_in in [1, 2^20]: every call's n <= in_stride <= max_in.  Each bad field is
+ *              refused on its own.  A rejected set_blanker changes nothing; an accepted one, and
+ *              sdrg_engine_blanker_reset, restart every stream: g = 0, unseeded.
+ *   design     sdrg_blanker_design, in double, each result rounded to float once: beta = 1 - exp(-1 / tau_blocks), and
+ *              exactly 1.0f at tau_blocks = 0; ratio = 10^(threshold_db / 10); floor_thr = 10^(floor_db / 10); the last
+ *              two are refused unless they are finite positive floats.  Advice: L sits under the mean power even on
+ *              noise alone (by 1.2 dB at S = 64, 2.9 dB at S = 1024: DESIGN.md §3.20), so threshold_db counts from the
+ *              floor, not from the mean; on Gaussian noise alone 13 dB gives under one false hit in 10^4 samples at
+ *              every S, and 16 dB gave none in 2 * 10^6.
+ *   sample     z = (zr, zi) is the format's scaled value, as the IQ correction reads it: CS8 v / 128, CU8 (v - 127.4f)
+ *              * (1 / 128), CS16 v / 32768, CF32 as it lies.  q = zr zr + zi zi: two products and one sum.
+ *   floor      a block is cut into S / 16 sub-blocks of 16 samples; f_j is the adjacent-pair tree over sub-block j's 16
+ *              powers in order (q'[i] = q[2 i] + q[2 i + 1] until one value is left); F = min_j(f_j) * 0.0625f.  A
+ *              block's F depends on its own samples only.
+ *   step       for each completed block, in order: if the stream is not seeded, L = F and seeded = 1; otherwise L = L +
+ *              beta (F - L), also at beta = 1.  thr_k = fmaxf(L, floor_thr) * ratio after global block k; thr_-1 = +inf:
+ *              nothing is blanked before the first block completes.
+ *   hit        the input at global index v, in block k, is a hit iff q[v] > thr_(k-1): the decision never reaches into
+ *              the block that produced it.
+ *   output     the output at global index j carries the input i = j - lead.  If i < 0 it is (+0, +0); if any v in
+ *              [max(i - tail, 0), i + lead] is a hit it is (+0, +0); otherwise it is z[i] as scaled.  Every index an
+ *              output needs is <= j.  out [n_streams][in_stride][2] float, 8-byte aligned: every byte is written by
+ *              every call, zero from n on.  out must not overlap iq in any format: a workgroup reads raw samples that
+ *              lie where another's outputs go; an overlap is not detected and its result is undefined.  n = 0 is a
+ *              valid call: it writes out and the records and leaves the state where it is.
+ *   records    sdrg_blanker_record [n_streams], written by every call: level is L after the last block completed so
+ *              far; level_db = 10.0f * log10f(L + 1e-20f) with glibc's log10f bit for bit (the squelch's); hits is how
+ *              many of this call's n inputs were hits; blanked is how many of this call's n outputs with i >= 0 the
+ *              rule zeroed (it differs from hits by the windows, and by lead at the call's two ends).  *n_blocks =
+ *              floor((g + n) / S) - floor(g / S) is set on the host before the call returns.
+ *   state      per stream the powers of the block in progress, L, seeded and the threshold in force for the block in
+ *              progress, the hit flags of the last lead + tail inputs and the last lead scaled samples, in device
+ *              memory (allocated at the first blanker call), in two halves a call reads and writes in turn; per engine
+ *              g, advanced by n once the call's launches have been issued: a failed call commits nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_BLANKER_MIN_BLOCK 64
+#define SDRG_BLANKER_MAX_BLOCK 1024
+#define SDRG_BLANKER_MAX_LEAD 16
+#define SDRG_BLANKER_MAX_TAIL 64
+#define SDRG_BLANKER_MAX_IN 1048576
+#define SDRG_CLEAN_IQCORR 1 /* sdrg_engine_clean_process_host's mask: the IQ correction ahead of the blanker */
+typedef struct sdrg_blanker_config {
+    double tau_blocks;
+    double threshold_db;   /* a hit is a sample over 10^(threshold_db / 10) times the level */
+    double floor_db;       /* the level counts as at least 10^(floor_db / 10) */
+    int32_t block;
+    int32_t lead;
+    int32_t tail;
+    int32_t max_in;
+} sdrg_blanker_config;
+
+typedef struct sdrg_blanker_record {
+    float level;
+    float level_db;
+    int32_t hits;
+    int32_t blanked;
+} sdrg_blanker_record;
+
+/* Host-only, no device.  After the checks of set_blanker: the three design values above; any of the three pointers may
+ * be NULL. */
+int32_t sdrg_blanker_design(const sdrg_blanker_config *cfg, float *beta, float *ratio, float *floor_thr);
+/* Host-only: *floor_tile = max(512, block), how many consecutive positions, counted from the start of the block in
+ * progress, one workgroup of the floor kernel takes; *pass_tile = 512, how many consecutive outputs of the call one
+ * workgroup of the pass kernel writes (it decides the hits of as many inputs, and again those of the lead + tail inputs
+ * before them).  Either pointer may be NULL, not both. */
+int32_t sdrg_blanker_geometry(int32_t block, int32_t *floor_tile, int32_t *pass_tile);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the stage.  A blanker call while it is off returns SDRG_E_INVALID and
+ * writes nothing. */
+int32_t sdrg_engine_set_blanker(sdrg_engine *eng, const sdrg_blanker_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its three design values and g, the samples every stream has
+ * consumed since the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_blanker(const sdrg_engine *eng, sdrg_blanker_config *cfg, float *beta, float *ratio,
+                                float *floor_thr, uint64_t *samples_consumed);
+int32_t sdrg_engine_blanker_reset(sdrg_engine *eng);
+/* iq: n_streams rows of in_stride raw samples in fmt, aligned as the format's components, of which the first n of every
+ * row are this call's (0 <= n <= in_stride <= max_in); out [n_streams][in_stride][2] float, not overlapping iq; records
+ * [n_streams] or NULL; all in device memory.  Stream rules and waiting as sdrg_engine_squelch_device.  To blank ahead
+ * of the DDC or the channelizer, pass out to their _device calls as SDRG_IQ_CF32; to correct first, pass
+ * sdrg_engine_iqcorr_device's out here as SDRG_IQ_CF32. */
+int32_t sdrg_engine_blanker_device(sdrg_engine *eng, const void *iq, int32_t fmt, int32_t in_stride, int32_t n, void *out,
+                                   sdrg_blanker_record *records, int32_t *n_blocks);
+/* Host buffers of the same shapes, synchronous; all n_streams * in_stride samples of iq are copied. */
+int32_t sdrg_engine_blanker_host(sdrg_engine *eng, const void *iq, int32_t fmt, int32_t in_stride, int32_t n, void *out,
+                                 sdrg_blanker_record *records, int32_t *n_blocks);
+/* Clean, then look and listen: one frame per stream (n = in_stride = samples_per_reading) goes raw -> [IQ correction,
+ * with SDRG_CLEAN_IQCORR in mask] -> blanker into device buffers the engine owns, sdrg_engine_process_host's stages run
+ * on the cleaned rows as SDRG_IQ_CF32, and what process_host copies back comes back, plus iq_records [n_streams] (only
+ * with SDRG_CLEAN_IQCORR) and blank_records [n_streams], each unless NULL.  The spectra and the audio are of the stream
+ * delayed by lead samples.  SDRG_E_INVALID, with no stage moved, for a mask with other bits, if the blanker (or, in the
+ * mask, the IQ correction) is off or its max_in is smaller than the frame, and under sdrg_engine_process_host's own
+ * conditions; each stage's cursor moves only once everything behind it is enqueued.  sdrg_engine_process_host and
+ * sdrg_engine_iqcorr_process_host never blank, whether or not the stage is set. */
+int32_t sdrg_engine_clean_process_host(sdrg_engine *eng, const void *iq, int32_t fmt, int32_t mask, int32_t stages,
+                                       float *spectra, sdrg_frame_record *records, int16_t *pcm, int64_t now_ms,
+                                       sdrg_iqcorr_record *iq_records, sdrg_blanker_record *blank_records);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

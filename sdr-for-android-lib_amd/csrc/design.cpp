@@ -395,6 +395,30 @@ void iqcorr_design(const sdrg_iqcorr_config &c, float *beta_dc, float *beta_bal,
     if (floor_thr) *floor_thr = (float)std::pow(10.0, c.floor_db / 10.0);
 }
 
+// The noise blanker stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *blanker_check(const sdrg_blanker_config &c) {
+    if (!(c.tau_blocks >= 0.0) || !std::isfinite(c.tau_blocks)) return "tau_blocks must be >= 0 and finite";
+    if (!std::isfinite(c.threshold_db)) return "threshold_db must be finite";
+    if (!std::isfinite(c.floor_db)) return "floor_db must be finite";
+    if (c.block < SDRG_BLANKER_MIN_BLOCK || c.block > SDRG_BLANKER_MAX_BLOCK || (c.block & (c.block - 1)) != 0)
+        return "block must be a power of two in [64, 1024]";
+    if (c.lead < 0 || c.lead > SDRG_BLANKER_MAX_LEAD) return "lead outside [0, 16]";
+    if (c.tail < 0 || c.tail > SDRG_BLANKER_MAX_TAIL) return "tail outside [0, 64]";
+    if (c.max_in < 1 || c.max_in > SDRG_BLANKER_MAX_IN) return "max_in outside [1, 2^20]";
+    float ratio, floor_thr;
+    blanker_design(c, nullptr, &ratio, &floor_thr);
+    if (!std::isfinite(ratio) || !(ratio > 0.0f)) return "10^(threshold_db / 10) is not a finite, positive float";
+    if (!std::isfinite(floor_thr) || !(floor_thr > 0.0f)) return "10^(floor_db / 10) is not a finite, positive float";
+    return nullptr;
+}
+
+// The noise blanker stage's constants (sdrg.h), in double, each rounded to float once
+void blanker_design(const sdrg_blanker_config &c, float *beta, float *ratio, float *floor_thr) {
+    if (beta) *beta = c.tau_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.tau_blocks)) : 1.0f;
+    if (ratio) *ratio = (float)std::pow(10.0, c.threshold_db / 10.0);
+    if (floor_thr) *floor_thr = (float)std::pow(10.0, c.floor_db / 10.0);
+}
+
 // The AGC stage's configuration rules (sdrg.h): nullptr, or what is wrong
 const char *agc_check(const sdrg_agc_config &c) {
     if (!std::isfinite(c.target) || !std::isfinite((float)c.target) || !((float)c.target > 0.0f))

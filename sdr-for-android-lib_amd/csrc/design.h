@@ -41,6 +41,8 @@ void squelch_design(const sdrg_squelch_config &cfg, float *open_thr, float *clos
 // be null)
 const char *iqcorr_check(const sdrg_iqcorr_config &cfg);
 void iqcorr_design(const sdrg_iqcorr_config &cfg, float *beta_dc, float *beta_bal, float *floor_thr);
+const char *blanker_check(const sdrg_blanker_config &cfg);
+void blanker_design(const sdrg_blanker_config &cfg, float *beta, float *ratio, float *floor_thr);
 // AGC stage: the configuration rules (nullptr = valid) and the five design values (any pointer may be null)
 struct AgcDesign {
     float max_gain, init_gain, floor_thr, alpha_a, alpha_d;

@@ -261,6 +261,22 @@ struct IqcorrStage {
     size_t blocks() const { return (size_t)BlockCursor::cap(cfg.max_in, cfg.block); }
 };
 
+// noise blanker stage (sdrg_engine_set_blanker / blanker_device / blanker_host / clean_process_host; blanker.hip)
+struct BlankerStage {
+    sdrg_blanker_config cfg{};
+    bool set = false;
+    BlockCursor cur;
+    float beta = 0.0f, ratio = 0.0f, floor_thr = 0.0f;  // blanker_design of cfg
+    // halves of [n_streams][blanker_state_words(S)]: the head, the block's powers so far, the flags, the last samples
+    DevicePingPong<float> state;
+    DeviceBuf<float> blk;  // [the most blocks a call completes][n_streams] floors, then as many thresholds
+    // clean_process_host's: the blanked frame, [n_streams][samples_per_reading][2], and the records
+    DeviceBuf<float> rows;
+    DeviceBuf<sdrg_blanker_record> rec;
+    size_t half(int B) const { return (size_t)B * (size_t)blanker_state_words(cfg.block); }
+    size_t blocks() const { return (size_t)BlockCursor::cap(cfg.max_in, cfg.block); }
+};
+
 // sideband stage (sdrg_engine_set_sideband / sideband_device / sideband_host / listen_sideband_host; sideband.hip)
 struct SidebandStage {
     sdrg_sideband_config cfg{};
@@ -560,6 +576,7 @@ struct sdrg_engine {
     AgcStage agc;
     SidebandStage sb;
     IqcorrStage iqc;
+    BlankerStage blank;
     // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host,
     // squelch_host, agc_host, iqcorr_host and the chains), as bytes: the caller's input, and the rows it gets back (with the squelch's
     // and the AGC's records behind them).  One pair serves them all, as spec_in does its
@@ -685,7 +702,7 @@ int32_t ensure_nco_table(sdrg_engine *e) {
     return upload_floats(&e->d_nco_tab, tab, "NCO table");
 }
 
-// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband, IQ correction ----------
+// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband, IQ correction, blanker --
 //
 // A call of a stage goes through three steps.  x_resolve makes every refusal and touches nothing; what it finds goes
 // into the stage's XCall.  x_reserve does everything that can fail without a launch (the stage's device buffers, the
@@ -1988,11 +2005,146 @@ int32_t sdrg_engine_iqcorr_host(sdrg_engine *e, const void *iq, int32_t fmt, int
     return iqc_stage(e, "iq", iq, out, n_blocks, true, fmt, in_stride, n, records);
 }
 
-// sdrg_engine_process_host, and sdrg_engine_iqcorr_process_host with `corr`, the resolved correction of the frame: the
-// stages then read the corrected rows in e->iqc.rows as CF32, and the correction's cursor moves once they are enqueued.
+// ---- noise blanker stage (blanker.hip) -----------------------------------------------------------------------------
+
+int32_t sdrg_blanker_design(const sdrg_blanker_config *cfg, float *beta, float *ratio, float *floor_thr) {
+    if (!cfg) return fail(SDRG_E_INVALID, "null blanker config");
+    if (const char *bad = blanker_check(*cfg)) return fail(SDRG_E_INVALID, "blanker: %s", bad);
+    blanker_design(*cfg, beta, ratio, floor_thr);
+    return SDRG_OK;
+}
+
+int32_t sdrg_blanker_geometry(int32_t block, int32_t *floor_tile, int32_t *pass_tile) {
+    if (!floor_tile && !pass_tile) return fail(SDRG_E_INVALID, "null floor_tile and pass_tile");
+    if (block < BLANKER_MIN_BLOCK || block > BLOCK_MAX || (block & (block - 1)) != 0)
+        return fail(SDRG_E_INVALID, "blanker: block must be a power of two in [64, 1024]");
+    if (floor_tile) *floor_tile = block_tile(block);
+    if (pass_tile) *pass_tile = BLANKER_TILE;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_blanker(sdrg_engine *e, const sdrg_blanker_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    BlankerStage &s = e->blank;
+    if (cfg) {
+        if (const char *bad = blanker_check(*cfg)) return fail(SDRG_E_INVALID, "blanker: %s", bad);
+        s.cfg = *cfg;
+        blanker_design(*cfg, &s.beta, &s.ratio, &s.floor_thr);
+    }
+    s.set = cfg != nullptr;
+    s.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_blanker(const sdrg_engine *e, sdrg_blanker_config *cfg, float *beta, float *ratio,
+                                float *floor_thr, uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    const BlankerStage &s = e->blank;
+    if (!s.set) return fail(SDRG_E_INVALID, "no blanker configuration set");
+    if (cfg) *cfg = s.cfg;
+    if (beta) *beta = s.beta;
+    if (ratio) *ratio = s.ratio;
+    if (floor_thr) *floor_thr = s.floor_thr;
+    if (samples_consumed) *samples_consumed = s.cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_blanker_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->blank.cur.restart();
+    return SDRG_OK;
+}
+
+using BlankerCall = IqcorrCall;  // a block stage's call and the format of its raw rows
+
+static int32_t blank_resolve(const sdrg_engine *e, int32_t fmt, int32_t in_stride, int32_t n,
+                             sdrg_blanker_record *records, BlankerCall *c) {
+    const BlankerStage &s = e->blank;
+    if (int32_t rc = require_set(s.set, "blanker")) return rc;
+    const int bps = bytes_per_sample(fmt);
+    if (!bps) return fail(SDRG_E_INVALID, "unknown iq format %d", fmt);
+    if (n < 0 || n > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "blanker: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
+    if (in_stride < std::max(n, 1) || in_stride > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "blanker: in_stride %d outside [max(n, 1) = %d, max_in = %d]", in_stride,
+                    std::max(n, 1), s.cfg.max_in);
+    c->fmt = fmt;
+    c->n = n;
+    c->in_stride = in_stride;
+    c->cap = in_stride;
+    c->n_out = s.cur.blocks(n, s.cfg.block);
+    c->in_bytes = (size_t)e->n_streams * (size_t)in_stride * (size_t)bps;
+    c->out_bytes = (size_t)e->n_streams * (size_t)in_stride * 2 * sizeof(float);
+    c->aux = records;
+    c->aux_bytes = (size_t)e->n_streams * sizeof(*records);
+    return SDRG_OK;
+}
+
+static int32_t blank_reserve(sdrg_engine *e, const BlankerCall &) {
+    BlankerStage &s = e->blank;
+    const int32_t rc = ensure_halves(&s.state, s.half(e->n_streams));
+    return rc ? rc : ensure_device(&s.blk, (size_t)e->n_streams * s.blocks() * 2);
+}
+
+// The three launches on the main stream, the cursor left where it is: iq (rows of in_stride raw samples), out (rows of
+// in_stride complex samples, not overlapping iq) and c.aux, the records or null, in device memory.
+static int32_t blank_enqueue(sdrg_engine *e, const BlankerCall &c, const void *iq, void *out) {
+    BlankerStage &s = e->blank;
+    const size_t half = s.half(e->n_streams);
+    BlankerParams p{};
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.block = s.cfg.block;
+    p.lead = s.cfg.lead;
+    p.tail = s.cfg.tail;
+    p.off = s.cur.offset(s.cfg.block);
+    p.n_blocks = c.n_out;
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.skip = s.cur.g < (uint64_t)s.cfg.lead ? s.cfg.lead - (int)s.cur.g : 0;
+    p.beta = s.beta;
+    p.ratio = s.ratio;
+    p.floor_thr = s.floor_thr;
+    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    p.state_new = s.state.next(s.cur, half);
+    p.flo = s.blk.p;
+    p.thr = s.blk.p + (size_t)e->n_streams * s.blocks();
+    p.records = static_cast<sdrg_blanker_record *>(c.aux);
+    HIP_TRY(launch_blanker(iq, c.fmt, e->n_streams, p, static_cast<float *>(out), e->s_main));
+    return SDRG_OK;
+}
+
+static void blank_commit(sdrg_engine *e, const BlankerCall &c) {
+    e->blank.cur.advance(c.n);  // a call without samples wrote out and the records only: the state stays where it is
+    e->outputs_unmarked = true;
+}
+
+static int32_t blank_launch(sdrg_engine *e, const BlankerCall &c, const void *iq, void *out) {
+    const int32_t rc = blank_enqueue(e, c, iq, out);
+    if (!rc) blank_commit(e, c);
+    return rc;
+}
+
+static constexpr auto blank_stage =
+    &stage_call<BlankerCall, blank_resolve, blank_reserve, blank_launch, int32_t, int32_t, int32_t, sdrg_blanker_record *>;
+
+int32_t sdrg_engine_blanker_device(sdrg_engine *e, const void *iq, int32_t fmt, int32_t in_stride, int32_t n, void *out,
+                                   sdrg_blanker_record *records, int32_t *n_blocks) {
+    return blank_stage(e, "iq", iq, out, n_blocks, false, fmt, in_stride, n, records);
+}
+
+int32_t sdrg_engine_blanker_host(sdrg_engine *e, const void *iq, int32_t fmt, int32_t in_stride, int32_t n, void *out,
+                                 sdrg_blanker_record *records, int32_t *n_blocks) {
+    return blank_stage(e, "iq", iq, out, n_blocks, true, fmt, in_stride, n, records);
+}
+
+// sdrg_engine_process_host; sdrg_engine_iqcorr_process_host with `corr`, the resolved correction of the frame; and
+// sdrg_engine_clean_process_host with `blank`, the resolved blanking of the frame (fmt: what it reads, CF32 behind a
+// correction), and with or without `corr`.  The stages then read the last cleaning stage's rows (e->iqc.rows,
+// e->blank.rows) as CF32, and the cleaning stages' cursors move once everything is enqueued.
 static int32_t process_host_frames(sdrg_engine *e, const void *iq, int32_t format, int32_t stages, float *spectra,
                                    sdrg_frame_record *records, int16_t *pcm, int64_t now_ms, IqcorrCall *corr,
-                                   sdrg_iqcorr_record *iq_records) {
+                                   sdrg_iqcorr_record *iq_records, BlankerCall *blank = nullptr,
+                                   sdrg_blanker_record *blank_records = nullptr) {
     const int bps = bytes_per_sample(format);
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
@@ -2003,6 +2155,9 @@ static int32_t process_host_frames(sdrg_engine *e, const void *iq, int32_t forma
     if (!rc && corr) rc = iqc_reserve(e, *corr);
     if (!rc && corr) rc = ensure_device(&e->iqc.rows, (size_t)B * n * 2);
     if (!rc && corr) rc = ensure_device(&e->iqc.rec, (size_t)B);
+    if (!rc && blank) rc = blank_reserve(e, *blank);
+    if (!rc && blank) rc = ensure_device(&e->blank.rows, (size_t)B * n * 2);
+    if (!rc && blank) rc = ensure_device(&e->blank.rec, (size_t)B);
     if (rc) return rc;
     const bool want_cb = e->has_cbs;
     const bool do_spec = stages & SDRG_STAGE_SPECTRUM, do_stats = stages & SDRG_STAGE_STATS,
@@ -2029,6 +2184,13 @@ static int32_t process_host_frames(sdrg_engine *e, const void *iq, int32_t forma
         frames = e->iqc.rows.p;
         format = SDRG_IQ_CF32;
     }
+    if (blank) {
+        blank->aux = e->blank.rec.p;
+        rc = blank_enqueue(e, *blank, frames, e->blank.rows.p);
+        if (rc) return rc;
+        frames = e->blank.rows.p;
+        format = SDRG_IQ_CF32;
+    }
     rc = enqueue(e, frames, format, stages, do_spec ? e->d_spec_stage.p : nullptr,
                  do_stats ? e->d_rec_stage.p : nullptr, do_ssb ? e->d_pcm_stage.p : nullptr, now_ms, true);
     if (rc) return rc;
@@ -2037,6 +2199,12 @@ static int32_t process_host_frames(sdrg_engine *e, const void *iq, int32_t forma
         if (iq_records)
             HIP_TRY(hipMemcpyAsync(iq_records, e->iqc.rec.p, sizeof(sdrg_iqcorr_record) * (size_t)B, hipMemcpyDeviceToHost,
                                    e->s_main));
+    }
+    if (blank) {
+        blank_commit(e, *blank);
+        if (blank_records)
+            HIP_TRY(hipMemcpyAsync(blank_records, e->blank.rec.p, sizeof(sdrg_blanker_record) * (size_t)B,
+                                   hipMemcpyDeviceToHost, e->s_main));
     }
     if (do_spec) e->host_spec_n = n;  // sdrg_engine_display_host(spectra = NULL) reads these spectra
     float *h_spec = spectra;
@@ -2099,6 +2267,30 @@ int32_t sdrg_engine_iqcorr_process_host(sdrg_engine *e, const void *iq, int32_t 
     IqcorrCall c;
     if (int32_t rc = iqc_resolve(e, fmt, n, n, nullptr, &c)) return rc;
     return process_host_frames(e, iq, fmt, stages, spectra, records, pcm, now_ms, &c, iq_records);
+}
+
+int32_t sdrg_engine_clean_process_host(sdrg_engine *e, const void *iq, int32_t fmt, int32_t mask, int32_t stages,
+                                       float *spectra, sdrg_frame_record *records, int16_t *pcm, int64_t now_ms,
+                                       sdrg_iqcorr_record *iq_records, sdrg_blanker_record *blank_records) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!iq) return fail(SDRG_E_INVALID, "null iq");
+    if (mask & ~SDRG_CLEAN_IQCORR) return fail(SDRG_E_INVALID, "clean mask %d has bits other than SDRG_CLEAN_IQCORR", mask);
+    const bool correct = mask & SDRG_CLEAN_IQCORR;
+    if (int32_t rc = require_set(e->blank.set, "blanker")) return rc;
+    if (correct)
+        if (int32_t rc = require_set(e->iqc.set, "iqcorr")) return rc;
+    const int n = e->cfg.samples_per_reading;
+    if (e->blank.cfg.max_in < n)
+        return fail(SDRG_E_INVALID, "blanker max_in %d smaller than the frame's %d samples", e->blank.cfg.max_in, n);
+    if (correct && e->iqc.cfg.max_in < n)
+        return fail(SDRG_E_INVALID, "iqcorr max_in %d smaller than the frame's %d samples", e->iqc.cfg.max_in, n);
+    IqcorrCall c;
+    BlankerCall k;
+    if (correct)
+        if (int32_t rc = iqc_resolve(e, fmt, n, n, nullptr, &c)) return rc;
+    if (int32_t rc = blank_resolve(e, correct ? SDRG_IQ_CF32 : fmt, n, n, nullptr, &k)) return rc;
+    return process_host_frames(e, iq, fmt, stages, spectra, records, pcm, now_ms, correct ? &c : nullptr, iq_records, &k,
+                               blank_records);
 }
 
 // ---- display stage (display.hip) ----------------------------------------------------------------------------------

@@ -324,6 +324,34 @@ static_assert(SDRG_IQCORR_MAX_BLOCK == BLOCK_MAX && SDRG_IQCORR_MAX_IN == BLOCK_
               "the block stages' positions and butterfly: a block is at least a wave's 32 pairs");
 hipError_t launch_iqcorr(const void *iq, int fmt, int n_streams, IqcorrParams p, float *out, hipStream_t stream);
 
+// Noise blanker stage (blanker.hip): per stream the n raw samples at iq + stream * in_stride (in fmt) are the positions
+// [off, off + n) of a run of blocks of `block` samples, as the block stages' are.  state_old / state_new [n_streams]
+// [blanker_state_words(block)] floats: {L, seeded (int bits), the threshold in force for the block in progress, 0}, the
+// powers so far of the block in progress, the hit flags of the last BLANKER_FLAGS inputs (ints, the oldest first; 0 for
+// what lies before the stream) and the last BLANKER_MAX_LEAD scaled samples (pairs, zeros before the stream); fresh:
+// state_old is not read (L = 0, unseeded, +inf, no flags, zeros, and off is 0).  flo and thr [blocks][n_streams] floats
+// are scratch: the completed blocks' F, and the threshold after each.  skip = max(lead - g, 0): the call's outputs whose
+// input lies before the stream.  Writes out [n_streams][in_stride][2] whole (zeros from n on; out must not overlap iq),
+// and, if n > 0, state_new; records [n_streams] unless nullptr.  n_streams, log2_block and tile are the launcher's.
+struct BlankerParams {
+    int n, in_stride, block, lead, tail, off, n_blocks, fresh, skip;
+    float beta, floor_thr, ratio;
+    const float *state_old;
+    float *state_new;
+    float *flo, *thr;
+    sdrg_blanker_record *records;
+    int n_streams, log2_block, tile;
+};
+constexpr int BLANKER_STATE_HEAD = 4;
+constexpr int BLANKER_MIN_BLOCK = SDRG_BLANKER_MIN_BLOCK;
+constexpr int BLANKER_MAX_LEAD = SDRG_BLANKER_MAX_LEAD, BLANKER_MAX_TAIL = SDRG_BLANKER_MAX_TAIL;
+constexpr int BLANKER_FLAGS = BLANKER_MAX_LEAD + BLANKER_MAX_TAIL;
+constexpr int BLANKER_TILE = BLOCK_PASS;  // outputs per workgroup of the pass kernel
+static_assert(SDRG_BLANKER_MAX_BLOCK == BLOCK_MAX && SDRG_BLANKER_MAX_IN == BLOCK_MAX_IN && BLANKER_MIN_BLOCK >= 64,
+              "the block stages' positions and butterfly: a block is at least a wave's 32 pairs");
+constexpr int blanker_state_words(int block) { return BLANKER_STATE_HEAD + block + BLANKER_FLAGS + 2 * BLANKER_MAX_LEAD; }
+hipError_t launch_blanker(const void *iq, int fmt, int n_streams, BlankerParams p, float *out, hipStream_t stream);
+
 // Sideband stage (sideband.hip): per stream and output j, A = sum_k cr[k] zr[first + j decim - k] and Bm = sum_k ci[k]
 // zi[first + j decim - k], z the n complex samples at chan + stream * in_stride (float2); u = A - Bm, l = A + Bm.  The
 // history holds samples, [taps - 1][2] per stream.  Writes out [n_streams][cap] (u gain, l gain, or at mode BOTH the

@@ -153,6 +153,9 @@ EXPORTS = [
     "sdrg_iqcorr_design", "sdrg_iqcorr_geometry", "sdrg_engine_set_iqcorr", "sdrg_engine_get_iqcorr",
     "sdrg_engine_iqcorr_reset", "sdrg_engine_iqcorr_device", "sdrg_engine_iqcorr_host",
     "sdrg_engine_iqcorr_process_host",
+    "sdrg_blanker_design", "sdrg_blanker_geometry", "sdrg_engine_set_blanker", "sdrg_engine_get_blanker",
+    "sdrg_engine_blanker_reset", "sdrg_engine_blanker_device", "sdrg_engine_blanker_host",
+    "sdrg_engine_clean_process_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -264,6 +267,20 @@ class IqcorrConfig(ctypes.Structure):
 IqcorrRecord = np.dtype([("dc_re", "<f4"), ("dc_im", "<f4"), ("w_re", "<f4"), ("w_im", "<f4"), ("power", "<f4"),
                          ("image_db", "<f4"), ("held_blocks", "<i4"), ("seeded", "<i4")])
 IQCORR_DC, IQCORR_BALANCE = 1, 2
+
+
+class BlankerConfig(ctypes.Structure):
+    """sdrg_blanker_config: the noise blanker stage's time constant, threshold, floor, block length, window and row
+    length (include/sdrg.h)."""
+    _fields_ = [("tau_blocks", ctypes.c_double), ("threshold_db", ctypes.c_double), ("floor_db", ctypes.c_double),
+                ("block", ctypes.c_int32), ("lead", ctypes.c_int32), ("tail", ctypes.c_int32),
+                ("max_in", ctypes.c_int32)]
+
+
+# sdrg_blanker_record
+BlankerRecord = np.dtype([("level", "<f4"), ("level_db", "<f4"), ("hits", "<i4"), ("blanked", "<i4")])
+CLEAN_IQCORR = 1  # SDRG_CLEAN_IQCORR
+BLANKER_MAX_LEAD, BLANKER_MAX_TAIL = 16, 64
 
 
 class AgcConfig(ctypes.Structure):
@@ -537,6 +554,16 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_iqcorr_device": (_I32, [P, P, _I32, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_iqcorr_host": (_I32, [P, P, _I32, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_iqcorr_process_host": (_I32, [P, P, _I32, _I32, P, P, P, _I64, P]),
+        "sdrg_blanker_design": (_I32, [ctypes.POINTER(BlankerConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
+                                       ctypes.POINTER(_F)]),
+        "sdrg_blanker_geometry": (_I32, [_I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_blanker": (_I32, [P, ctypes.POINTER(BlankerConfig)]),
+        "sdrg_engine_get_blanker": (_I32, [P, ctypes.POINTER(BlankerConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
+                                           ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_blanker_reset": (_I32, [P]),
+        "sdrg_engine_blanker_device": (_I32, [P, P, _I32, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_blanker_host": (_I32, [P, P, _I32, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_clean_process_host": (_I32, [P, P, _I32, _I32, _I32, P, P, P, _I64, P, P]),
         "sdrg_engine_set_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig)]),
         "sdrg_engine_get_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
                                            ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_uint64)]),
@@ -847,6 +874,24 @@ def iqcorr_geometry(block: int) -> int:
     t = _I32()
     _check(load().sdrg_iqcorr_geometry(block, ctypes.byref(t)), "iqcorr_geometry")
     return t.value
+
+
+def blanker_design(**fields) -> dict:
+    """The noise blanker stage's design for a configuration (host-side, no device): beta, ratio and floor_thr as
+    np.float32.  The fields are sdrg_blanker_config's (fields left out are 0)."""
+    c = _filled(BlankerConfig, "blanker", fields)
+    beta, ratio, fl = _F(), _F(), _F()
+    _check(load().sdrg_blanker_design(ctypes.byref(c), ctypes.byref(beta), ctypes.byref(ratio), ctypes.byref(fl)),
+           "blanker_design")
+    return {"beta": np.float32(beta.value), "ratio": np.float32(ratio.value), "floor_thr": np.float32(fl.value)}
+
+
+def blanker_geometry(block: int) -> tuple[int, int]:
+    """(floor_tile, pass_tile): consecutive positions per workgroup of the blanker's floor kernel (counted from the
+    start of the block in progress) and consecutive outputs of the call per workgroup of its pass kernel."""
+    f, t = _I32(), _I32()
+    _check(load().sdrg_blanker_geometry(block, ctypes.byref(f), ctypes.byref(t)), "blanker_geometry")
+    return f.value, t.value
 
 
 def agc_design(**fields) -> dict:
@@ -1496,6 +1541,62 @@ class Engine:
                                                       _ptr(pcm) if plen > 0 else None, now_ms, _ptr(iq_rec)),
                "iqcorr_process_host")
         return spec, recs, pcm, iq_rec
+
+    # ---- noise blanker stage ----------------------------------------------------------------------
+    def set_blanker(self, **fields) -> None:
+        """sdrg_engine_set_blanker: tau_blocks, threshold_db, floor_db, block, lead, tail, max_in (fields left out are
+        0); set_blanker(off=True) switches the stage off."""
+        self._set_stage(BlankerConfig, "blanker", fields)
+
+    def blanker_config(self) -> dict:
+        """The configuration in force, plus its design (beta, ratio, floor_thr as np.float32) and samples_consumed."""
+        c, beta, ratio, fl, g = BlankerConfig(), _F(), _F(), _F(), ctypes.c_uint64()
+        _check(load().sdrg_engine_get_blanker(self._h, ctypes.byref(c), ctypes.byref(beta), ctypes.byref(ratio),
+                                              ctypes.byref(fl), ctypes.byref(g)), "get_blanker")
+        return dict(_as_dict(c), beta=np.float32(beta.value), ratio=np.float32(ratio.value),
+                    floor_thr=np.float32(fl.value), samples_consumed=g.value)
+
+    def blanker_reset(self) -> None:
+        _check(load().sdrg_engine_blanker_reset(self._h), "blanker_reset")
+
+    def blanker_device(self, iq_ptr: int, fmt: int, in_stride: int, n: int, out_ptr: int,
+                       records_ptr: int | None = None) -> int:
+        """Device path: iq [n_streams][in_stride] raw samples in fmt (the first n of every row are the call's), the
+        blanked rows [n_streams][in_stride] complex64 out, delayed by lead samples (out must not overlap iq) and,
+        unless records_ptr is None, [n_streams] BlankerRecord; asynchronous on the main stream.  Returns n_blocks."""
+        return self._i32_call(load().sdrg_engine_blanker_device, "blanker_device", iq_ptr, fmt, in_stride, n, out_ptr,
+                              records_ptr)
+
+    def blanker_host(self, iq: np.ndarray, fmt: int = CS8, want_records: bool = True):
+        """Host path: iq is [n_streams][n * 2] raw samples in the type of fmt, n <= max_in.  Returns (the blanked
+        complex64 [n_streams][n], the records [n_streams] BlankerRecord or None, n_blocks)."""
+        iq = np.ascontiguousarray(iq, dtype=NUMPY_DTYPE[fmt])
+        iq = iq.reshape(self.n_streams, iq.size // self.n_streams)
+        n = iq.shape[1] // 2
+        rows = iq if n else np.zeros((self.n_streams, 2), iq.dtype)  # a call without samples still wants rows
+        out = np.empty((self.n_streams, rows.shape[1] // 2), np.complex64)
+        rec = np.empty(self.n_streams, BlankerRecord) if want_records else None
+        n_blocks = self._i32_call(load().sdrg_engine_blanker_host, "blanker_host", _ptr(rows), fmt, rows.shape[1] // 2,
+                                  n, _ptr(out), _ptr(rec))
+        return out[:, :n], rec, n_blocks
+
+    def clean_process_host(self, iq: np.ndarray, fmt: int = CS8, mask: int = 0, stages: int = STAGE_ALL,
+                           now_ms: int = 0):
+        """Clean, then look and listen: process() on the frame corrected (with CLEAN_IQCORR in mask) and blanked on the
+        device.  Returns (spectra, records, pcm, the correction's records [n_streams] IqcorrRecord or None, the
+        blanker's records [n_streams] BlankerRecord)."""
+        n = self.cfg.samplesPerReading
+        iq = self._iq(iq, fmt)
+        plen = self.pcm_len
+        spec = np.empty((self.n_streams, n), np.float32) if stages & STAGE_SPECTRUM else None
+        recs = np.zeros(self.n_streams, RECORD_DTYPE) if stages & STAGE_STATS else None
+        pcm = np.empty((self.n_streams, max(plen, 0)), np.int16) if stages & STAGE_SSB else None
+        iq_rec = np.empty(self.n_streams, IqcorrRecord) if mask & CLEAN_IQCORR else None
+        blank_rec = np.empty(self.n_streams, BlankerRecord)
+        _check(load().sdrg_engine_clean_process_host(self._h, _ptr(iq), fmt, mask, stages, _ptr(spec), _ptr(recs),
+                                                     _ptr(pcm) if plen > 0 else None, now_ms, _ptr(iq_rec),
+                                                     _ptr(blank_rec)), "clean_process_host")
+        return spec, recs, pcm, iq_rec, blank_rec
 
     # ---- AGC stage --------------------------------------------------------------------------------
     def set_agc(self, **fields) -> None:
