@@ -1502,6 +1502,131 @@ int32_t sdrg_engine_clean_process_host(sdrg_engine *eng, const void *iq, int32_t
                                        float *spectra, sdrg_frame_record *records, int16_t *pcm, int64_t now_ms,
                                        sdrg_iqcorr_record *iq_records, sdrg_blanker_record *blank_records);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the tone detector stage, the power at K configured frequencies per block
+ * of a stream and a latched decision that survives a noisy block: the sub-audible tone of an FM channel, a call tone, a
+ * keyed carrier, the mark and space of an FSK signal, a pilot.  Per stream, the n values of a call are cut into blocks
+ * of S = 64 Q values at the global indices that are multiples of S.  At components = 1 a value is a real float (the
+ * audio of the demodulator or of the sideband stage at *_OUT_F32), at components = 2 a CF32 sample (the DDC's channel, a
+ * row of the channelizer's).  Over the whole life of a stream (the calls' values concatenated, whatever their lengths)
+ * the result is that of one call.  All arithmetic is float, every product, sum and quotient rounded on its own, unless
+ * "double" is stated; denormals are kept.  A non-finite value makes that stream's outputs unspecified from then on.
+ *   config     rate_hz fa > 0, finite; components 1 or 2; n_tones K in [1, SDRG_TONES_MAX_TONES]; freq_hz (the first K
+ *              are used) each finite, 0 < f < fa / 2 at components 1, |f| <= fa / 2 at components 2, equal frequencies
+ *              allowed; sub_blocks Q in [1, SDRG_TONES_MAX_SUB_BLOCKS]; window SDRG_TONES_RECT or SDRG_TONES_HANN; min_db
+ *              and dominance_db finite, dominance_db >= 0; share in [0, 1]; confirm_blocks in [1, 255]; release_blocks in
+ *              [0, 255]; max_in in [1, SDRG_TONES_MAX_IN]: every call's n <= in_stride <= max_in.  Each bad field is
+ *              refused on its own.  A rejected set_tones changes nothing; an accepted one, and sdrg_engine_tones_reset,
+ *              restart every stream.
+ *   design     sdrg_tones_design, in double, each result rounded to float once: w[i] = 1 (RECT) or 0.5 - 0.5 cos(2 pi
+ *              (i + 1) / (S + 1)) (HANN) for i in [0, S); t = f_k i / fa, theta = 2 pi (t - floor(t)); c[k][i] = (float)
+ *              (w[i] cos theta), s[k][i] = (float)(w[i] sin theta); wf[i] = (float)w[i]; W1 = sum w, W2 = sum w^2; at
+ *              components 1 pnorm = (float)(4 / W1^2) and enorm = (float)(2 / W2), at components 2 pnorm = (float)(1 /
+ *              W1^2) and enorm = (float)(1 / W2); min_power = (float)10^(min_db / 10), dom = (float)10^(dominance_db /
+ *              10), share_thr = (float)share.  A tone of amplitude A at f_k then reads power_k ~ A^2, and its share of
+ *              the block's energy ~ 1.
+ *   products   at in-block index i.  components 1: C_i = x c, S_i = x s, e_i = (x wf) (x wf).  components 2: C_i = xr c
+ *              + xi s and S_i = xi c - xr s, each two products then one sum or difference; a = xr wf, b = xi wf, e_i = a
+ *              a + b b.
+ *   sums       the 64 products of sub-block j (the indices [64 j, 64 j + 64)) are joined by the adjacent-pair tree
+ *              (q'[i] = q[2 i] + q[2 i + 1] until one value is left); a block's accumulators start at +0 and take the
+ *              sub-block sums in ascending j, acc = acc + sub_j: 2 K + 1 accumulators, C_k, S_k and E.
+ *   block      per completed block: P_k = (C_k C_k + S_k S_k) pnorm; Et = E enorm; k* the smallest k with the largest
+ *              P_k; P2 the largest P_k over k != k*, +0 at K = 1; share_b = P_k* / fmaxf(Et, 1e-30f); the candidate is
+ *              k* if P_k* >= min_power and P_k* >= share_thr Et and P_k* >= dom P2, else -1.
+ *   latch      in this order: if cand >= 0 and cand == last then run = min(run + 1, 65535), otherwise run = (cand >= 0)
+ *              ? 1 : 0; last = cand; if cand >= 0 and run >= confirm_blocks then tone = cand, miss = 0; else if tone >=
+ *              0: if cand == tone then miss = 0, else miss = miss + 1 and, if miss > release_blocks, tone = -1 and miss
+ *              = 0.  A fresh stream has tone = last = -1, run = miss = 0.
+ *   outputs    powers [n_streams][cap_blocks][K] float, cap_blocks = ceil(max_in / S) (sdrg_engine_tones_max_blocks):
+ *              row b is P_0 .. P_(K-1) of the b-th block this call completed; every byte is written by every call, +0
+ *              from n_blocks on.  records [n_streams] (NULL allowed): tone, the latched tone or -1; candidate, that of
+ *              the last block completed so far (-1 before the first); power, P_k* of that block (+0 before the first);
+ *              power_db = 10.0f * log10f(power + 1e-20f) with glibc's log10f bit for bit; share, share_b of that block
+ *              (+0 before the first); tone_blocks, the blocks of this call after which a tone was latched; changes, the
+ *              blocks of this call after which tone differs from before them; run.  *n_blocks = floor((g + n) / S) -
+ *              floor(g / S) is set on the host.  n = 0 is a valid call: it writes powers and the records and leaves the
+ *              state where it is.
+ *   state      per stream the at most 63 values of the sub-block in progress, the 2 K + 1 accumulators, the latch's
+ *              words and what the record repeats, in device memory, in two halves a call reads and writes in turn; per
+ *              engine g, advanced by n once the call's launches have been issued: a failed call commits nothing.
+ *   memory     besides the state and the design ((2 K + 1) S floats), a call of n values needs n_streams * ceil(n /
+ *              64) * (2 K + 1) floats of device scratch, kept and grown as needed: 43 MB at 4096 streams, n = 1639 and K
+ *              = 50, but 2.2 GB at 4096 streams, n = 65536 and K = 64.  A call that cannot have it returns SDRG_E_NOMEM
+ *              and commits nothing; a caller short of memory feeds long rows in several calls, whose result is the same.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_TONES_MAX_TONES 64
+#define SDRG_TONES_MAX_SUB_BLOCKS 256
+#define SDRG_TONES_MAX_IN 65536
+#define SDRG_TONES_RECT 0
+#define SDRG_TONES_HANN 1
+typedef struct sdrg_tones_config {
+    double rate_hz;
+    double freq_hz[SDRG_TONES_MAX_TONES];
+    double min_db;        /* a candidate's power is at least 10^(min_db / 10) */
+    double dominance_db;  /* and at least 10^(dominance_db / 10) times the second largest */
+    double share;         /* and at least this share of the block's energy */
+    int32_t components;
+    int32_t n_tones;
+    int32_t sub_blocks;
+    int32_t window;
+    int32_t confirm_blocks;
+    int32_t release_blocks;
+    int32_t max_in;
+    int32_t reserved;     /* ignored */
+} sdrg_tones_config;
+
+typedef struct sdrg_tones_record {
+    int32_t tone;
+    int32_t candidate;
+    float power;
+    float power_db;
+    float share;
+    int32_t tone_blocks;
+    int32_t changes;
+    int32_t run;
+} sdrg_tones_record;
+
+typedef struct sdrg_tones_scalars {
+    float pnorm, enorm, min_power, dom, share_thr;
+} sdrg_tones_scalars;
+
+/* Host-only, no device.  After the checks of set_tones: table [K][S][2] (c, s), wf [S] and the five scalars; any of the
+ * three pointers may be NULL. */
+int32_t sdrg_tones_design(const sdrg_tones_config *cfg, float *table, float *wf, sdrg_tones_scalars *scalars);
+/* Host-only: *sub_blocks_per_group, how many consecutive sub-blocks of 64 values, counted from the start of the
+ * sub-block in progress, one workgroup of the correlate kernel takes. */
+int32_t sdrg_tones_geometry(int32_t *sub_blocks_per_group);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the stage; an accepted set uploads the design.  A tones call while it
+ * is off returns SDRG_E_INVALID and writes nothing. */
+int32_t sdrg_engine_set_tones(sdrg_engine *eng, const sdrg_tones_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its scalars and g, the values every stream has consumed since
+ * the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_tones(const sdrg_engine *eng, sdrg_tones_config *cfg, sdrg_tones_scalars *scalars,
+                              uint64_t *samples_consumed);
+int32_t sdrg_engine_tones_reset(sdrg_engine *eng);
+/* cap_blocks = ceil(max_in / S): the rows of powers per stream */
+int32_t sdrg_engine_tones_max_blocks(const sdrg_engine *eng, int32_t *cap_blocks);
+/* in: n_streams rows of in_stride values (floats at components 1, float pairs aligned to 8 bytes at components 2), of
+ * which the first n of every row are this call's (0 <= n <= in_stride <= max_in); powers [n_streams][cap_blocks][K]
+ * float; records [n_streams] or NULL; all in device memory.  Stream rules and waiting as sdrg_engine_squelch_device. */
+int32_t sdrg_engine_tones_device(sdrg_engine *eng, const void *in, int32_t in_stride, int32_t n, void *powers,
+                                 sdrg_tones_record *records, int32_t *n_blocks);
+/* Host buffers of the same shapes, synchronous; all n_streams * in_stride values of in are copied. */
+int32_t sdrg_engine_tones_host(sdrg_engine *eng, const void *in, int32_t in_stride, int32_t n, void *powers,
+                               sdrg_tones_record *records, int32_t *n_blocks);
+/* sdrg_engine_listen_host with the tone stage reading the demodulator's float rows on the device, ahead of the
+ * resampler: besides what listen_host returns, powers [n_streams][cap_blocks][K], tone_records [n_streams] unless NULL
+ * and *n_blocks.  SDRG_E_INVALID, with no stage moved, under listen_host's conditions, for a null powers or n_blocks, if
+ * the tone stage is off, its components is not 1, the demodulator does not write SDRG_DEMOD_OUT_F32, or the tone
+ * stage's max_in is under the demodulator's row length; a call that fails for want of memory commits nothing in any
+ * stage either.  The other chain calls never run the tone stage, whether or not it is set. */
+int32_t sdrg_engine_listen_tones_host(sdrg_engine *eng, int32_t steps, const void *iq, int32_t fmt, void *out,
+                                      int32_t *n_out, sdrg_squelch_record *squelch_records,
+                                      sdrg_agc_record *agc_records, float *powers, sdrg_tones_record *tone_records,
+                                      int32_t *n_blocks);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

@@ -419,6 +419,60 @@ void blanker_design(const sdrg_blanker_config &c, float *beta, float *ratio, flo
     if (floor_thr) *floor_thr = (float)std::pow(10.0, c.floor_db / 10.0);
 }
 
+// The tone detector stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *tones_check(const sdrg_tones_config &c) {
+    if (!std::isfinite(c.rate_hz) || !(c.rate_hz > 0.0)) return "rate_hz must be > 0 and finite";
+    if (c.components != 1 && c.components != 2) return "components must be 1 or 2";
+    if (c.n_tones < 1 || c.n_tones > SDRG_TONES_MAX_TONES) return "n_tones outside [1, 64]";
+    for (int k = 0; k < c.n_tones; k++) {
+        const double f = c.freq_hz[k];
+        if (!std::isfinite(f)) return "freq_hz must be finite";
+        if (c.components == 1 && !(f > 0.0 && f < c.rate_hz / 2.0)) return "freq_hz outside (0, rate_hz / 2) at components 1";
+        if (c.components == 2 && !(std::fabs(f) <= c.rate_hz / 2.0)) return "|freq_hz| over rate_hz / 2 at components 2";
+    }
+    if (c.sub_blocks < 1 || c.sub_blocks > SDRG_TONES_MAX_SUB_BLOCKS) return "sub_blocks outside [1, 256]";
+    if (c.window != SDRG_TONES_RECT && c.window != SDRG_TONES_HANN) return "unknown window";
+    if (!std::isfinite(c.min_db)) return "min_db must be finite";
+    if (!std::isfinite(c.dominance_db) || !(c.dominance_db >= 0.0)) return "dominance_db must be >= 0 and finite";
+    if (!(c.share >= 0.0 && c.share <= 1.0)) return "share outside [0, 1]";
+    if (c.confirm_blocks < 1 || c.confirm_blocks > 255) return "confirm_blocks outside [1, 255]";
+    if (c.release_blocks < 0 || c.release_blocks > 255) return "release_blocks outside [0, 255]";
+    if (c.max_in < 1 || c.max_in > SDRG_TONES_MAX_IN) return "max_in outside [1, 65536]";
+    return nullptr;
+}
+
+// The tone detector stage's design (sdrg.h), in double, each result rounded to float once: table [K][S][2], wf [S] and
+// the scalars; any pointer may be null
+void tones_design(const sdrg_tones_config &c, float *table, float *wf, sdrg_tones_scalars *sc) {
+    const int S = 64 * c.sub_blocks, K = c.n_tones;
+    std::vector<double> w((size_t)S);
+    double W1 = 0.0, W2 = 0.0;
+    for (int i = 0; i < S; i++) {
+        w[(size_t)i] = c.window == SDRG_TONES_HANN ? 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)(i + 1) / (double)(S + 1)) : 1.0;
+        W1 += w[(size_t)i];
+        W2 += w[(size_t)i] * w[(size_t)i];
+    }
+    if (wf)
+        for (int i = 0; i < S; i++) wf[i] = (float)w[(size_t)i];
+    if (table)
+        for (int k = 0; k < K; k++)
+            for (int i = 0; i < S; i++) {
+                const double t = c.freq_hz[k] * (double)i / c.rate_hz;
+                const double theta = 2.0 * M_PI * (t - std::floor(t));
+                float *to = table + ((size_t)k * (size_t)S + (size_t)i) * 2;
+                to[0] = (float)(w[(size_t)i] * std::cos(theta));
+                to[1] = (float)(w[(size_t)i] * std::sin(theta));
+            }
+    if (sc) {
+        const double two = c.components == 1 ? 2.0 : 1.0;
+        sc->pnorm = (float)(two * two / (W1 * W1));
+        sc->enorm = (float)(two / W2);
+        sc->min_power = (float)std::pow(10.0, c.min_db / 10.0);
+        sc->dom = (float)std::pow(10.0, c.dominance_db / 10.0);
+        sc->share_thr = (float)c.share;
+    }
+}
+
 // The AGC stage's configuration rules (sdrg.h): nullptr, or what is wrong
 const char *agc_check(const sdrg_agc_config &c) {
     if (!std::isfinite(c.target) || !std::isfinite((float)c.target) || !((float)c.target > 0.0f))

@@ -43,6 +43,10 @@ const char *iqcorr_check(const sdrg_iqcorr_config &cfg);
 void iqcorr_design(const sdrg_iqcorr_config &cfg, float *beta_dc, float *beta_bal, float *floor_thr);
 const char *blanker_check(const sdrg_blanker_config &cfg);
 void blanker_design(const sdrg_blanker_config &cfg, float *beta, float *ratio, float *floor_thr);
+// tone detector stage: the configuration rules (nullptr = valid) and the design, table [K][S][2], wf [S] and the five
+// scalars (any pointer may be null)
+const char *tones_check(const sdrg_tones_config &cfg);
+void tones_design(const sdrg_tones_config &cfg, float *table, float *wf, sdrg_tones_scalars *scalars);
 // AGC stage: the configuration rules (nullptr = valid) and the five design values (any pointer may be null)
 struct AgcDesign {
     float max_gain, init_gain, floor_thr, alpha_a, alpha_d;

@@ -277,6 +277,21 @@ struct BlankerStage {
     size_t blocks() const { return (size_t)BlockCursor::cap(cfg.max_in, cfg.block); }
 };
 
+// tone detector stage (sdrg_engine_set_tones / tones_device / tones_host / listen_tones_host; tones.hip)
+struct TonesStage {
+    sdrg_tones_config cfg{};
+    bool set = false;
+    BlockCursor cur;
+    sdrg_tones_scalars sc{};  // tones_design of cfg
+    DeviceBuf<float> d_design;  // the table [K][S][2], then wf [S]: written by set_tones
+    // halves of [n_streams][tones_state_words(K, components)]: the head, the accumulators, the sub-block's values so far
+    DevicePingPong<float> state;
+    DeviceBuf<float> sums;  // [n_streams][the call's sub-blocks][2 K + 1]: the sub-blocks' sums of the call in flight
+    int S() const { return TONES_SUB * cfg.sub_blocks; }
+    int cap_blocks() const { return BlockCursor::cap(cfg.max_in, S()); }
+    size_t half(int B) const { return (size_t)B * (size_t)tones_state_words(cfg.n_tones, cfg.components); }
+};
+
 // sideband stage (sdrg_engine_set_sideband / sideband_device / sideband_host / listen_sideband_host; sideband.hip)
 struct SidebandStage {
     sdrg_sideband_config cfg{};
@@ -577,6 +592,7 @@ struct sdrg_engine {
     SidebandStage sb;
     IqcorrStage iqc;
     BlankerStage blank;
+    TonesStage tones;
     // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host,
     // squelch_host, agc_host, iqcorr_host and the chains), as bytes: the caller's input, and the rows it gets back (with the squelch's
     // and the AGC's records behind them).  One pair serves them all, as spec_in does its
@@ -702,7 +718,8 @@ int32_t ensure_nco_table(sdrg_engine *e) {
     return upload_floats(&e->d_nco_tab, tab, "NCO table");
 }
 
-// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband, IQ correction, blanker --
+// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband, IQ correction, blanker,
+// ---- tone detector -------------------------------------------------------------------------------------------------
 //
 // A call of a stage goes through three steps.  x_resolve makes every refusal and touches nothing; what it finds goes
 // into the stage's XCall.  x_reserve does everything that can fail without a launch (the stage's device buffers, the
@@ -726,25 +743,34 @@ struct StageCall {
 // callers' host pointers out of the calls (the stages' whose launches write them: one, or in a chain the squelch's and
 // the AGC's, either or both; a call without a second output takes no room) and says how much stream_out must hold;
 // stage() points the calls at the staging once host_begin has made it; finish() copies back, then host_end.
+// listen_tones_host adds the tone stage's powers and records behind those two with add(): `slot` holds the caller's host
+// pointer (null: no room taken) and is pointed at the staging by stage().
 struct HostAux {
-    StageCall *c[2];
-    void *host[2];
-    size_t at[2], end;
-    HostAux(size_t out_bytes, StageCall *first, StageCall *second = nullptr) : c{first, second}, end(out_bytes) {
-        for (int i = 0; i < 2; i++) {
-            host[i] = c[i] ? c[i]->aux : nullptr;
-            at[i] = (end + 15) & ~(size_t)15;
-            if (host[i]) end = at[i] + c[i]->aux_bytes;
-        }
+    static constexpr int MAX = 4;
+    void **slot[MAX];
+    void *host[MAX];
+    size_t bytes[MAX], at[MAX], end;
+    int count = 0;
+    HostAux(size_t out_bytes, StageCall *first, StageCall *second = nullptr) : end(out_bytes) {
+        if (first) add(&first->aux, first->aux_bytes);
+        if (second) add(&second->aux, second->aux_bytes);
+    }
+    void add(void **s, size_t n) {
+        slot[count] = s;
+        host[count] = *s;
+        bytes[count] = n;
+        at[count] = (end + 15) & ~(size_t)15;
+        if (host[count]) end = at[count] + n;
+        count++;
     }
     size_t staged_bytes() const { return end; }
     void stage(sdrg_engine *e) const {
-        for (int i = 0; i < 2; i++)
-            if (host[i]) c[i]->aux = e->stream_out.p + at[i];
+        for (int i = 0; i < count; i++)
+            if (host[i]) *slot[i] = e->stream_out.p + at[i];
     }
     int32_t finish(sdrg_engine *e, void *out, size_t out_bytes) const {
-        for (int i = 0; i < 2; i++)
-            if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], c[i]->aux, c[i]->aux_bytes, hipMemcpyDeviceToHost, e->s_main));
+        for (int i = 0; i < count; i++)
+            if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], *slot[i], bytes[i], hipMemcpyDeviceToHost, e->s_main));
         return host_end(e, out, out_bytes);
     }
 };
@@ -3389,6 +3415,140 @@ int32_t sdrg_engine_sideband_host(sdrg_engine *e, const void *chan, int32_t n, v
     return sb_stage(e, "chan", chan, out, n_out, true, n);
 }
 
+// ---- tone detector stage (tones.hip) -------------------------------------------------------------------------------
+
+int32_t sdrg_tones_design(const sdrg_tones_config *cfg, float *table, float *wf, sdrg_tones_scalars *scalars) {
+    if (!cfg) return fail(SDRG_E_INVALID, "null tones config");
+    if (const char *bad = tones_check(*cfg)) return fail(SDRG_E_INVALID, "tones: %s", bad);
+    tones_design(*cfg, table, wf, scalars);
+    return SDRG_OK;
+}
+
+int32_t sdrg_tones_geometry(int32_t *sub_blocks_per_group) {
+    if (!sub_blocks_per_group) return fail(SDRG_E_INVALID, "null sub_blocks_per_group");
+    *sub_blocks_per_group = TONES_GROUP_SUBS;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_tones(sdrg_engine *e, const sdrg_tones_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    TonesStage &s = e->tones;
+    if (cfg) {
+        if (const char *bad = tones_check(*cfg)) return fail(SDRG_E_INVALID, "tones: %s", bad);
+        const size_t S = (size_t)TONES_SUB * (size_t)cfg->sub_blocks, K = (size_t)cfg->n_tones;
+        std::vector<float> des(K * S * 2 + S);
+        sdrg_tones_scalars sc;
+        tones_design(*cfg, des.data(), des.data() + K * S * 2, &sc);
+        DeviceScope dscope(e->device);
+        HIP_TRY(dscope.error());
+        const int32_t rc = upload_floats(&s.d_design, des, "tones design");
+        if (rc) return rc;
+        s.cfg = *cfg;
+        s.sc = sc;
+    }
+    s.set = cfg != nullptr;
+    s.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_tones(const sdrg_engine *e, sdrg_tones_config *cfg, sdrg_tones_scalars *scalars,
+                              uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    const TonesStage &s = e->tones;
+    if (!s.set) return fail(SDRG_E_INVALID, "no tones configuration set");
+    if (cfg) *cfg = s.cfg;
+    if (scalars) *scalars = s.sc;
+    if (samples_consumed) *samples_consumed = s.cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_tones_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->tones.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_tones_max_blocks(const sdrg_engine *e, int32_t *cap_blocks) {
+    if (!e || !cap_blocks) return fail(SDRG_E_INVALID, "null engine or cap_blocks");
+    if (int32_t rc = require_set(e->tones.set, "tones")) return rc;
+    *cap_blocks = e->tones.cap_blocks();
+    return SDRG_OK;
+}
+
+// n_out is the blocks the call completes (*n_blocks); out is powers; aux, the records
+static int32_t tones_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_tones_record *records, StageCall *c) {
+    const TonesStage &s = e->tones;
+    if (int32_t rc = require_set(s.set, "tones")) return rc;
+    if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "tones: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
+    if (in_stride < std::max(n, 1) || in_stride > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "tones: in_stride %d outside [max(n, 1) = %d, max_in = %d]", in_stride, std::max(n, 1),
+                    s.cfg.max_in);
+    c->n = n;
+    c->in_stride = in_stride;
+    c->cap = s.cap_blocks();
+    c->n_out = s.cur.blocks(n, s.S());
+    c->in_bytes = (size_t)e->n_streams * (size_t)in_stride * (size_t)s.cfg.components * sizeof(float);
+    c->out_bytes = (size_t)e->n_streams * (size_t)c->cap * (size_t)s.cfg.n_tones * sizeof(float);
+    c->aux = records;
+    c->aux_bytes = (size_t)e->n_streams * sizeof(*records);
+    return SDRG_OK;
+}
+
+// the sub-blocks a call of n values completes at most: the rows per stream of the sums
+static size_t tones_max_sub(int n) { return (size_t)(n + TONES_SUB - 1) / TONES_SUB; }
+
+static int32_t tones_reserve(sdrg_engine *e, const StageCall &c) {
+    TonesStage &s = e->tones;
+    const int32_t rc = ensure_halves(&s.state, s.half(e->n_streams));
+    const size_t sums = (size_t)e->n_streams * tones_max_sub(c.n) * (size_t)(2 * s.cfg.n_tones + 1);
+    return rc ? rc : ensure_device(&s.sums, std::max<size_t>(sums, 1));
+}
+
+// One call on the main stream: in (rows of in_stride values) and powers, and c.aux, the records or null, in device memory
+static int32_t tones_launch(sdrg_engine *e, const StageCall &c, const void *in, void *powers) {
+    TonesStage &s = e->tones;
+    const size_t half = s.half(e->n_streams), K = (size_t)s.cfg.n_tones, S = (size_t)s.S();
+    TonesParams p{};
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.components = s.cfg.components;
+    p.n_tones = s.cfg.n_tones;
+    p.sub_blocks = s.cfg.sub_blocks;
+    p.soff = s.cur.offset(TONES_SUB);
+    p.sub0 = s.cur.offset(s.S()) / TONES_SUB;
+    p.n_sub = (p.soff + c.n) / TONES_SUB;
+    p.n_blocks = c.n_out;
+    p.cap_blocks = c.cap;
+    p.max_sub = (int)tones_max_sub(c.n);
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.confirm = s.cfg.confirm_blocks;
+    p.release = s.cfg.release_blocks;
+    p.pnorm = s.sc.pnorm, p.enorm = s.sc.enorm, p.min_power = s.sc.min_power, p.dom = s.sc.dom, p.share_thr = s.sc.share_thr;
+    p.table = s.d_design.p;
+    p.wf = s.d_design.p + K * S * 2;
+    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    p.state_new = s.state.next(s.cur, half);
+    p.sums = s.sums.p;
+    p.records = static_cast<sdrg_tones_record *>(c.aux);
+    HIP_TRY(launch_tones(in, e->n_streams, p, static_cast<float *>(powers), e->s_main));
+    s.cur.advance(c.n);  // a call without values wrote powers and the records only: the state stays where it is
+    e->outputs_unmarked = true;
+    return SDRG_OK;
+}
+
+static constexpr auto tones_stage =
+    &stage_call<StageCall, tones_resolve, tones_reserve, tones_launch, int32_t, int32_t, sdrg_tones_record *>;
+
+int32_t sdrg_engine_tones_device(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *powers,
+                                 sdrg_tones_record *records, int32_t *n_blocks) {
+    return tones_stage(e, "in", in, powers, n_blocks, false, in_stride, n, records);
+}
+
+int32_t sdrg_engine_tones_host(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *powers,
+                               sdrg_tones_record *records, int32_t *n_blocks) {
+    return tones_stage(e, "in", in, powers, n_blocks, true, in_stride, n, records);
+}
+
 // ---- the chains: DDC (-> squelch) (-> AGC) -> demodulator or sideband (-> resampler), host memory in and out --------
 
 // The stage that turns the channel into audio.  What a chain asks of it, whichever it is: whether it is set, its
@@ -3420,12 +3580,21 @@ static DetectorView detector_view(const sdrg_engine *e, Detector det) {
 // x_reserve of the call has returned SDRG_OK, so a call that fails for want of memory has advanced no stage's cursor:
 // "commits nothing in any stage" (include/sdrg.h) holds for SDRG_E_NOMEM as for the refusals.
 // The squelch, then the AGC, work in place on the channel between the DDC and the demodulator, and their records
-// (unless null) come back with the audio, staged behind it in stream_out.
+// (unless null) come back with the audio, staged behind it in stream_out.  With `tap` (listen_tones_host) the tone stage
+// reads the detector's float rows where they lie on the device, ahead of the resampler, and its powers and records are
+// staged behind the other records.
+struct ToneTap {
+    float *powers;
+    sdrg_tones_record *records;
+    int32_t *n_blocks;
+};
+
 static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const void *iq, int32_t fmt, void *out,
                           int32_t *n_out, sdrg_squelch_record *sq_records = nullptr,
-                          sdrg_agc_record *agc_records = nullptr) {
+                          sdrg_agc_record *agc_records = nullptr, const ToneTap *tap = nullptr) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    if (tap && (!tap->powers || !tap->n_blocks)) return fail(SDRG_E_INVALID, "null powers or n_blocks");
     if (steps & ~(SDRG_LISTEN_SQUELCH | SDRG_LISTEN_AGC | SDRG_LISTEN_RESAMPLE))
         return fail(SDRG_E_INVALID, "listen: unknown bits in steps 0x%x", (unsigned)steps);
     const bool squelch = steps & SDRG_LISTEN_SQUELCH, agc = steps & SDRG_LISTEN_AGC, resample = steps & SDRG_LISTEN_RESAMPLE;
@@ -3434,8 +3603,9 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     if (!rc && resample) rc = require_set(e->rs.set, "resample");
     if (!rc && squelch) rc = require_set(e->sq.set, "squelch");
     if (!rc && agc) rc = require_set(e->agc.set, "agc");
+    if (!rc && tap) rc = require_set(e->tones.set, "tones");
     DdcCall d;
-    StageCall q, g, a, r;  // the squelch's, the AGC's, the detector's and the resampler's
+    StageCall q, g, a, r, t;  // the squelch's, the AGC's, the detector's, the resampler's and the tone stage's
     if (!rc) rc = ddc_resolve(e, fmt, &d);
     if (rc) return rc;
     // the checks between the stages come before the later stages' own: after them those cannot refuse their n
@@ -3455,18 +3625,33 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
             return fail(SDRG_E_INVALID, "resample max_in %d smaller than the %s's row length %d", e->rs.cfg.max_in, v.name,
                         v.cap);
     }
+    if (tap) {
+        if (e->tones.cfg.components != 1)
+            return fail(SDRG_E_INVALID, "the tone stage reads real audio here: tones components must be 1");
+        if (!v.f32)
+            return fail(SDRG_E_INVALID, "the tone stage reads float audio: %s out_format must be %s", v.name, v.f32_name);
+        if (v.components != 1) return fail(SDRG_E_INVALID, "the tone stage reads one value per output of the %s", v.name);
+        if (e->tones.cfg.max_in < v.cap)
+            return fail(SDRG_E_INVALID, "tones max_in %d smaller than the %s's row length %d", e->tones.cfg.max_in, v.name,
+                        v.cap);
+    }
     rc = v.resolve(e, d.n_out, &a);
     a.in_stride = d.cap;  // the channel's rows are the DDC's
+    if (!rc && tap) rc = tones_resolve(e, a.cap, a.n_out, tap->records, &t);
     if (!rc && resample) rc = rs_resolve(e, a.cap, a.n_out, &r);
     if (!rc && squelch) rc = sq_resolve(e, d.cap, d.n_out, sq_records, &q);
     if (!rc && agc) rc = agc_resolve(e, d.cap, d.n_out, agc_records, &g);
     if (rc) return rc;
     const StageCall &last = resample ? r : a;
     // a stage that is not in the mask was not resolved: its aux is null, and nothing is staged or copied for it
-    const HostAux aux(last.out_bytes, &q, &g);
+    HostAux aux(last.out_bytes, &q, &g);
+    void *powers = tap ? tap->powers : nullptr;  // the caller's, then where the launch writes them
+    if (tap) aux.add(&powers, t.out_bytes);
+    if (tap) aux.add(&t.aux, t.aux_bytes);
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     rc = ddc_reserve(e, d);
+    if (!rc && tap) rc = tones_reserve(e, t);
     if (!rc && squelch) rc = sq_reserve(e, q);
     if (!rc && agc) rc = agc_reserve(e, g);
     if (!rc) rc = v.reserve(e, a);
@@ -3480,16 +3665,25 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     if (!rc && agc) rc = agc_launch(e, g, e->chain_chan.p, e->chain_chan.p);
     void *audio = resample ? (void *)e->chain_audio.p : (void *)e->stream_out.p;
     if (!rc) rc = v.launch(e, a, e->chain_chan.p, audio);
+    if (!rc && tap) rc = tones_launch(e, t, audio, powers);
     if (!rc && resample) rc = rs_launch(e, r, e->chain_audio.p, e->stream_out.p);
     if (!rc) rc = aux.finish(e, out, last.out_bytes);
     if (rc) return rc;
     *n_out = last.n_out;
+    if (tap) *tap->n_blocks = t.n_out;
     return SDRG_OK;
 }
 
 int32_t sdrg_engine_listen_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
                                 sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records) {
     return chain_host(e, Detector::Demod, steps, iq, fmt, out, n_out, squelch_records, agc_records);
+}
+
+int32_t sdrg_engine_listen_tones_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
+                                      sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records, float *powers,
+                                      sdrg_tones_record *tone_records, int32_t *n_blocks) {
+    const ToneTap tap{powers, tone_records, n_blocks};
+    return chain_host(e, Detector::Demod, steps, iq, fmt, out, n_out, squelch_records, agc_records, &tap);
 }
 
 int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {

@@ -352,6 +352,33 @@ static_assert(SDRG_BLANKER_MAX_BLOCK == BLOCK_MAX && SDRG_BLANKER_MAX_IN == BLOC
 constexpr int blanker_state_words(int block) { return BLANKER_STATE_HEAD + block + BLANKER_FLAGS + 2 * BLANKER_MAX_LEAD; }
 hipError_t launch_blanker(const void *iq, int fmt, int n_streams, BlankerParams p, float *out, hipStream_t stream);
 
+// Tone detector stage (tones.hip): per stream the n values at in + stream * in_stride (floats, or float pairs at
+// components 2) are the positions [soff, soff + n) counted from the start of the sub-block of 64 in progress, soff = g
+// mod 64; that sub-block is the sub0-th of its block of sub_blocks, sub0 = (g mod S) / 64.  n_sub = (soff + n) / 64
+// sub-blocks and n_blocks = (sub0 + n_sub) / sub_blocks blocks complete.  table [K][S][2] (c, s) and wf [S] are the
+// design.  state_old / state_new [n_streams][tones_state_words(K, components)] floats: the TONES_STATE_HEAD words {tone,
+// last, run, miss (int bits), power, share, 0, 0}, the 2 K + 1 accumulators (C_0 .. C_(K-1), S_0 .. S_(K-1), E) of the
+// block in progress, and the values so far of the sub-block in progress; fresh: state_old is not read (and soff, sub0
+// are 0).  sums [n_streams][max_sub][2 K + 1] floats is scratch, the completed sub-blocks' sums in the accumulators'
+// order, max_sub the rows per stream.  Writes powers [n_streams][cap_blocks][K] whole (+0 from n_blocks on), and, if n >
+// 0, state_new; records [n_streams] unless nullptr.  n_streams is the launcher's.
+struct TonesParams {
+    int n, in_stride, components, n_tones, sub_blocks, soff, sub0, n_sub, n_blocks, cap_blocks, max_sub, fresh;
+    int confirm, release;
+    float pnorm, enorm, min_power, dom, share_thr;
+    const float *table, *wf;
+    const float *state_old;
+    float *state_new;
+    float *sums;
+    sdrg_tones_record *records;
+    int n_streams;
+};
+constexpr int TONES_STATE_HEAD = 8;
+constexpr int TONES_SUB = 64;        // values per sub-block: one per lane of a wave
+constexpr int TONES_GROUP_SUBS = 4;  // sub-blocks per workgroup of the correlate kernel, one per wave
+constexpr int tones_state_words(int K, int components) { return TONES_STATE_HEAD + 2 * K + 1 + (TONES_SUB - 1) * components; }
+hipError_t launch_tones(const void *in, int n_streams, TonesParams p, float *powers, hipStream_t stream);
+
 // Sideband stage (sideband.hip): per stream and output j, A = sum_k cr[k] zr[first + j decim - k] and Bm = sum_k ci[k]
 // zi[first + j decim - k], z the n complex samples at chan + stream * in_stride (float2); u = A - Bm, l = A + Bm.  The
 // history holds samples, [taps - 1][2] per stream.  Writes out [n_streams][cap] (u gain, l gain, or at mode BOTH the

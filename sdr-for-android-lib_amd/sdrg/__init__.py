@@ -156,6 +156,9 @@ EXPORTS = [
     "sdrg_blanker_design", "sdrg_blanker_geometry", "sdrg_engine_set_blanker", "sdrg_engine_get_blanker",
     "sdrg_engine_blanker_reset", "sdrg_engine_blanker_device", "sdrg_engine_blanker_host",
     "sdrg_engine_clean_process_host",
+    "sdrg_tones_design", "sdrg_tones_geometry", "sdrg_engine_set_tones", "sdrg_engine_get_tones",
+    "sdrg_engine_tones_reset", "sdrg_engine_tones_max_blocks", "sdrg_engine_tones_device", "sdrg_engine_tones_host",
+    "sdrg_engine_listen_tones_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -281,6 +284,51 @@ class BlankerConfig(ctypes.Structure):
 BlankerRecord = np.dtype([("level", "<f4"), ("level_db", "<f4"), ("hits", "<i4"), ("blanked", "<i4")])
 CLEAN_IQCORR = 1  # SDRG_CLEAN_IQCORR
 BLANKER_MAX_LEAD, BLANKER_MAX_TAIL = 16, 64
+
+
+TONES_MAX_TONES, TONES_MAX_SUB_BLOCKS, TONES_MAX_IN = 64, 256, 65536
+TONES_RECT, TONES_HANN = 0, 1
+
+
+class TonesConfig(ctypes.Structure):
+    """sdrg_tones_config: the tone detector stage's rate, frequencies, decision thresholds, components, tone count,
+    block length in sub-blocks of 64, window, latch counts and row length (include/sdrg.h)."""
+    _fields_ = [("rate_hz", ctypes.c_double), ("freq_hz", ctypes.c_double * TONES_MAX_TONES),
+                ("min_db", ctypes.c_double), ("dominance_db", ctypes.c_double), ("share", ctypes.c_double),
+                ("components", ctypes.c_int32), ("n_tones", ctypes.c_int32), ("sub_blocks", ctypes.c_int32),
+                ("window", ctypes.c_int32), ("confirm_blocks", ctypes.c_int32), ("release_blocks", ctypes.c_int32),
+                ("max_in", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class TonesScalars(ctypes.Structure):
+    """sdrg_tones_scalars: the five scalars of the tone detector's design."""
+    _fields_ = [("pnorm", ctypes.c_float), ("enorm", ctypes.c_float), ("min_power", ctypes.c_float),
+                ("dom", ctypes.c_float), ("share_thr", ctypes.c_float)]
+
+
+# sdrg_tones_record
+TonesRecord = np.dtype([("tone", "<i4"), ("candidate", "<i4"), ("power", "<f4"), ("power_db", "<f4"), ("share", "<f4"),
+                        ("tone_blocks", "<i4"), ("changes", "<i4"), ("run", "<i4")])
+
+
+def _tones_filled(fields: dict) -> TonesConfig:
+    """A TonesConfig of `fields`; freq_hz is a sequence of at most 64 frequencies, and n_tones defaults to its length."""
+    fields = dict(fields)
+    freq = [float(f) for f in fields.pop("freq_hz", ())]
+    if len(freq) > TONES_MAX_TONES:
+        raise TypeError(f"freq_hz has {len(freq)} entries, more than {TONES_MAX_TONES}")
+    fields.setdefault("n_tones", len(freq))
+    c = _filled(TonesConfig, "tones", fields)
+    for k, f in enumerate(freq):
+        c.freq_hz[k] = f
+    return c
+
+
+def _tones_dict(c: TonesConfig) -> dict:
+    d = _as_dict(c)
+    d["freq_hz"] = [c.freq_hz[k] for k in range(max(0, min(c.n_tones, TONES_MAX_TONES)))]
+    del d["reserved"]
+    return d
 
 
 class AgcConfig(ctypes.Structure):
@@ -564,6 +612,17 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_blanker_device": (_I32, [P, P, _I32, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_blanker_host": (_I32, [P, P, _I32, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_clean_process_host": (_I32, [P, P, _I32, _I32, _I32, P, P, P, _I64, P, P]),
+        "sdrg_tones_design": (_I32, [ctypes.POINTER(TonesConfig), P, P, ctypes.POINTER(TonesScalars)]),
+        "sdrg_tones_geometry": (_I32, [ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_tones": (_I32, [P, ctypes.POINTER(TonesConfig)]),
+        "sdrg_engine_get_tones": (_I32, [P, ctypes.POINTER(TonesConfig), ctypes.POINTER(TonesScalars),
+                                         ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_tones_reset": (_I32, [P]),
+        "sdrg_engine_tones_max_blocks": (_I32, [P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_tones_device": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_tones_host": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_listen_tones_host": (_I32, [P, _I32, P, _I32, P, ctypes.POINTER(_I32), P, P, P, P,
+                                                 ctypes.POINTER(_I32)]),
         "sdrg_engine_set_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig)]),
         "sdrg_engine_get_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
                                            ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_uint64)]),
@@ -892,6 +951,30 @@ def blanker_geometry(block: int) -> tuple[int, int]:
     f, t = _I32(), _I32()
     _check(load().sdrg_blanker_geometry(block, ctypes.byref(f), ctypes.byref(t)), "blanker_geometry")
     return f.value, t.value
+
+
+def _scalars_dict(sc: TonesScalars) -> dict:
+    return {k: np.float32(getattr(sc, k)) for k, _ in sc._fields_}
+
+
+def tones_design(**fields) -> dict:
+    """The tone detector stage's design for a configuration (host-side, no device): table float32 [K][S][2] (c, s), wf
+    float32 [S] and pnorm, enorm, min_power, dom and share_thr as np.float32.  The fields are sdrg_tones_config's
+    (fields left out are 0; freq_hz a sequence, n_tones its length unless given)."""
+    c = _tones_filled(fields)
+    _check(load().sdrg_tones_design(ctypes.byref(c), None, None, None), "tones_design")
+    S, K, sc = 64 * c.sub_blocks, c.n_tones, TonesScalars()
+    table, wf = np.empty((K, S, 2), np.float32), np.empty(S, np.float32)
+    _check(load().sdrg_tones_design(ctypes.byref(c), _ptr(table), _ptr(wf), ctypes.byref(sc)), "tones_design")
+    return dict(_scalars_dict(sc), table=table, wf=wf)
+
+
+def tones_geometry() -> int:
+    """Consecutive sub-blocks of 64 values per workgroup of the tone detector's correlate kernel, counted from the
+    start of the sub-block in progress."""
+    t = _I32()
+    _check(load().sdrg_tones_geometry(ctypes.byref(t)), "tones_geometry")
+    return t.value
 
 
 def agc_design(**fields) -> dict:
@@ -1597,6 +1680,69 @@ class Engine:
                                                      _ptr(pcm) if plen > 0 else None, now_ms, _ptr(iq_rec),
                                                      _ptr(blank_rec)), "clean_process_host")
         return spec, recs, pcm, iq_rec, blank_rec
+
+    # ---- tone detector stage ---------------------------------------------------------------------
+    def set_tones(self, **fields) -> None:
+        """sdrg_engine_set_tones: the fields of sdrg_tones_config (fields left out are 0; freq_hz a sequence, n_tones
+        its length unless given); set_tones(off=True) switches the stage off."""
+        fields = dict(fields)
+        off = fields.pop("off", False)
+        if off and fields:
+            raise TypeError("off=True takes no other field")
+        c = None if off else ctypes.byref(_tones_filled(fields))
+        _check(load().sdrg_engine_set_tones(self._h, c), "set_tones")
+
+    def tones_config(self) -> dict:
+        """The configuration in force (freq_hz as a list of n_tones), plus its scalars (np.float32) and
+        samples_consumed."""
+        c, sc, g = TonesConfig(), TonesScalars(), ctypes.c_uint64()
+        _check(load().sdrg_engine_get_tones(self._h, ctypes.byref(c), ctypes.byref(sc), ctypes.byref(g)), "get_tones")
+        return dict(_tones_dict(c), **_scalars_dict(sc), samples_consumed=g.value)
+
+    def tones_reset(self) -> None:
+        _check(load().sdrg_engine_tones_reset(self._h), "tones_reset")
+
+    def tones_max_blocks(self) -> int:
+        """cap_blocks = ceil(max_in / S): the rows of powers per stream."""
+        return self._i32_call(load().sdrg_engine_tones_max_blocks, "tones_max_blocks")
+
+    def tones_device(self, in_ptr: int, in_stride: int, n: int, powers_ptr: int, records_ptr: int | None = None) -> int:
+        """Device path: in [n_streams][in_stride] values, float32 or complex64 by components (the first n of every row
+        are the call's), powers float32 [n_streams][cap_blocks][K] out and, unless records_ptr is None, [n_streams]
+        TonesRecord; asynchronous on the main stream.  Returns n_blocks, the blocks the call completed."""
+        return self._i32_call(load().sdrg_engine_tones_device, "tones_device", in_ptr, in_stride, n, powers_ptr,
+                              records_ptr)
+
+    def tones_host(self, values: np.ndarray, want_records: bool = True):
+        """Host path: values is float32 (components 1) or complex64 (components 2) [n_streams][n], n <= max_in.
+        Returns (powers float32 [n_streams][n_blocks][K], the records [n_streams] TonesRecord or None, n_blocks)."""
+        cfg = self.tones_config()
+        dtype = np.float32 if cfg["components"] == 1 else np.complex64
+        values = np.ascontiguousarray(values, dtype).reshape(self.n_streams, -1)
+        n = values.shape[1]
+        rows = values if n else np.zeros((self.n_streams, 1), dtype)  # a call without values still wants rows
+        powers = np.empty((self.n_streams, self.tones_max_blocks(), cfg["n_tones"]), np.float32)
+        rec = np.empty(self.n_streams, TonesRecord) if want_records else None
+        n_blocks = self._i32_call(load().sdrg_engine_tones_host, "tones_host", _ptr(rows), rows.shape[1], n,
+                                  _ptr(powers), _ptr(rec))
+        return powers[:, :n_blocks], rec, n_blocks
+
+    def listen_tones(self, iq: np.ndarray, fmt: int = CS8, steps: int = 0, want_records: bool = True):
+        """sdrg_engine_listen_tones_host: listen() with the tone detector reading the demodulator's float audio on the
+        device, ahead of the resampler.  Returns (the audio [n_streams][n_out], the squelch's records or None, the
+        AGC's records or None, powers float32 [n_streams][n_blocks][K], the tone records or None, n_blocks)."""
+        iq, n_out, n_blocks = self._iq(iq, fmt), _I32(), _I32()
+        out = self._resample_out() if steps & LISTEN_RESAMPLE else self._demod_out()
+        sq_rec = np.empty(self.n_streams, SquelchRecord) if steps & LISTEN_SQUELCH else None
+        agc_rec = np.empty(self.n_streams, AGC_RECORD_DTYPE) if steps & LISTEN_AGC else None
+        c = TonesConfig()
+        _check(load().sdrg_engine_get_tones(self._h, ctypes.byref(c), None, None), "get_tones")
+        powers = np.empty((self.n_streams, self.tones_max_blocks(), c.n_tones), np.float32)
+        rec = np.empty(self.n_streams, TonesRecord) if want_records else None
+        _check(load().sdrg_engine_listen_tones_host(self._h, steps, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out),
+                                                    _ptr(sq_rec), _ptr(agc_rec), _ptr(powers), _ptr(rec),
+                                                    ctypes.byref(n_blocks)), "listen_tones_host")
+        return out[..., :n_out.value], sq_rec, agc_rec, powers[:, :n_blocks.value], rec, n_blocks.value
 
     # ---- AGC stage --------------------------------------------------------------------------------
     def set_agc(self, **fields) -> None:
