@@ -1627,6 +1627,133 @@ int32_t sdrg_engine_listen_tones_host(sdrg_engine *eng, int32_t steps, const voi
                                       sdrg_agc_record *agc_records, float *powers, sdrg_tones_record *tone_records,
                                       int32_t *n_blocks);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the AFC stage, automatic frequency control: the carrier offset of a CF32
+ * channel estimated block by block and removed per stream.  Per stream, the n CF32 channel samples of a call (the DDC's
+ * out, a row of the channelizer's, or any rows in device memory) are cut into blocks of S samples at the global indices
+ * that are multiples of S, as the squelch's are.  Each completed block's lag-1 product sum (the mean of z[i] conj(z[i -
+ * 1]), whose angle is the phase step per sample) moves a smoothed estimate; its coherence against the smoothed power
+ * decides whether the stream is locked, and while it is, the estimate sets the frequency of a phase-continuous NCO that
+ * mixes the following blocks down.  The estimate comes from the input, not from the corrected output (feed-forward): no
+ * decision reaches back into the block that produced it, the stage adds no delay and out has one sample per input
+ * sample.  Over the whole life of a stream (the calls' samples concatenated, whatever their lengths) the result is that
+ * of one call.  All arithmetic is float, every product, sum, quotient and root rounded on its own, unless "double" is
+ * stated; denormals are kept.  A non-finite sample makes that stream's outputs and records unspecified from then on.
+ *   config     channel_rate finite, > 0; max_offset_hz in (0, channel_rate / 4]; tau_blocks finite, >= 0; floor_db
+ *              finite; lock_threshold in [0, 1]; mode SDRG_AFC_TRACK or SDRG_AFC_MEASURE (anything else is refused);
+ *              block S a power of two in [SDRG_AFC_MIN_BLOCK, SDRG_AFC_MAX_BLOCK]; max_in in [1, 2^20]: every call's
+ *              n <= in_stride <= max_in.  A rejected set_afc changes nothing; an accepted one, and
+ *              sdrg_engine_afc_reset, restart every stream: g = 0, A = B = P = +0, unseeded, unlocked, coh = +0,
+ *              inc = 0, Phi = 0.
+ *   design     sdrg_afc_design, in double, each result rounded to float once: beta = 1 - exp(-1 / tau_blocks), and
+ *              exactly 1.0f at tau_blocks = 0; floor_thr = 10^(floor_db / 10), refused unless it is a finite positive
+ *              float; lock_thr = (float)lock_threshold; max_s = (float)(2^32 max_offset_hz / channel_rate), at most
+ *              2^30; K = (float)(2^31 / pi); hz_per_inc = (float)(channel_rate / 2^32); rad_per_inc =
+ *              (float)(pi / 2^31).
+ *   products   for the sample z = (zr, zi) at in-block index i >= 1, with z' = (zr', zi') the sample before it:
+ *              pr = zr zr' + zi zi', pi = zi zr' - zr zi' (the demodulator's FM products, in its order); at i = 0,
+ *              pr = pi = +0: a block's statistics depend on its own samples only, and a block seam costs one product
+ *              in S.  q = zr zr + zi zi.
+ *   block      T(.) is the adjacent-pair tree over a block's S values in order (q'[i] = q[2 i] + q[2 i + 1] until one
+ *              value is left), r = 1 / S: Rr = T(pr) r, Ri = T(pi) r, W = T(q) r.
+ *   step       for each completed block, in order: if W < floor_thr the block is held (nothing moves, held counts one).
+ *              Otherwise, if not yet seeded, (A, B, P) = (Rr, Ri, W) and seeded = 1, else A = A + beta (Rr - A) and the
+ *              same for B with Ri and P with W (also at beta = 1); then coh = sqrtf(A A + B B) / P and
+ *              locked = coh >= lock_thr.  If locked: phi = sdrg_atan2f(B, A) (the demodulator's), s = phi K,
+ *              s = fminf(fmaxf(s, -max_s), max_s), inc = (int32_t) rintf(s), ties to even; if not, inc stays where it
+ *              is.  inc_k is inc after global block k; inc_-1 = 0.
+ *   phase      Phi_0 = 0, Phi_(k+1) = (uint32)(Phi_k + (uint32) inc_(k-1) * S); the sample at in-block index i of global
+ *              block k has ph = (uint32)(Phi_k + (uint32) inc_(k-1) * i): the frequency moves at a block seam only, and
+ *              the phase never jumps.  Block k is mixed by the estimate after block k - 1.
+ *   output     SDRG_AFC_TRACK: H = hi[ph >> 22], L = lo[(ph >> 12) & 1023] of sdrg_nco_tables; wr = H.re L.re -
+ *              H.im L.im, wi = H.re L.im + H.im L.re; yr = zr wr - zi wi, yi = zr wi + zi wr (the DDC's mix, in its
+ *              order): a positive measured offset is mixed down.  inc = 0 goes through the table too, and hi[0] lo[0]
+ *              = 1 leaves the sample's bits but for the sign of a zero.  out [n_streams][in_stride][2] float, 8-byte
+ *              aligned: every byte is written by every call, zero from n on.  out may be chan itself; any other overlap
+ *              is undefined.  SDRG_AFC_MEASURE: out must be NULL, and nothing is written but the records.  n = 0 is a
+ *              valid call: it writes out and the records and leaves the state where it is.
+ *   records    sdrg_afc_record [n_streams], written by every call: offset_hz = (float) inc * hz_per_inc and
+ *              step = (float) inc * rad_per_inc (radians per sample) of inc after the last block completed so far;
+ *              inc itself; coherence is the last computed coh (+0 before the first); level = P; level_db = 10.0f *
+ *              log10f(P + 1e-20f) with glibc's log10f bit for bit (the squelch's); held_blocks is how many of the
+ *              blocks this call completed were held; flags = locked | seeded << 1.  *n_blocks = floor((g + n) / S) -
+ *              floor(g / S) is set on the host before the call returns.
+ *   state      per stream the samples of the block in progress (S - 1 pairs of floats), A, B, P, coh, inc, Phi and the
+ *              two flags, in device memory (allocated at the first afc call), in two halves a call reads and writes in
+ *              turn; per engine g, advanced by n once the call's launches have been issued: a failed call commits
+ *              nothing.  Calls shorter than a block accumulate; any number of calls may share one block.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_AFC_TRACK 1
+#define SDRG_AFC_MEASURE 2
+#define SDRG_AFC_LOCKED 1 /* sdrg_afc_record.flags */
+#define SDRG_AFC_SEEDED 2
+#define SDRG_AFC_MIN_BLOCK 16
+#define SDRG_AFC_MAX_BLOCK 1024
+#define SDRG_AFC_MAX_IN 1048576
+typedef struct sdrg_afc_config {
+    double channel_rate;   /* Hz: the rate of the channel's samples */
+    double max_offset_hz;  /* the estimate is clamped to +- this */
+    double tau_blocks;
+    double floor_db;       /* blocks whose mean power is under 10^(floor_db / 10) move nothing */
+    double lock_threshold; /* the coherence from which the estimate steers the NCO */
+    int32_t mode;
+    int32_t block;
+    int32_t max_in;
+} sdrg_afc_config;
+
+typedef struct sdrg_afc_design_values {
+    float beta, floor_thr, lock_thr, max_s, K, hz_per_inc, rad_per_inc;
+} sdrg_afc_design_values;
+
+typedef struct sdrg_afc_record {
+    float offset_hz;
+    float step;
+    int32_t inc;
+    float coherence;
+    float level;
+    float level_db;
+    int32_t held_blocks;
+    int32_t flags;
+} sdrg_afc_record;
+
+/* Host-only, no device.  After the checks of set_afc: the seven design values above. */
+int32_t sdrg_afc_design(const sdrg_afc_config *cfg, sdrg_afc_design_values *design);
+/* Host-only: *tile = max(512, block), how many consecutive samples one workgroup takes at a time: of the moments kernel
+ * those of the positions [k tile, (k + 1) tile) counted from the start of the block in progress; the pass kernel's
+ * workgroup k takes the four tiles of the call's indices [4 k tile, 4 (k + 1) tile) one after the other. */
+int32_t sdrg_afc_geometry(int32_t block, int32_t *tile);
+/* Host-only: inc * channel_rate / 2^32 in double: a record's inc in Hz without the float's rounding (to feed a DDC's
+ * offset_hz, for instance).  NaN for a channel_rate that is not finite and positive. */
+double sdrg_afc_offset_hz(int32_t inc, double channel_rate);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the stage.  An afc call while it is off returns SDRG_E_INVALID and
+ * writes nothing. */
+int32_t sdrg_engine_set_afc(sdrg_engine *eng, const sdrg_afc_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its design values and g, the samples every stream has consumed
+ * since the last restart; any pointer may be NULL. */
+int32_t sdrg_engine_get_afc(const sdrg_engine *eng, sdrg_afc_config *cfg, sdrg_afc_design_values *design,
+                            uint64_t *samples_consumed);
+int32_t sdrg_engine_afc_reset(sdrg_engine *eng);
+/* chan and out: n_streams rows of in_stride complex samples ([n_streams][in_stride][2] float), of which the first n of
+ * every row are this call's (0 <= n <= in_stride <= max_in); records [n_streams] or NULL; all in device memory.  In
+ * SDRG_AFC_TRACK mode out must not be NULL, in SDRG_AFC_MEASURE mode it must be: either is refused with SDRG_E_INVALID.
+ * Stream rules and waiting as sdrg_engine_squelch_device. */
+int32_t sdrg_engine_afc_device(sdrg_engine *eng, const void *chan, int32_t in_stride, int32_t n, void *out,
+                               sdrg_afc_record *records, int32_t *n_blocks);
+/* Host buffers of the same shapes, synchronous; all n_streams * in_stride samples of chan are copied. */
+int32_t sdrg_engine_afc_host(sdrg_engine *eng, const void *chan, int32_t in_stride, int32_t n, void *out,
+                             sdrg_afc_record *records, int32_t *n_blocks);
+/* sdrg_engine_listen_host with the AFC first on the channel: iq through DDC -> AFC -> [squelch] -> [AGC] -> demodulator
+ * -> [resampler], the same mask bits, records and buffers kept on the device; the AFC runs in place on the channel
+ * (in_stride = the DDC's cap, n = the DDC call's n_out) and its records [n_streams] come back unless afc_records is
+ * NULL.  SDRG_E_INVALID, with no stage moved, under listen_host's conditions in its order, with the AFC's among them: the
+ * AFC off, or in SDRG_AFC_MEASURE mode, after the mask's stages' own; its max_in smaller than the DDC's cap, after the
+ * AGC's.  Every buffer is reserved before the first launch: a call that fails for want of memory commits nothing in any
+ * stage either.  The other chain calls never run the AFC, whether or not it is set. */
+int32_t sdrg_engine_listen_afc_host(sdrg_engine *eng, int32_t steps, const void *iq, int32_t fmt, void *out,
+                                    int32_t *n_out, sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records,
+                                    sdrg_afc_record *afc_records);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

@@ -395,6 +395,36 @@ void iqcorr_design(const sdrg_iqcorr_config &c, float *beta_dc, float *beta_bal,
     if (floor_thr) *floor_thr = (float)std::pow(10.0, c.floor_db / 10.0);
 }
 
+// The AFC stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *afc_check(const sdrg_afc_config &c) {
+    if (!std::isfinite(c.channel_rate) || !(c.channel_rate > 0.0)) return "channel_rate must be > 0 and finite";
+    if (!(c.max_offset_hz > 0.0) || !(c.max_offset_hz <= c.channel_rate / 4.0))
+        return "max_offset_hz must be in (0, channel_rate / 4]";
+    if (!(c.tau_blocks >= 0.0) || !std::isfinite(c.tau_blocks)) return "tau_blocks must be >= 0 and finite";
+    if (!std::isfinite(c.floor_db)) return "floor_db must be finite";
+    if (!(c.lock_threshold >= 0.0) || !(c.lock_threshold <= 1.0)) return "lock_threshold must be in [0, 1]";
+    if (c.mode != SDRG_AFC_TRACK && c.mode != SDRG_AFC_MEASURE) return "mode must be SDRG_AFC_TRACK or SDRG_AFC_MEASURE";
+    if (c.block < SDRG_AFC_MIN_BLOCK || c.block > SDRG_AFC_MAX_BLOCK || (c.block & (c.block - 1)) != 0)
+        return "block must be a power of two in [16, 1024]";
+    if (c.max_in < 1 || c.max_in > SDRG_AFC_MAX_IN) return "max_in outside [1, 2^20]";
+    const float floor_thr = afc_design(c).floor_thr;
+    if (!std::isfinite(floor_thr) || !(floor_thr > 0.0f)) return "10^(floor_db / 10) is not a finite, positive float";
+    return nullptr;
+}
+
+// The AFC stage's constants (sdrg.h), in double, each rounded to float once
+sdrg_afc_design_values afc_design(const sdrg_afc_config &c) {
+    sdrg_afc_design_values d;
+    d.beta = c.tau_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.tau_blocks)) : 1.0f;
+    d.floor_thr = (float)std::pow(10.0, c.floor_db / 10.0);
+    d.lock_thr = (float)c.lock_threshold;
+    d.max_s = (float)(4294967296.0 * c.max_offset_hz / c.channel_rate);  // at most 2^30: max_offset_hz <= rate / 4
+    d.K = (float)(2147483648.0 / M_PI);
+    d.hz_per_inc = (float)(c.channel_rate / 4294967296.0);
+    d.rad_per_inc = (float)(M_PI / 2147483648.0);
+    return d;
+}
+
 // The noise blanker stage's configuration rules (sdrg.h): nullptr, or what is wrong
 const char *blanker_check(const sdrg_blanker_config &c) {
     if (!(c.tau_blocks >= 0.0) || !std::isfinite(c.tau_blocks)) return "tau_blocks must be >= 0 and finite";

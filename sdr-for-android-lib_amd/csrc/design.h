@@ -41,6 +41,9 @@ void squelch_design(const sdrg_squelch_config &cfg, float *open_thr, float *clos
 // be null)
 const char *iqcorr_check(const sdrg_iqcorr_config &cfg);
 void iqcorr_design(const sdrg_iqcorr_config &cfg, float *beta_dc, float *beta_bal, float *floor_thr);
+// AFC stage: the configuration rules (nullptr = valid) and the seven design values
+const char *afc_check(const sdrg_afc_config &cfg);
+sdrg_afc_design_values afc_design(const sdrg_afc_config &cfg);
 const char *blanker_check(const sdrg_blanker_config &cfg);
 void blanker_design(const sdrg_blanker_config &cfg, float *beta, float *ratio, float *floor_thr);
 // tone detector stage: the configuration rules (nullptr = valid) and the design, table [K][S][2], wf [S] and the five

@@ -261,6 +261,21 @@ struct IqcorrStage {
     size_t blocks() const { return (size_t)BlockCursor::cap(cfg.max_in, cfg.block); }
 };
 
+// AFC stage (sdrg_engine_set_afc / afc_device / afc_host / listen_afc_host; afc.hip)
+struct AfcStage {
+    sdrg_afc_config cfg{};
+    bool set = false;
+    BlockCursor cur;
+    sdrg_afc_design_values des{};  // afc_design of cfg
+    // halves of [n_streams][2 S + AFC_STATE_HEAD]: the eight words, the block's samples so far
+    DevicePingPong<float> state;
+    // [the most blocks a call completes]: [3][n_streams] moments, then one more of [2][n_streams] words (Phi, inc)
+    DeviceBuf<float> blk;
+    bool track() const { return cfg.mode == SDRG_AFC_TRACK; }
+    size_t half(int B) const { return (size_t)B * (size_t)(2 * cfg.block + AFC_STATE_HEAD); }
+    size_t blocks() const { return (size_t)BlockCursor::cap(cfg.max_in, cfg.block); }
+};
+
 // noise blanker stage (sdrg_engine_set_blanker / blanker_device / blanker_host / clean_process_host; blanker.hip)
 struct BlankerStage {
     sdrg_blanker_config cfg{};
@@ -591,6 +606,7 @@ struct sdrg_engine {
     AgcStage agc;
     SidebandStage sb;
     IqcorrStage iqc;
+    AfcStage afc;
     BlankerStage blank;
     TonesStage tones;
     // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host,
@@ -691,8 +707,8 @@ int32_t host_begin(sdrg_engine *e, const void *in, size_t in_bytes, size_t out_b
     return SDRG_OK;
 }
 
-int32_t host_end(sdrg_engine *e, void *out, size_t out_bytes) {
-    HIP_TRY(hipMemcpyAsync(out, e->stream_out.p, out_bytes, hipMemcpyDeviceToHost, e->s_main));
+int32_t host_end(sdrg_engine *e, void *out, size_t out_bytes) {  // no rows (the AFC measuring): the wait alone
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(out, e->stream_out.p, out_bytes, hipMemcpyDeviceToHost, e->s_main));
     HIP_TRY(hipStreamSynchronize(e->s_main));
     return SDRG_OK;
 }
@@ -719,7 +735,7 @@ int32_t ensure_nco_table(sdrg_engine *e) {
 }
 
 // ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband, IQ correction, blanker,
-// ---- tone detector -------------------------------------------------------------------------------------------------
+// ---- tone detector, AFC --------------------------------------------------------------------------------------------
 //
 // A call of a stage goes through three steps.  x_resolve makes every refusal and touches nothing; what it finds goes
 // into the stage's XCall.  x_reserve does everything that can fail without a launch (the stage's device buffers, the
@@ -2029,6 +2045,132 @@ int32_t sdrg_engine_iqcorr_device(sdrg_engine *e, const void *iq, int32_t fmt, i
 int32_t sdrg_engine_iqcorr_host(sdrg_engine *e, const void *iq, int32_t fmt, int32_t in_stride, int32_t n, void *out,
                                 sdrg_iqcorr_record *records, int32_t *n_blocks) {
     return iqc_stage(e, "iq", iq, out, n_blocks, true, fmt, in_stride, n, records);
+}
+
+// ---- AFC stage (afc.hip) -------------------------------------------------------------------------------------------
+
+int32_t sdrg_afc_design(const sdrg_afc_config *cfg, sdrg_afc_design_values *design) {
+    if (!cfg || !design) return fail(SDRG_E_INVALID, "null afc config or design");
+    if (const char *bad = afc_check(*cfg)) return fail(SDRG_E_INVALID, "afc: %s", bad);
+    *design = afc_design(*cfg);
+    return SDRG_OK;
+}
+
+int32_t sdrg_afc_geometry(int32_t block, int32_t *tile) { return block_geometry("afc", block, tile); }
+
+double sdrg_afc_offset_hz(int32_t inc, double channel_rate) {
+    if (!std::isfinite(channel_rate) || !(channel_rate > 0.0)) return NAN;
+    return (double)inc * channel_rate / 4294967296.0;
+}
+
+int32_t sdrg_engine_set_afc(sdrg_engine *e, const sdrg_afc_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    AfcStage &s = e->afc;
+    if (cfg) {
+        if (const char *bad = afc_check(*cfg)) return fail(SDRG_E_INVALID, "afc: %s", bad);
+        s.cfg = *cfg;
+        s.des = afc_design(*cfg);
+    }
+    s.set = cfg != nullptr;
+    s.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_afc(const sdrg_engine *e, sdrg_afc_config *cfg, sdrg_afc_design_values *design,
+                            uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    const AfcStage &s = e->afc;
+    if (!s.set) return fail(SDRG_E_INVALID, "no afc configuration set");
+    if (cfg) *cfg = s.cfg;
+    if (design) *design = s.des;
+    if (samples_consumed) *samples_consumed = s.cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_afc_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->afc.cur.restart();
+    return SDRG_OK;
+}
+
+// out_bytes is the rows' when the stage tracks, and 0 when it measures: it writes no rows then
+static int32_t afc_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_afc_record *records, StageCall *c) {
+    const int32_t rc = block_resolve(e, e->afc, "afc", sizeof(*records), in_stride, n, records, c);
+    if (!rc && !e->afc.track()) c->out_bytes = 0;
+    return rc;
+}
+
+static int32_t afc_reserve(sdrg_engine *e, const StageCall &) {
+    AfcStage &s = e->afc;
+    int32_t rc = ensure_halves(&s.state, s.half(e->n_streams));
+    if (!rc) rc = ensure_device(&s.blk, (size_t)e->n_streams * (s.blocks() * 3 + (s.blocks() + 1) * 2));
+    if (!rc && s.track()) rc = ensure_nco_table(e);
+    return rc;
+}
+
+// One call on the main stream: chan and out (rows of in_stride complex samples; out may be chan, and is null when the
+// stage measures) and c.aux, the records or null, in device memory.
+static int32_t afc_launch(sdrg_engine *e, const StageCall &c, const void *chan, void *out) {
+    AfcStage &s = e->afc;
+    const size_t half = s.half(e->n_streams);
+    AfcParams p{};
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.block = s.cfg.block;
+    p.track = s.track() ? 1 : 0;
+    p.off = s.cur.offset(s.cfg.block);
+    p.n_blocks = c.n_out;
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.beta = s.des.beta, p.floor_thr = s.des.floor_thr, p.lock_thr = s.des.lock_thr, p.max_s = s.des.max_s;
+    p.K = s.des.K, p.hz_per_inc = s.des.hz_per_inc, p.rad_per_inc = s.des.rad_per_inc;
+    p.nco_tab = e->d_nco_tab.p;
+    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    p.state_new = s.state.next(s.cur, half);
+    p.mom = s.blk.p;
+    p.blk = reinterpret_cast<uint32_t *>(s.blk.p + (size_t)e->n_streams * s.blocks() * 3);
+    p.records = static_cast<sdrg_afc_record *>(c.aux);
+    HIP_TRY(launch_afc(static_cast<const float *>(chan), e->n_streams, p, static_cast<float *>(out), e->s_main));
+    s.cur.advance(c.n);  // a call without samples wrote out and the records only: the state stays where it is
+    e->outputs_unmarked = true;
+    return SDRG_OK;
+}
+
+// stage_call for a stage whose `out` is null in one of its modes
+static int32_t afc_call(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
+                        sdrg_afc_record *records, int32_t *n_blocks, bool host) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!chan || !n_blocks) return fail(SDRG_E_INVALID, "null chan or n_blocks");
+    StageCall c;
+    int32_t rc = afc_resolve(e, in_stride, n, records, &c);
+    if (rc) return rc;
+    const bool track = e->afc.track();
+    if (track && !out) return fail(SDRG_E_INVALID, "afc: null out in SDRG_AFC_TRACK mode");
+    if (!track && out) return fail(SDRG_E_INVALID, "afc: out must be NULL in SDRG_AFC_MEASURE mode");
+    DeviceScope dscope(e->device);
+    HIP_TRY(dscope.error());
+    rc = afc_reserve(e, c);
+    if (!rc && host) {
+        const HostAux aux(c.out_bytes, &c);
+        rc = host_begin(e, chan, c.in_bytes, aux.staged_bytes());
+        if (!rc) aux.stage(e);
+        if (!rc) rc = afc_launch(e, c, e->stream_in.p, track ? e->stream_out.p : nullptr);
+        if (!rc) rc = aux.finish(e, out, c.out_bytes);
+    } else if (!rc) {
+        rc = afc_launch(e, c, chan, out);
+    }
+    if (rc) return rc;
+    *n_blocks = c.n_out;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_afc_device(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
+                               sdrg_afc_record *records, int32_t *n_blocks) {
+    return afc_call(e, chan, in_stride, n, out, records, n_blocks, false);
+}
+
+int32_t sdrg_engine_afc_host(sdrg_engine *e, const void *chan, int32_t in_stride, int32_t n, void *out,
+                             sdrg_afc_record *records, int32_t *n_blocks) {
+    return afc_call(e, chan, in_stride, n, out, records, n_blocks, true);
 }
 
 // ---- noise blanker stage (blanker.hip) -----------------------------------------------------------------------------
@@ -3549,7 +3691,7 @@ int32_t sdrg_engine_tones_host(sdrg_engine *e, const void *in, int32_t in_stride
     return tones_stage(e, "in", in, powers, n_blocks, true, in_stride, n, records);
 }
 
-// ---- the chains: DDC (-> squelch) (-> AGC) -> demodulator or sideband (-> resampler), host memory in and out --------
+// ---- the chains: DDC (-> AFC) (-> squelch) (-> AGC) -> demodulator or sideband (-> resampler), host memory in and out
 
 // The stage that turns the channel into audio.  What a chain asks of it, whichever it is: whether it is set, its
 // max_in and cap, whether it writes floats, how many components an output has, and its three steps.
@@ -3589,9 +3731,16 @@ struct ToneTap {
     int32_t *n_blocks;
 };
 
+// With `afc` (listen_afc_host) the AFC runs first on that channel, in place, and its records are staged behind the
+// squelch's and the AGC's.
+struct AfcStep {
+    sdrg_afc_record *records;
+};
+
 static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const void *iq, int32_t fmt, void *out,
                           int32_t *n_out, sdrg_squelch_record *sq_records = nullptr,
-                          sdrg_agc_record *agc_records = nullptr, const ToneTap *tap = nullptr) {
+                          sdrg_agc_record *agc_records = nullptr, const ToneTap *tap = nullptr,
+                          const AfcStep *afc = nullptr) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
     if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
     if (tap && (!tap->powers || !tap->n_blocks)) return fail(SDRG_E_INVALID, "null powers or n_blocks");
@@ -3604,8 +3753,12 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     if (!rc && squelch) rc = require_set(e->sq.set, "squelch");
     if (!rc && agc) rc = require_set(e->agc.set, "agc");
     if (!rc && tap) rc = require_set(e->tones.set, "tones");
+    if (!rc && afc) rc = require_set(e->afc.set, "afc");
+    if (!rc && afc && !e->afc.track())
+        rc = fail(SDRG_E_INVALID, "the chain corrects the channel: afc mode must be SDRG_AFC_TRACK");
     DdcCall d;
-    StageCall q, g, a, r, t;  // the squelch's, the AGC's, the detector's, the resampler's and the tone stage's
+    // the squelch's, the AGC's, the detector's, the resampler's, the tone stage's and the AFC's
+    StageCall q, g, a, r, t, f;
     if (!rc) rc = ddc_resolve(e, fmt, &d);
     if (rc) return rc;
     // the checks between the stages come before the later stages' own: after them those cannot refuse their n
@@ -3615,6 +3768,8 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
         return fail(SDRG_E_INVALID, "squelch max_in %d smaller than the ddc's row length %d", e->sq.cfg.max_in, d.cap);
     if (agc && e->agc.cfg.max_in < d.cap)
         return fail(SDRG_E_INVALID, "agc max_in %d smaller than the ddc's row length %d", e->agc.cfg.max_in, d.cap);
+    if (afc && e->afc.cfg.max_in < d.cap)
+        return fail(SDRG_E_INVALID, "afc max_in %d smaller than the ddc's row length %d", e->afc.cfg.max_in, d.cap);
     if (resample) {
         if (!v.f32)
             return fail(SDRG_E_INVALID, "the resampler reads float audio: %s out_format must be %s", v.name, v.f32_name);
@@ -3641,6 +3796,7 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     if (!rc && resample) rc = rs_resolve(e, a.cap, a.n_out, &r);
     if (!rc && squelch) rc = sq_resolve(e, d.cap, d.n_out, sq_records, &q);
     if (!rc && agc) rc = agc_resolve(e, d.cap, d.n_out, agc_records, &g);
+    if (!rc && afc) rc = afc_resolve(e, d.cap, d.n_out, afc->records, &f);
     if (rc) return rc;
     const StageCall &last = resample ? r : a;
     // a stage that is not in the mask was not resolved: its aux is null, and nothing is staged or copied for it
@@ -3648,10 +3804,12 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     void *powers = tap ? tap->powers : nullptr;  // the caller's, then where the launch writes them
     if (tap) aux.add(&powers, t.out_bytes);
     if (tap) aux.add(&t.aux, t.aux_bytes);
+    if (afc) aux.add(&f.aux, f.aux_bytes);
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     rc = ddc_reserve(e, d);
     if (!rc && tap) rc = tones_reserve(e, t);
+    if (!rc && afc) rc = afc_reserve(e, f);
     if (!rc && squelch) rc = sq_reserve(e, q);
     if (!rc && agc) rc = agc_reserve(e, g);
     if (!rc) rc = v.reserve(e, a);
@@ -3661,6 +3819,7 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     if (!rc) rc = host_begin(e, iq, d.in_bytes, aux.staged_bytes());
     if (!rc) aux.stage(e);
     if (!rc) rc = ddc_launch(e, d, e->stream_in.p, e->chain_chan.p);
+    if (!rc && afc) rc = afc_launch(e, f, e->chain_chan.p, e->chain_chan.p);
     if (!rc && squelch) rc = sq_launch(e, q, e->chain_chan.p, e->chain_chan.p);
     if (!rc && agc) rc = agc_launch(e, g, e->chain_chan.p, e->chain_chan.p);
     void *audio = resample ? (void *)e->chain_audio.p : (void *)e->stream_out.p;
@@ -3677,6 +3836,13 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
 int32_t sdrg_engine_listen_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
                                 sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records) {
     return chain_host(e, Detector::Demod, steps, iq, fmt, out, n_out, squelch_records, agc_records);
+}
+
+int32_t sdrg_engine_listen_afc_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,
+                                    sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records,
+                                    sdrg_afc_record *afc_records) {
+    const AfcStep afc{afc_records};
+    return chain_host(e, Detector::Demod, steps, iq, fmt, out, n_out, squelch_records, agc_records, nullptr, &afc);
 }
 
 int32_t sdrg_engine_listen_tones_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out, int32_t *n_out,

@@ -324,6 +324,32 @@ static_assert(SDRG_IQCORR_MAX_BLOCK == BLOCK_MAX && SDRG_IQCORR_MAX_IN == BLOCK_
               "the block stages' positions and butterfly: a block is at least a wave's 32 pairs");
 hipError_t launch_iqcorr(const void *iq, int fmt, int n_streams, IqcorrParams p, float *out, hipStream_t stream);
 
+// AFC stage (afc.hip): per stream the n complex samples at chan + stream * in_stride (float2) are the positions
+// [off, off + n) of a run of blocks of `block` samples, as the block stages' are.  state_old / state_new [n_streams]
+// [2 block + AFC_STATE_HEAD] floats: {A, B, P, coh, inc (int bits), Phi of the block in progress (uint bits), flags
+// (locked | seeded << 1, int bits), 0}, then the samples so far of the block in progress; fresh: state_old is not read
+// (zeros, and off is 0).  mom [blocks][3][n_streams] floats and blk [blocks + 1][2][n_streams] words are scratch: the
+// completed blocks' Rr, Ri and W, and (Phi, inc) as uint bits for the call's block j (the block in progress when the
+// call began is block 0): the phase at its first sample and the increment it is mixed by.  With track, writes out
+// [n_streams][in_stride][2] whole (zeros from n on; out may be chan); without, out is not touched.  If n > 0, state_new;
+// records [n_streams] unless nullptr.  n_streams, log2_block, tile and inv_block are the launcher's.
+struct AfcParams {
+    int n, in_stride, block, track, off, n_blocks, fresh;
+    float beta, floor_thr, lock_thr, max_s, K, hz_per_inc, rad_per_inc;
+    const float *nco_tab;  // nco_tables() on the device
+    const float *state_old;
+    float *state_new;
+    float *mom;
+    uint32_t *blk;
+    sdrg_afc_record *records;
+    int n_streams, log2_block, tile;
+    float inv_block;
+};
+constexpr int AFC_STATE_HEAD = 8;
+static_assert(SDRG_AFC_MIN_BLOCK == BLOCK_MIN && SDRG_AFC_MAX_BLOCK == BLOCK_MAX && SDRG_AFC_MAX_IN == BLOCK_MAX_IN,
+              "the block stages' positions and butterfly");
+hipError_t launch_afc(const float *chan, int n_streams, AfcParams p, float *out, hipStream_t stream);
+
 // Noise blanker stage (blanker.hip): per stream the n raw samples at iq + stream * in_stride (in fmt) are the positions
 // [off, off + n) of a run of blocks of `block` samples, as the block stages' are.  state_old / state_new [n_streams]
 // [blanker_state_words(block)] floats: {L, seeded (int bits), the threshold in force for the block in progress, 0}, the

@@ -159,6 +159,8 @@ EXPORTS = [
     "sdrg_tones_design", "sdrg_tones_geometry", "sdrg_engine_set_tones", "sdrg_engine_get_tones",
     "sdrg_engine_tones_reset", "sdrg_engine_tones_max_blocks", "sdrg_engine_tones_device", "sdrg_engine_tones_host",
     "sdrg_engine_listen_tones_host",
+    "sdrg_afc_design", "sdrg_afc_geometry", "sdrg_afc_offset_hz", "sdrg_engine_set_afc", "sdrg_engine_get_afc",
+    "sdrg_engine_afc_reset", "sdrg_engine_afc_device", "sdrg_engine_afc_host", "sdrg_engine_listen_afc_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -270,6 +272,27 @@ class IqcorrConfig(ctypes.Structure):
 IqcorrRecord = np.dtype([("dc_re", "<f4"), ("dc_im", "<f4"), ("w_re", "<f4"), ("w_im", "<f4"), ("power", "<f4"),
                          ("image_db", "<f4"), ("held_blocks", "<i4"), ("seeded", "<i4")])
 IQCORR_DC, IQCORR_BALANCE = 1, 2
+
+
+class AfcConfig(ctypes.Structure):
+    """sdrg_afc_config: the AFC stage's channel rate, clamp, time constant, floor, lock threshold, mode, block length and
+    row length (include/sdrg.h)."""
+    _fields_ = [("channel_rate", ctypes.c_double), ("max_offset_hz", ctypes.c_double), ("tau_blocks", ctypes.c_double),
+                ("floor_db", ctypes.c_double), ("lock_threshold", ctypes.c_double), ("mode", ctypes.c_int32),
+                ("block", ctypes.c_int32), ("max_in", ctypes.c_int32)]
+
+
+class AfcDesign(ctypes.Structure):
+    """sdrg_afc_design_values: the seven values of the AFC stage's design."""
+    _fields_ = [(k, ctypes.c_float) for k in ("beta", "floor_thr", "lock_thr", "max_s", "K", "hz_per_inc",
+                                              "rad_per_inc")]
+
+
+# sdrg_afc_record
+AfcRecord = np.dtype([("offset_hz", "<f4"), ("step", "<f4"), ("inc", "<i4"), ("coherence", "<f4"), ("level", "<f4"),
+                      ("level_db", "<f4"), ("held_blocks", "<i4"), ("flags", "<i4")])
+AFC_TRACK, AFC_MEASURE = 1, 2
+AFC_LOCKED, AFC_SEEDED = 1, 2  # sdrg_afc_record.flags
 
 
 class BlankerConfig(ctypes.Structure):
@@ -623,6 +646,16 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_tones_host": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_listen_tones_host": (_I32, [P, _I32, P, _I32, P, ctypes.POINTER(_I32), P, P, P, P,
                                                  ctypes.POINTER(_I32)]),
+        "sdrg_afc_design": (_I32, [ctypes.POINTER(AfcConfig), ctypes.POINTER(AfcDesign)]),
+        "sdrg_afc_geometry": (_I32, [_I32, ctypes.POINTER(_I32)]),
+        "sdrg_afc_offset_hz": (ctypes.c_double, [_I32, ctypes.c_double]),
+        "sdrg_engine_set_afc": (_I32, [P, ctypes.POINTER(AfcConfig)]),
+        "sdrg_engine_get_afc": (_I32, [P, ctypes.POINTER(AfcConfig), ctypes.POINTER(AfcDesign),
+                                       ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_afc_reset": (_I32, [P]),
+        "sdrg_engine_afc_device": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_afc_host": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_listen_afc_host": (_I32, [P, _I32, P, _I32, P, ctypes.POINTER(_I32), P, P, P]),
         "sdrg_engine_set_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig)]),
         "sdrg_engine_get_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
                                            ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_uint64)]),
@@ -933,6 +966,31 @@ def iqcorr_geometry(block: int) -> int:
     t = _I32()
     _check(load().sdrg_iqcorr_geometry(block, ctypes.byref(t)), "iqcorr_geometry")
     return t.value
+
+
+def _afc_design_dict(d: AfcDesign) -> dict:
+    return {k: np.float32(getattr(d, k)) for k, _ in AfcDesign._fields_}
+
+
+def afc_design(**fields) -> dict:
+    """The AFC stage's design for a configuration (host-side, no device): beta, floor_thr, lock_thr, max_s, K,
+    hz_per_inc and rad_per_inc as np.float32.  The fields are sdrg_afc_config's (fields left out are 0)."""
+    c, d = _filled(AfcConfig, "afc", fields), AfcDesign()
+    _check(load().sdrg_afc_design(ctypes.byref(c), ctypes.byref(d)), "afc_design")
+    return _afc_design_dict(d)
+
+
+def afc_geometry(block: int) -> int:
+    """tile: consecutive samples a workgroup of the AFC's moments kernel takes (by position in the run of blocks); a
+    workgroup of its pass kernel takes four such tiles of the call's indices one after the other."""
+    t = _I32()
+    _check(load().sdrg_afc_geometry(block, ctypes.byref(t)), "afc_geometry")
+    return t.value
+
+
+def afc_offset_hz(inc: int, channel_rate: float) -> float:
+    """A record's inc in Hz, in double: inc * channel_rate / 2^32 (NaN unless channel_rate is finite and positive)."""
+    return float(load().sdrg_afc_offset_hz(int(inc), float(channel_rate)))
 
 
 def blanker_design(**fields) -> dict:
@@ -1624,6 +1682,54 @@ class Engine:
                                                       _ptr(pcm) if plen > 0 else None, now_ms, _ptr(iq_rec)),
                "iqcorr_process_host")
         return spec, recs, pcm, iq_rec
+
+    # ---- AFC stage --------------------------------------------------------------------------------
+    def set_afc(self, **fields) -> None:
+        """sdrg_engine_set_afc: channel_rate, max_offset_hz, tau_blocks, floor_db, lock_threshold, mode, block, max_in
+        (fields left out are 0); set_afc(off=True) switches the stage off."""
+        self._set_stage(AfcConfig, "afc", fields)
+
+    def afc_config(self) -> dict:
+        """The configuration in force, plus its design (afc_design's seven values as np.float32) and
+        samples_consumed."""
+        c, d, g = AfcConfig(), AfcDesign(), ctypes.c_uint64()
+        _check(load().sdrg_engine_get_afc(self._h, ctypes.byref(c), ctypes.byref(d), ctypes.byref(g)), "get_afc")
+        return dict(_as_dict(c), **_afc_design_dict(d), samples_consumed=g.value)
+
+    def afc_reset(self) -> None:
+        _check(load().sdrg_engine_afc_reset(self._h), "afc_reset")
+
+    def afc_device(self, chan_ptr: int, in_stride: int, n: int, out_ptr: int | None,
+                   records_ptr: int | None = None) -> int:
+        """Device path: chan [n_streams][in_stride] complex64 in (the first n of every row are the call's), the
+        corrected rows of the same shape out (out_ptr may be chan_ptr; None in AFC_MEASURE mode, which writes no rows)
+        and, unless records_ptr is None, [n_streams] AfcRecord; asynchronous on the main stream.  Returns n_blocks."""
+        return self._i32_call(load().sdrg_engine_afc_device, "afc_device", chan_ptr, in_stride, n, out_ptr, records_ptr)
+
+    def afc_host(self, chan: np.ndarray, want_records: bool = True):
+        """Host path: chan is complex64 [n_streams][n], n <= max_in.  Returns (the corrected complex64 [n_streams][n],
+        or None in AFC_MEASURE mode; the records [n_streams] AfcRecord or None; n_blocks)."""
+        chan = np.ascontiguousarray(chan, np.complex64).reshape(self.n_streams, -1)
+        n = chan.shape[1]
+        rows = chan if n else np.zeros((self.n_streams, 1), np.complex64)  # a call without samples still wants rows
+        out = np.empty_like(rows) if self.afc_config()["mode"] == AFC_TRACK else None
+        rec = np.empty(self.n_streams, AfcRecord) if want_records else None
+        n_blocks = self._i32_call(load().sdrg_engine_afc_host, "afc_host", _ptr(rows), rows.shape[1], n, _ptr(out),
+                                  _ptr(rec))
+        return None if out is None else out[:, :n], rec, n_blocks
+
+    def listen_afc(self, iq: np.ndarray, fmt: int = CS8, steps: int = 0):
+        """sdrg_engine_listen_afc_host: listen() with the AFC first on the channel, DDC -> AFC -> [squelch] -> [AGC] ->
+        demodulator -> [resampler].  Returns (the audio [n_streams][n_out], the squelch's records or None, the AGC's
+        records or None, the AFC's records [n_streams] AfcRecord)."""
+        iq, n_out = self._iq(iq, fmt), _I32()
+        out = self._resample_out() if steps & LISTEN_RESAMPLE else self._demod_out()
+        sq_rec = np.empty(self.n_streams, SquelchRecord) if steps & LISTEN_SQUELCH else None
+        agc_rec = np.empty(self.n_streams, AGC_RECORD_DTYPE) if steps & LISTEN_AGC else None
+        afc_rec = np.empty(self.n_streams, AfcRecord)
+        _check(load().sdrg_engine_listen_afc_host(self._h, steps, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out),
+                                                  _ptr(sq_rec), _ptr(agc_rec), _ptr(afc_rec)), "listen_afc_host")
+        return out[..., :n_out.value], sq_rec, agc_rec, afc_rec
 
     # ---- noise blanker stage ----------------------------------------------------------------------
     def set_blanker(self, **fields) -> None:
