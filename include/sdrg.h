@@ -307,6 +307,23 @@ const char *sdrg_last_error(void);      /* thread-local message for the last fai
  * (ssb_demod_opt.cpp:121-143, :273). */
 int32_t sdrg_ssb_pcm_len(int32_t n, int64_t sample_rate);
 
+/* How the SSB launcher lays out a frame of n samples at sample_rate with fir_taps (0 = the reference's 255, else odd
+ * in [3, 255], as sdrg_engine_set_ssb_variant takes it); answered by the launcher's own predicate, so tests that want
+ * every layout cannot drift from it.  Host-only, launches nothing.
+ *   decimation         max(1, int(fs / 48000.0f))
+ *   taps               the FIR length actually used (fir_taps or 255, or n|1 when the frame is shorter)
+ *   pcm_len            PCM samples per call, as sdrg_engine_pcm_len reports under that variant
+ *   pipeline           1: the pipeline kernel; 0: the lane-per-stream kernels (the pipeline does not hold the shape)
+ *   slots              FIR accumulators per stream in the pipeline kernel: (chunk + taps - 2) / decimation + 1 rounded
+ *                      up to 4, 8, 16 or 32 (4 when pcm_len is 0); 0 when pipeline is 0
+ *   chunk              samples per pipeline chunk
+ *   chunk_outputs      FIR outputs one chunk can complete, ceil(chunk / decimation)
+ *   max_chunk_outputs  the most the pipeline kernel holds; a larger chunk_outputs selects the lane-per-stream kernels */
+typedef struct sdrg_ssb_layout_info {
+    int32_t decimation, taps, pcm_len, pipeline, slots, chunk, chunk_outputs, max_chunk_outputs;
+} sdrg_ssb_layout_info;
+int32_t sdrg_ssb_layout(int64_t sample_rate, int32_t n, int32_t fir_taps, sdrg_ssb_layout_info *out);
+
 /* The focus window of evaluateSignalStrength (fft_process.cpp:124-140) in the fftshifted spectrum the engine
  * writes: bins [*first_bin, *first_bin + *n_bins) hold offsets -focus_khz .. +focus_khz kHz around the
  * centre.  *n_bins = 0 when the window is empty (focus wider than the band, :218-247).  Host-only; used to

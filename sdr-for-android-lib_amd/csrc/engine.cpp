@@ -1399,6 +1399,29 @@ int32_t sdrg_ssb_pcm_len(int32_t n, int64_t sample_rate) {
     return ssb_pcm_len(n, (uint32_t)sample_rate);
 }
 
+int32_t sdrg_ssb_layout(int64_t sample_rate, int32_t n, int32_t fir_taps, sdrg_ssb_layout_info *out) {
+    if (!out) return fail(SDRG_E_INVALID, "null output");
+    if (n <= 0 || sample_rate <= 0 || sample_rate > 0xFFFFFFFFll) return fail(SDRG_E_INVALID, "bad n/sample_rate");
+    if (fir_taps != 0 && (fir_taps < 3 || fir_taps > 255 || (fir_taps & 1) == 0))
+        return fail(SDRG_E_INVALID, "fir_taps must be 0 or odd in [3, 255], got %d", fir_taps);
+    SsbParams p{};  // the fields ssb_pipe_supported reads, filled as prepare_ssb fills them
+    p.samp_count = n;
+    p.decim = ssb_decim((uint32_t)sample_rate);
+    p.n_taps = ssb_taps_for(n, fir_taps);
+    p.pcm_len = ssb_pcm_len(n, (uint32_t)sample_rate, fir_taps);
+    int nsl_mask = 0;
+    const bool pipe = ssb_pipe_supported(p, &nsl_mask);
+    out->decimation = p.decim;
+    out->taps = p.n_taps;
+    out->pcm_len = p.pcm_len;
+    out->pipeline = pipe ? 1 : 0;
+    out->slots = pipe ? nsl_mask + 1 : 0;
+    out->chunk = ssb_pipe_chunk();
+    out->chunk_outputs = ssb_pipe_chunk_outputs(p.decim);
+    out->max_chunk_outputs = ssb_pipe_max_chunk_outputs();
+    return SDRG_OK;
+}
+
 int32_t sdrg_host_alloc(size_t bytes, void **out) {
     if (!out) return fail(SDRG_E_INVALID, "null out");
     *out = nullptr;

@@ -94,6 +94,11 @@ void ssb_report_stamps();  // diagnostic (SDRG_PIPE_STAMPS=1)
 // chunk_table: per chunk of ssb_pipe_chunk() samples {first, last output overlapping it, first, last output
 // completed in it} (host-computed, see engine.cpp); may be null (reference kernels).
 int ssb_pipe_chunk(void);
+// The launcher's choice for p (samp_count, decim, n_taps, pcm_len): true = the pipeline kernel with
+// *nsl_mask + 1 FIR slots per stream, false = the lane-per-stream kernels.  Host-only (sdrg_ssb_layout asks it too).
+bool ssb_pipe_supported(const SsbParams &p, int *nsl_mask);
+int ssb_pipe_chunk_outputs(int decim);  // FIR outputs one chunk can complete
+int ssb_pipe_max_chunk_outputs(void);   // the most the pipeline kernel holds
 // audio (nullable): run the audio pulse detector's front end on the PCM as it is produced
 // stop: an event the pipeline kernel may complete itself (*stop_recorded = true); otherwise the caller records it
 hipError_t launch_ssb(const void *iq, int fmt, int n_frames, const SsbParams &p, const float *taps,

@@ -1036,10 +1036,12 @@ bool ssb_pipe_supported(const SsbParams &p, int *nsl_mask) {
     int nsl = 4;
     while (nsl < ns) nsl *= 2;
     *nsl_mask = nsl - 1;
-    return nsl <= MAX_SLOTS && (CH + p.decim - 1) / p.decim <= MAX_DONE && p.n_taps <= 256;
+    return nsl <= MAX_SLOTS && ssb_pipe_chunk_outputs(p.decim) <= MAX_DONE && p.n_taps <= 256;
 }
 
 int ssb_pipe_chunk(void) { return CH; }
+int ssb_pipe_chunk_outputs(int decim) { return (CH + decim - 1) / decim; }
+int ssb_pipe_max_chunk_outputs(void) { return MAX_DONE; }
 
 // The pipeline kernel goes out through hipExtLaunchKernel with `stop` as its stop event (the event completes with the
 // kernel's own dispatch), so the caller records no marker packet between two SSB kernels on the SSB stream, the

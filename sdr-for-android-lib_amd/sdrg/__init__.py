@@ -100,7 +100,7 @@ PEAKS_SUMMARY_DTYPE = np.dtype([("count", "<i4"), ("n_above", "<i4"), ("floor_po
 
 # Every entry point include/sdrg.h declares (checked by tests/test_abi.py).
 EXPORTS = [
-    "sdrg_abi_version", "sdrg_last_error", "sdrg_ssb_pcm_len", "sdrg_focus_window", "sdrg_host_alloc", "sdrg_host_free", "sdrg_ssb_design", "sdrg_engine_create", "sdrg_engine_destroy",
+    "sdrg_abi_version", "sdrg_last_error", "sdrg_ssb_pcm_len", "sdrg_ssb_layout", "sdrg_focus_window", "sdrg_host_alloc", "sdrg_host_free", "sdrg_ssb_design", "sdrg_engine_create", "sdrg_engine_destroy",
     "sdrg_engine_apply_config", "sdrg_engine_set_frequency", "sdrg_engine_set_frequency_focus_range",
     "sdrg_engine_set_sound_mode", "sdrg_engine_set_sample_rate", "sdrg_engine_set_samples_per_reading",
     "sdrg_engine_input_released", "sdrg_engine_wait_input_released", "sdrg_engine_wait_outputs", "sdrg_engine_set_upper_sideband", "sdrg_engine_get_config", "sdrg_engine_n_streams", "sdrg_engine_pcm_len",
@@ -216,6 +216,12 @@ class PeaksConfig(ctypes.Structure):
     """sdrg_peaks_config: the peak table stage's span, table size, spacing and threshold (include/sdrg.h)."""
     _fields_ = [("span", ctypes.c_int32), ("first_bin", ctypes.c_int32), ("n_bins", ctypes.c_int32),
                 ("max_peaks", ctypes.c_int32), ("min_separation", ctypes.c_int32), ("threshold_db", ctypes.c_float)]
+
+
+class SsbLayout(ctypes.Structure):
+    """sdrg_ssb_layout_info: what the SSB launcher does with (sample_rate, n, fir_taps) (include/sdrg.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("decimation", "taps", "pcm_len", "pipeline", "slots", "chunk",
+                                              "chunk_outputs", "max_chunk_outputs")]
 
 
 class DdcConfig(ctypes.Structure):
@@ -468,6 +474,7 @@ def load() -> ctypes.CDLL:
         "sdrg_abi_version": (_I32, []),
         "sdrg_last_error": (ctypes.c_char_p, []),
         "sdrg_ssb_pcm_len": (_I32, [_I32, _I64]),
+        "sdrg_ssb_layout": (_I32, [_I64, _I32, _I32, ctypes.POINTER(SsbLayout)]),
         "sdrg_ssb_design": (_I32, [_I32, _I64, _I32, P, P, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_create": (_I32, [ctypes.POINTER(_Config), _I32, _I32, ctypes.POINTER(P)]),
         "sdrg_engine_destroy": (_I32, [P]),
@@ -699,6 +706,17 @@ def _check(rc: int, what: str) -> None:
 
 def ssb_pcm_len(n: int, sample_rate: int) -> int:
     return int(load().sdrg_ssb_pcm_len(n, sample_rate))
+
+
+def ssb_layout(sample_rate: int, n: int, fir_taps: int = 0) -> dict:
+    """The SSB launcher's layout for a frame of n samples at sample_rate with fir_taps (0: 255), host-side, no device:
+    decimation, taps, pcm_len, pipeline (False: the lane-per-stream kernels), slots (4, 8, 16 or 32; 0 without the
+    pipeline), chunk, chunk_outputs and max_chunk_outputs."""
+    o = SsbLayout()
+    _check(load().sdrg_ssb_layout(sample_rate, n, fir_taps, ctypes.byref(o)), "ssb_layout")
+    d = {k: int(getattr(o, k)) for k, _ in SsbLayout._fields_}
+    d["pipeline"] = bool(d["pipeline"])
+    return d
 
 
 class HostBuffer:

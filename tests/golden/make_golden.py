@@ -12,7 +12,8 @@ Window geometry is the table SURVEY.md section 8 measured on the reference build
 
 Inputs are stored as raw bytes (never regenerated from cos/sin on another machine).
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py          every fixture
+    python tests/golden/make_golden.py ssb      only the SSB layout fixtures (golden_ssb_*.npz), the others untouched
 """
 from __future__ import annotations
 
@@ -25,7 +26,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle as O  # noqa: E402
+import ssb_cases as C  # noqa: E402
 
 
 def np_unpack(fmt: int, raw: np.ndarray) -> np.ndarray:
@@ -66,10 +69,57 @@ def make_case(name: str, fmt: int, n: int, fs: int, stream_modes, tones, spectra
     print(name, raw.shape, raw.dtype, "pcm", pcm.shape)
 
 
+def make_ssb_case(name: str, fmt_name: str, n: int, fs: int, stream_modes, uppers, families, seed: int = 0x60D):
+    """A fixture from the input families of tests/ssb_cases.py (stream s runs families[s], 1-based) at a sample rate
+    whose FIR layout or kernel family the 2 to 2.5 MHz fixtures do not reach; uppers[s] = 0 is a lower-sideband
+    stream.  Expected PCM from the reference build, one fresh process per stream."""
+    fmt = getattr(O, fmt_name)
+    S, F = len(stream_modes), len(stream_modes[0])
+    raw = np.stack([np.stack([C.FAMILIES[families[s] - 1](fmt_name, s, f, n, fs, seed) for f in range(F)])
+                    for s in range(S)])
+    pcm_len = O.ssb_pcm_len(n, fs)
+    pcm = np.zeros((S, F, pcm_len), dtype=np.int16)
+    for s in range(S):
+        frames = np.stack([np_unpack(fmt, raw[s, f]).reshape(n, 2) for f in range(F)])
+        outs = O.ref_ssb_run(frames, fs, stream_modes[s], upper=bool(uppers[s]))
+        for f in range(F):
+            assert outs[f].size == pcm_len, (outs[f].size, pcm_len)
+            pcm[s, f] = outs[f]
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), raw=raw, fmt=np.int32(fmt), n=np.int32(n), fs=np.int64(fs),
+                        modes=np.array(stream_modes, dtype=np.int32), upper=np.array(uppers, dtype=np.int32), pcm=pcm,
+                        families=np.array(families, dtype=np.int32))
+    print(name, raw.shape, raw.dtype, "pcm", pcm.shape, "nonzero", int(np.count_nonzero(pcm)),
+          "clamped", int((np.abs(pcm.astype(np.int32)) == 32767).sum()))
+
+
+def make_ssb_layout_fixtures() -> None:
+    """The lane-per-stream kernels' rate (250 kHz, D = 5), the 32-slot (480 kHz, D = 10), 16-slot (1.024 MHz, D = 21)
+    and 4-slot (10 MHz, D = 208) layouts; two streams, three frames, mixed sound modes, one stream lower sideband;
+    and one CF32 case of family 6 (magnitudes 2^-149 .. 2^100).  The names are tests/ssb_cases.py GOLDEN_SSB_CASES."""
+    make_ssb_case("golden_ssb_cs8_2048_fs250k", "CS8", 2048, 250_000, [[0, 1, 2], [1, 2, 0]], [1, 0], [2, 1])
+    make_ssb_case("golden_ssb_cu8_2005_fs480k", "CU8", 2005, 480_000, [[2, 2, 0], [1, 0, 2]], [0, 1], [5, 1])
+    make_ssb_case("golden_ssb_cs16_2048_fs1024k", "CS16", 2048, 1_024_000, [[1, 0, 2], [0, 0, 1]], [1, 0], [3, 4])
+    make_ssb_case("golden_ssb_cf32_2048_fs10m", "CF32", 2048, 10_000_000, [[0, 2, 1], [2, 1, 0]], [1, 0], [1, 2])
+    make_ssb_case("golden_ssb_cf32_range_2048_fs1024k", "CF32", 2048, 1_024_000, [[1, 2, 0], [0, 1, 2]], [1, 0],
+                  [6, 6])
+    # design coefficients of those rates from the reference build (bit patterns), in a file of their own
+    coefs = {}
+    for fs in (250_000, 480_000, 1_024_000, 10_000_000):
+        for (fc, q) in ((3200.0, 0.9), (2200.0, 1.2)):
+            coefs[f"lpf_{fs}_{int(fc)}"] = O.ref_coefs("lpf", float(fs), fc, q)
+    for (size, dec) in ((2048, 5), (2005, 10), (2048, 21), (2048, 208)):
+        coefs[f"taps_{size}_{dec}"] = O.ref_taps(size, dec)
+    np.savez_compressed(os.path.join(HERE, "golden_ssb_layout_design.npz"), **coefs)
+    print("layout design", sorted(coefs))
+
+
 def main() -> None:
     if not O.have_ref():
         O.build()
     assert O.have_ref(), "oracle/_ref/ref_ssb missing: needs /root/reference"
+    make_ssb_layout_fixtures()
+    if sys.argv[1:] == ["ssb"]:
+        return
 
     # C1/C2/C3 shape: CS8, N=16384, fs=2 MHz, 4 streams x 3 frames, mixed sound modes (mode 3 = unknown:
     # keeps the previous mode's globals, ssb_demod_opt.cpp:230-255)
