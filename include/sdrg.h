@@ -730,6 +730,82 @@ int32_t sdrg_engine_ddc_device(sdrg_engine *eng, const void *iq, int32_t fmt, vo
 int32_t sdrg_engine_ddc_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
 
 /* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the DDC bank stage.  Per stream s and channel c < C, the stream's raw IQ
+ * mixed down by offsets_hz[s][c], low-passed by one shared T-tap FIR and decimated by D, as CF32: C channels at their own
+ * frequencies from one wideband capture.  Row s C + c of out holds, in bytes, what the DDC stage writes for stream s when
+ * set to that offset with the same cutoff, D and T, so the whole out is the [n_streams C][cap][2] a second engine of
+ * n_streams C streams takes on the device (demod_device, squelch_device, afc_device, tones_device, process_device as
+ * CF32).  Opt-in and apart from the DDC: each has its own configuration and state.  All arithmetic is float unless
+ * stated; fs and N as for the DDC.
+ *   config     sdrg_bank_config and offsets_hz, n_streams * channels doubles, stream-major (offsets_hz[s * C + c]).
+ *              decimation D, taps T and cutoff_hz under the DDC's rules and limits (SDRG_DDC_MAX_*); every offset finite;
+ *              channels C in [1, SDRG_BANK_MAX_CHANNELS]; n_streams * C <= 65535.  A rejected set_bank leaves the
+ *              previous configuration, offsets and state in force; an accepted one, and sdrg_engine_bank_reset, restart
+ *              every stream: g0 = 0, history +0.
+ *   per call   inc_c = round(frac(offset_c / fs) * 2^32) mod 2^32 and the taps are resolved from the current fs; an fs
+ *              other than the previous bank call's restarts the streams first; cutoff_hz > fs / 2 fails the call with
+ *              SDRG_E_INVALID and commits nothing (no restart either).  A change of samples_per_reading restarts nothing.
+ *   taps       sdrg_ddc_design's formula with f = cutoff_hz / fs; the tables are sdrg_nco_tables.
+ *   unpack     the DDC's: CS8 (float)v * (1/128), CU8 ((float)v - 127.4f) * (1/128), CS16 (float)v * (1/32768), CF32 as
+ *              is.  x_s[g] is stream s's unpacked sample at the global index g (uint64), +0 for g < 0.
+ *   mix        v_c[g] = x_s[g] * hi[ph >> 22] * lo[(ph >> 12) & 1023] with ph = (uint32)(inc_c * g), and the offsets in
+ *              force at the call: H = hi[..], L = lo[..]; wr = H.re L.re - H.im L.im, wi = H.re L.im + H.im L.re;
+ *              vr = xr wr - xi wi, vi = xr wi + xi wr: the DDC's products and order, each rounded on its own.
+ *   filter     with g0 samples consumed before the call: for every m with g0 <= m D < g0 + N: acc = +0.0f, then for
+ *              k = 0 .. T - 1 in this order acc = acc + h[k] * v_c[m D - k], each component on its own (a rounded
+ *              multiply, then a rounded add).  n_out = ceil((g0 + N) / D) - ceil(g0 / D), the same for every row.
+ *   output     out [n_streams][C][cap][2] float, cap = ceil(N / D); every byte is written by every call, the entries from
+ *              n_out on of every row are +0.  *n_out is set on the host before the call returns.
+ *   state      per stream the last T - 1 unpacked, *unmixed* samples (float pairs, 8 (T - 1) bytes whatever C is, in
+ *              device memory), per engine g0, advanced by N once the call's launch has been issued: a failed call commits
+ *              nothing.  v_c[g] is a function of g and x_s[g] alone, so mixing the history again gives the DDC's bytes
+ *              (a +0 sample mixes to +-0, which moves no sum that starts at +0); the format may change between calls.
+ *   retune     sdrg_engine_bank_retune replaces all offsets and restarts nothing: from the next call on, every row is
+ *              what a bank set to the new offsets since the stream's start would write for the same raw samples (the
+ *              phase at sample g is inc g whatever came before), the T - 1 samples of history included.  The filter is
+ *              not flushed.  The phase of a channel is NOT continuous across a retune: the output steps from
+ *              e^{-j 2 pi inc_old g} to e^{-j 2 pi inc_new g} at the call's first sample.  A refused retune (null,
+ *              a non-finite offset, bank off) changes nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_BANK_MAX_CHANNELS 4096
+typedef struct sdrg_bank_config {
+    double cutoff_hz;
+    int32_t decimation;
+    int32_t taps;
+    int32_t channels;
+} sdrg_bank_config;
+
+/* Host-only: for a bank of `channels` channels on n_streams streams (the checks of set_bank on these four), how many
+ * consecutive outputs one workgroup computes (an output index that is a multiple of it starts a new tile) and how many
+ * consecutive channels of a stream it computes them for (a channel index that is a multiple of it starts a new group):
+ * for tests that want windows across tile seams and channel counts across group seams.  No output byte depends on
+ * either.  Either pointer may be NULL. */
+int32_t sdrg_bank_geometry(int32_t decimation, int32_t taps, int32_t channels, int32_t n_streams, int32_t *tile_outputs,
+                           int32_t *channels_per_group);
+/* Set (cfg != NULL, offsets_hz [n_streams * cfg->channels]) or switch off (cfg == NULL; offsets_hz is not read) the
+ * bank.  A bank call while it is off returns SDRG_E_INVALID and writes nothing. */
+int32_t sdrg_engine_set_bank(sdrg_engine *eng, const sdrg_bank_config *cfg, const double *offsets_hz);
+/* Replace all n_streams * channels offsets; see `retune` above. */
+int32_t sdrg_engine_bank_retune(sdrg_engine *eng, const double *offsets_hz);
+/* The configuration in force (SDRG_E_INVALID when off) and g0, the samples every stream has consumed since the last
+ * restart; either pointer may be NULL. */
+int32_t sdrg_engine_get_bank(const sdrg_engine *eng, sdrg_bank_config *cfg, uint64_t *samples_consumed);
+/* The offsets in force and their NCO increments at the current sample rate, n_streams * channels values each; either
+ * pointer may be NULL. */
+int32_t sdrg_engine_bank_offsets(const sdrg_engine *eng, double *offsets_hz, uint32_t *increments);
+int32_t sdrg_engine_bank_reset(sdrg_engine *eng);
+/* cap = ceil(N / D) for the current samples_per_reading: the row length of `out`, in complex samples. */
+int32_t sdrg_engine_bank_max_out(const sdrg_engine *eng, int32_t *cap);
+/* iq [n_streams][N] raw samples of format fmt (SDRG_IQ_*) and out [n_streams][C][cap][2] float in device memory.  Reads
+ * iq only and shares nothing with sdrg_engine_process_device or sdrg_engine_ddc_device.  Stream rules and waiting as
+ * sdrg_engine_ddc_device: runs on the main stream (the caller's after sdrg_engine_set_stream); complete after
+ * sdrg_engine_synchronize, or on a stream after sdrg_engine_wait_outputs.  A retune issued after the call does not
+ * disturb it. */
+int32_t sdrg_engine_bank_device(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
+/* Host buffers, synchronous. */
+int32_t sdrg_engine_bank_host(sdrg_engine *eng, const void *iq, int32_t fmt, void *out, int32_t *n_out);
+
+/* ------------------------------------------------------------------------------------------------
  * BUILD EXTENSION, not a reference interface: the demodulator stage.  Per stream, the n CF32 channel samples of a call
  * (the DDC's out, or any [n_streams][max_in][2] float rows in device memory) become audio at channel_rate / R: detector
  * (AM envelope or FM phase step), DC block, de-emphasis, a T2-tap real FIR decimating by R, gain, and int16 PCM or

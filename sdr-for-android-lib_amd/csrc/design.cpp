@@ -235,6 +235,23 @@ const char *ddc_check(uint32_t sample_rate, double offset_hz, double cutoff_hz, 
     return nullptr;
 }
 
+// The DDC bank's configuration rules (sdrg.h): the DDC's for the shared filter, the channel count and the row limit of
+// the launch; nullptr, or what is wrong
+const char *bank_check(uint32_t sample_rate, double cutoff_hz, int decimation, int taps, int channels, int n_streams) {
+    if (const char *bad = ddc_check(sample_rate, 0.0, cutoff_hz, decimation, taps)) return bad;
+    if (channels < 1 || channels > SDRG_BANK_MAX_CHANNELS) return "channels outside [1, 4096]";
+    if (n_streams < 1 || (int64_t)n_streams * channels > 65535) return "n_streams * channels above 65535";
+    return nullptr;
+}
+
+// and its offsets', count = n_streams * channels of them: every one finite
+const char *bank_offsets_check(const double *offsets_hz, size_t count) {
+    if (!offsets_hz) return "null offsets_hz";
+    for (size_t i = 0; i < count; i++)
+        if (!std::isfinite(offsets_hz[i])) return "every offset must be finite";
+    return nullptr;
+}
+
 // The DDC stage's low-pass (sdrg.h): a Hann-windowed sinc of `taps` (odd) coefficients with unit DC gain, in double
 void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h) {
     lowpass_design(cutoff_hz / (double)sample_rate, taps, h);

@@ -1,6 +1,7 @@
 // design.h — host-side filter design and window geometry (see design.cpp).
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "sdrg_types.h"
@@ -19,6 +20,10 @@ void nco_tables(float *tab);  // [2][1024][2] floats
 // DDC stage: the configuration rules (nullptr = valid) and the Hann-sinc low-pass of unit DC gain
 const char *ddc_check(uint32_t sample_rate, double offset_hz, double cutoff_hz, int decimation, int taps);
 void ddc_design(uint32_t sample_rate, double cutoff_hz, int taps, float *h);
+// DDC bank: the configuration rules (nullptr = valid), and the offsets' (count = n_streams * channels values), which a
+// retune checks alone
+const char *bank_check(uint32_t sample_rate, double cutoff_hz, int decimation, int taps, int channels, int n_streams);
+const char *bank_offsets_check(const double *offsets_hz, size_t count);
 // the same low-pass at the relative cutoff f = cutoff / rate (cycles per sample)
 void lowpass_design(double f, int taps, float *h);
 // the same with the DC gain `scale`: h[k] = (float)(scale v[k] / sum), one rounding

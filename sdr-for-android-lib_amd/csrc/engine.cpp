@@ -185,6 +185,32 @@ struct DdcStage {
     }
 };
 
+// DDC bank stage (sdrg_engine_set_bank / bank_retune / bank_device / bank_host; bank.hip)
+struct BankStage {
+    sdrg_bank_config cfg{};
+    bool set = false;
+    DecimCursor cur;
+    uint32_t fs = 0;              // the sample rate of the previous bank call (0: none since set_bank)
+    std::vector<double> offsets;  // [n_streams][channels], in force
+    DevicePingPong<float> hist;   // halves of [n_streams][taps - 1][2]: the unmixed samples before the next frame
+    // The increments [n_streams][channels] of `offsets` at inc_fs, in inc[inc_at] (inc_fs == 0: neither table holds
+    // them).  A retune or another fs fills the other table, so a launch already issued keeps reading its own; read[i]
+    // follows the last launch that read inc[i], and is waited for before inc[i] is filled again.
+    DeviceBuf<uint32_t> inc[2];
+    Event read[2];
+    bool read_marked[2] = {false, false};
+    int inc_at = 0;
+    uint32_t inc_fs = 0;
+    uint32_t taps_fs = 0;         // the sample rate taps was designed for (0: not designed)
+    DdcTaps taps{};
+    size_t rows(int B) const { return (size_t)B * (size_t)cfg.channels; }
+    size_t half(int B) const { return (size_t)B * (size_t)(cfg.taps - 1) * 2; }
+    void restart() {
+        cur.restart();
+        fs = 0;
+    }
+};
+
 // demodulator stage (sdrg_engine_set_demod / demod_device / demod_host / ddc_demod_host; demod.hip)
 struct DemodStage {
     sdrg_demod_config cfg{};
@@ -599,6 +625,7 @@ struct sdrg_engine {
     PeaksStage peaks;
     // the streaming stages (DdcStage ... AgcStage above)
     DdcStage ddc;
+    BankStage bank;
     DemodStage demod;
     ChanStage chan;
     ResampleStage rs;
@@ -734,7 +761,7 @@ int32_t ensure_nco_table(sdrg_engine *e) {
     return upload_floats(&e->d_nco_tab, tab, "NCO table");
 }
 
-// ---- the streaming stages: DDC, demodulator, channelizer, resampler, squelch, AGC, sideband, IQ correction, blanker,
+// ---- the streaming stages: DDC, DDC bank, demodulator, channelizer, resampler, squelch, AGC, sideband, IQ correction, blanker,
 // ---- tone detector, AFC --------------------------------------------------------------------------------------------
 //
 // A call of a stage goes through three steps.  x_resolve makes every refusal and touches nothing; what it finds goes
@@ -2962,6 +2989,154 @@ int32_t sdrg_engine_ddc_device(sdrg_engine *e, const void *iq, int32_t fmt, void
 
 int32_t sdrg_engine_ddc_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
     return ddc_stage(e, "iq", iq, out, n_out, true, fmt);
+}
+
+// ---- DDC bank stage (bank.hip) ------------------------------------------------------------------------------------
+
+int32_t sdrg_bank_geometry(int32_t decimation, int32_t taps, int32_t channels, int32_t n_streams, int32_t *tile_outputs,
+                           int32_t *channels_per_group) {
+    if (const char *bad = bank_check(2, 1.0, decimation, taps, channels, n_streams))
+        return fail(SDRG_E_INVALID, "bank: %s", bad);
+    if (tile_outputs) *tile_outputs = bank_tile_outputs(decimation, taps);
+    if (channels_per_group) *channels_per_group = bank_group(channels, n_streams);
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_set_bank(sdrg_engine *e, const sdrg_bank_config *cfg, const double *offsets_hz) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    BankStage &s = e->bank;
+    if (cfg) {
+        const char *bad = bank_check((uint32_t)e->cfg.sample_rate, cfg->cutoff_hz, cfg->decimation, cfg->taps,
+                                     cfg->channels, e->n_streams);
+        if (!bad) bad = bank_offsets_check(offsets_hz, (size_t)e->n_streams * (size_t)cfg->channels);
+        if (bad) return fail(SDRG_E_INVALID, "bank: %s", bad);
+        s.cfg = *cfg;
+        s.offsets.assign(offsets_hz, offsets_hz + s.rows(e->n_streams));
+    }
+    s.set = cfg != nullptr;
+    s.taps_fs = 0;
+    s.inc_fs = 0;
+    s.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_bank_retune(sdrg_engine *e, const double *offsets_hz) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    BankStage &s = e->bank;
+    if (int32_t rc = require_set(s.set, "bank")) return rc;
+    if (const char *bad = bank_offsets_check(offsets_hz, s.rows(e->n_streams)))
+        return fail(SDRG_E_INVALID, "bank: %s", bad);
+    s.offsets.assign(offsets_hz, offsets_hz + s.rows(e->n_streams));
+    s.inc_fs = 0;  // the next call fills the table no launch in flight reads
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_bank(const sdrg_engine *e, sdrg_bank_config *cfg, uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    if (!e->bank.set) return fail(SDRG_E_INVALID, "no bank configuration set");
+    if (cfg) *cfg = e->bank.cfg;
+    if (samples_consumed) *samples_consumed = e->bank.cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_bank_offsets(const sdrg_engine *e, double *offsets_hz, uint32_t *increments) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    const BankStage &s = e->bank;
+    if (!s.set) return fail(SDRG_E_INVALID, "no bank configuration set");
+    for (size_t i = 0; i < s.offsets.size(); i++) {
+        if (offsets_hz) offsets_hz[i] = s.offsets[i];
+        if (increments) increments[i] = nco_increment(s.offsets[i], (uint32_t)e->cfg.sample_rate);
+    }
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_bank_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->bank.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_bank_max_out(const sdrg_engine *e, int32_t *cap) {
+    if (!e || !cap) return fail(SDRG_E_INVALID, "null argument");
+    if (int32_t rc = require_set(e->bank.set, "bank")) return rc;
+    *cap = DecimCursor::cap(e->cfg.samples_per_reading, e->bank.cfg.decimation);
+    return SDRG_OK;
+}
+
+using BankCall = DdcCall;  // the format, the sample rate and the cursor the call starts from
+
+static int32_t bank_resolve(const sdrg_engine *e, int32_t fmt, BankCall *c) {
+    const BankStage &s = e->bank;
+    if (int32_t rc = require_set(s.set, "bank")) return rc;
+    if (bytes_per_sample(fmt) == 0) return fail(SDRG_E_INVALID, "unknown iq format %d", fmt);
+    c->fmt = fmt;
+    c->fs = (uint32_t)e->cfg.sample_rate;
+    if (s.cfg.cutoff_hz > (double)c->fs / 2.0)
+        return fail(SDRG_E_INVALID, "bank cutoff %g Hz above half the sample rate %u", s.cfg.cutoff_hz, c->fs);
+    c->cur = s.cur;
+    if (s.fs != 0 && s.fs != c->fs) c->cur.restart();
+    c->n = e->cfg.samples_per_reading;
+    c->cap = DecimCursor::cap(c->n, s.cfg.decimation);
+    c->n_out = c->cur.n_out(c->n, s.cfg.decimation);
+    c->in_bytes = (size_t)e->n_streams * (size_t)c->n * (size_t)bytes_per_sample(fmt);
+    c->out_bytes = s.rows(e->n_streams) * (size_t)c->cap * 2 * sizeof(float);
+    return SDRG_OK;
+}
+
+static int32_t bank_reserve(sdrg_engine *e, const BankCall &c) {
+    BankStage &s = e->bank;
+    int32_t rc = ensure_halves(&s.hist, s.half(e->n_streams));
+    if (rc) return rc;
+    rc = ensure_nco_table(e);
+    if (rc) return rc;
+    if (s.inc_fs != c.fs) {  // new offsets or another rate: into the table the last launch does not read
+        const int at = s.inc_at ^ 1;
+        const size_t rows = s.rows(e->n_streams);
+        HIP_TRY(s.read[at].create(hipEventDisableTiming));
+        if (s.read_marked[at]) HIP_TRY(hipEventSynchronize(s.read[at]));  // the launch before the last
+        rc = ensure_device(&s.inc[at], rows);
+        if (rc) return rc;
+        std::vector<uint32_t> inc(rows);
+        for (size_t i = 0; i < rows; i++) inc[i] = nco_increment(s.offsets[i], c.fs);
+        HIP_TRY(hipMemcpy(s.inc[at].p, inc.data(), sizeof(uint32_t) * rows, hipMemcpyHostToDevice));
+        s.inc_at = at;  // what is committed here is the offsets in force at this rate: no call's state
+        s.inc_fs = c.fs;
+    }
+    HIP_TRY(s.read[s.inc_at].create(hipEventDisableTiming));
+    if (s.taps_fs != c.fs) {  // the taps travel in the kernel arguments: nothing on the device to replace
+        ddc_design(c.fs, s.cfg.cutoff_hz, s.cfg.taps, s.taps.h);
+        s.taps_fs = c.fs;
+    }
+    return SDRG_OK;
+}
+
+// one bank call on the main stream: iq, out in device memory
+static int32_t bank_launch(sdrg_engine *e, const BankCall &c, const void *iq, void *out) {
+    BankStage &s = e->bank;
+    BankParams p{};
+    fir_tile_fill(&p, c.cur, s.cfg.decimation, s.cfg.taps, c, s.hist, s.half(e->n_streams));
+    p.g0_lo = (uint32_t)c.cur.g;
+    p.nco_tab = e->d_nco_tab.p;
+    p.incs = s.inc[s.inc_at].p;
+    p.channels = s.cfg.channels;
+    HIP_TRY(launch_bank(iq, c.fmt, e->n_streams, p, s.taps, static_cast<float *>(out), e->s_main));
+    HIP_TRY(hipEventRecord(s.read[s.inc_at], e->s_main));
+    s.read_marked[s.inc_at] = true;
+    s.cur = c.cur;
+    s.cur.advance(c.n);
+    s.fs = c.fs;
+    e->outputs_unmarked = true;
+    return SDRG_OK;
+}
+
+static constexpr auto bank_stage = &stage_call<BankCall, bank_resolve, bank_reserve, bank_launch, int32_t>;
+
+int32_t sdrg_engine_bank_device(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    return bank_stage(e, "iq", iq, out, n_out, false, fmt);
+}
+
+int32_t sdrg_engine_bank_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {
+    return bank_stage(e, "iq", iq, out, n_out, true, fmt);
 }
 
 // ---- demodulator stage (demod.hip) --------------------------------------------------------------------------------

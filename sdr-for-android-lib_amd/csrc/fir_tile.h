@@ -1,4 +1,6 @@
 // fir_tile.h — the tile form the FIR stages share: ddc.hip, demod.hip's FIR kernel and sideband.hip take all of it;
+// bank.hip takes all of it with a channel-group dimension in the grid and a close_stream of its own (one history per
+// stream, C rows of tail);
 // channelizer.hip takes the grid, the history, the window and the staging, and has its own sums; resample.hip takes the
 // grid, the history and the output trait, and has a filter phase per output in place of the polyphase layout below.
 // DESIGN.md §3.18a says what the frame owns and what a stage supplies.

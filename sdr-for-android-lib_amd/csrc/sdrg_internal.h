@@ -201,6 +201,21 @@ int ddc_tile_outputs(int decim, int taps);  // outputs per workgroup
 hipError_t launch_ddc(const void *iq, int fmt, int n_streams, const DdcParams &p, const DdcTaps &taps, float *out,
                       hipStream_t stream);
 
+// DDC bank stage (bank.hip): per stream s and channel c < channels, row s channels + c of out is launch_ddc's row for the
+// stream's n raw samples at inc = incs[s channels + c] (phase inc * (g0_lo + t) at local index t), through the same
+// taps.  The history holds *unmixed* samples, [taps - 1][2] per stream.  Writes out [n_streams * channels][cap][2].
+// group (channels per workgroup: bank_group) and vec_ok are the launcher's.
+struct BankParams : FirTileParams {
+    uint32_t g0_lo;
+    const float *nco_tab;  // nco_tables() on the device
+    const uint32_t *incs;  // [n_streams][channels]
+    int channels, group, vec_ok;
+};
+int bank_tile_outputs(int decim, int taps);       // outputs per workgroup
+int bank_group(int channels, int n_streams);      // channels per workgroup
+hipError_t launch_bank(const void *iq, int fmt, int n_streams, const BankParams &p, const DdcTaps &taps, float *out,
+                       hipStream_t stream);
+
 // Demodulator stage (demod.hip): per stream the n complex samples at chan + stream * in_stride (float2) through the
 // detector (mode, kf; the previous sample from state_old), the DC block and the de-emphasis (alpha, a; m and s from
 // state_old) in `scratch` [n_streams][scratch_stride] floats, then out[j] = gain * sum_k h[k] v[first + j decim - k];

@@ -39,6 +39,7 @@ INTEGRATE_MEAN, INTEGRATE_MAX, INTEGRATE_EMA = 0, 1, 2              # sdrg_integ
 INTEGRATE_MAX_PERIOD = 64
 PEAKS_MAX, PEAKS_MAX_SEPARATION = 64, 4096                          # SDRG_PEAKS_MAX, SDRG_PEAKS_MAX_SEPARATION
 DDC_MAX_TAPS, DDC_MAX_DECIMATION = 511, 512                         # SDRG_DDC_MAX_TAPS, SDRG_DDC_MAX_DECIMATION
+BANK_MAX_CHANNELS = 4096                                            # SDRG_BANK_MAX_CHANNELS
 DEMOD_AM, DEMOD_FM = 0, 1                                           # SDRG_DEMOD_AM, SDRG_DEMOD_FM
 DEMOD_OUT_S16, DEMOD_OUT_F32 = 0, 1                                 # SDRG_DEMOD_OUT_*
 DEMOD_MAX_TAPS, DEMOD_MAX_DECIMATION, DEMOD_MAX_IN = 255, 64, 1 << 20  # SDRG_DEMOD_MAX_*
@@ -133,6 +134,9 @@ EXPORTS = [
     "sdrg_engine_peaks_host", "sdrg_engine_peaks_integrated_host",
     "sdrg_ddc_design", "sdrg_nco_tables", "sdrg_ddc_tile_outputs", "sdrg_engine_set_ddc", "sdrg_engine_get_ddc",
     "sdrg_engine_ddc_reset", "sdrg_engine_ddc_max_out", "sdrg_engine_ddc_device", "sdrg_engine_ddc_host",
+    "sdrg_bank_geometry", "sdrg_engine_set_bank", "sdrg_engine_bank_retune", "sdrg_engine_get_bank",
+    "sdrg_engine_bank_offsets", "sdrg_engine_bank_reset", "sdrg_engine_bank_max_out", "sdrg_engine_bank_device",
+    "sdrg_engine_bank_host",
     "sdrg_demod_design", "sdrg_demod_geometry", "sdrg_engine_set_demod", "sdrg_engine_get_demod",
     "sdrg_engine_demod_reset", "sdrg_engine_demod_max_out", "sdrg_engine_demod_device", "sdrg_engine_demod_host",
     "sdrg_engine_ddc_demod_host",
@@ -228,6 +232,13 @@ class DdcConfig(ctypes.Structure):
     """sdrg_ddc_config: the DDC stage's channel offset, low-pass cutoff, decimation and tap count (include/sdrg.h)."""
     _fields_ = [("offset_hz", ctypes.c_double), ("cutoff_hz", ctypes.c_double), ("decimation", ctypes.c_int32),
                 ("taps", ctypes.c_int32)]
+
+
+class BankConfig(ctypes.Structure):
+    """sdrg_bank_config: the DDC bank's shared low-pass cutoff, decimation and tap count, and its channels per stream
+    (include/sdrg.h)."""
+    _fields_ = [("cutoff_hz", ctypes.c_double), ("decimation", ctypes.c_int32), ("taps", ctypes.c_int32),
+                ("channels", ctypes.c_int32)]
 
 
 class DemodConfig(ctypes.Structure):
@@ -589,6 +600,15 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_ddc_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
         "sdrg_engine_ddc_device": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_ddc_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_bank_geometry": (_I32, [_I32, _I32, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+        "sdrg_engine_set_bank": (_I32, [P, ctypes.POINTER(BankConfig), P]),
+        "sdrg_engine_bank_retune": (_I32, [P, P]),
+        "sdrg_engine_get_bank": (_I32, [P, ctypes.POINTER(BankConfig), ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_bank_offsets": (_I32, [P, P, P]),
+        "sdrg_engine_bank_reset": (_I32, [P]),
+        "sdrg_engine_bank_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_bank_device": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_bank_host": (_I32, [P, P, _I32, P, ctypes.POINTER(_I32)]),
         "sdrg_demod_design": (_I32, [ctypes.POINTER(DemodConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
                                      ctypes.POINTER(_F), P]),
         "sdrg_demod_geometry": (_I32, [_I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
@@ -883,6 +903,15 @@ def ddc_tile_outputs(decimation: int, taps: int) -> int:
     t = _I32()
     _check(load().sdrg_ddc_tile_outputs(decimation, taps, ctypes.byref(t)), "ddc_tile_outputs")
     return t.value
+
+
+def bank_geometry(decimation: int, taps: int, channels: int, n_streams: int) -> tuple[int, int]:
+    """(tile_outputs, channels_per_group) of the DDC bank's kernel: consecutive outputs, and consecutive channels of a
+    stream, per workgroup (host-side)."""
+    t, g = _I32(), _I32()
+    _check(load().sdrg_bank_geometry(decimation, taps, channels, n_streams, ctypes.byref(t), ctypes.byref(g)),
+           "bank_geometry")
+    return t.value, g.value
 
 
 def demod_design(**fields) -> dict:
@@ -1450,6 +1479,66 @@ class Engine:
         """Host path: iq is [n_streams][samplesPerReading * 2] raw samples; returns complex64 [n_streams][n_out]."""
         return self._iq_call(load().sdrg_engine_ddc_host, "ddc_host", iq, fmt,
                              lambda: np.empty((self.n_streams, self.ddc_max_out()), np.complex64))
+
+    # ---- DDC bank stage --------------------------------------------------------------------------
+    def _bank_offsets(self, offsets_hz, channels: int) -> np.ndarray:
+        """offsets_hz as contiguous float64 [n_streams][channels]."""
+        o = np.ascontiguousarray(offsets_hz, dtype=np.float64)
+        if o.shape != (self.n_streams, channels):
+            raise SdrgError(f"offsets_hz {o.shape}: expected ({self.n_streams}, {channels})")
+        return o
+
+    def set_bank(self, offsets_hz=None, **fields) -> None:
+        """sdrg_engine_set_bank: offsets_hz [n_streams][C] and cutoff_hz, decimation, taps (fields left out are 0);
+        channels is offsets_hz's C unless given.  set_bank(off=True) switches the stage off."""
+        if fields.pop("off", False):
+            if fields or offsets_hz is not None:
+                raise TypeError("off=True takes no other field")
+            _check(load().sdrg_engine_set_bank(self._h, None, None), "set_bank")
+            return
+        if offsets_hz is None:
+            raise TypeError("set_bank needs offsets_hz")
+        o = np.ascontiguousarray(offsets_hz, dtype=np.float64)
+        fields.setdefault("channels", o.shape[-1] if o.ndim == 2 else 0)
+        c = _filled(BankConfig, "bank", fields)
+        o = self._bank_offsets(o, c.channels)  # the library reads n_streams * channels values
+        _check(load().sdrg_engine_set_bank(self._h, ctypes.byref(c), _ptr(o)), "set_bank")
+
+    def bank_retune(self, offsets_hz) -> None:
+        """sdrg_engine_bank_retune: replace all offsets [n_streams][C]; restarts nothing (see include/sdrg.h)."""
+        o = self._bank_offsets(offsets_hz, self.bank_config()["channels"])
+        _check(load().sdrg_engine_bank_retune(self._h, _ptr(o)), "bank_retune")
+
+    def bank_config(self) -> dict:
+        """The configuration in force, plus samples_consumed."""
+        c, g0 = BankConfig(), ctypes.c_uint64()
+        _check(load().sdrg_engine_get_bank(self._h, ctypes.byref(c), ctypes.byref(g0)), "get_bank")
+        return dict(_as_dict(c), samples_consumed=g0.value)
+
+    def bank_offsets(self) -> tuple[np.ndarray, np.ndarray]:
+        """(offsets_hz float64, increments uint32 at the current sample rate), each [n_streams][C]."""
+        C = self.bank_config()["channels"]
+        o, inc = np.zeros((self.n_streams, C), np.float64), np.zeros((self.n_streams, C), np.uint32)
+        _check(load().sdrg_engine_bank_offsets(self._h, _ptr(o), _ptr(inc)), "bank_offsets")
+        return o, inc
+
+    def bank_reset(self) -> None:
+        _check(load().sdrg_engine_bank_reset(self._h), "bank_reset")
+
+    def bank_max_out(self) -> int:
+        """ceil(samplesPerReading / decimation): the row length of a bank call's output, in complex samples."""
+        return self._i32_call(load().sdrg_engine_bank_max_out, "bank_max_out")
+
+    def bank_device(self, iq_ptr: int, fmt: int, out_ptr: int) -> int:
+        """Device path: iq [n_streams][N] raw samples in, out [n_streams][C][bank_max_out()] complex64 out;
+        asynchronous on the main stream.  Returns n_out, the outputs this call produced per row (the rest is zero)."""
+        return self._i32_call(load().sdrg_engine_bank_device, "bank_device", iq_ptr, fmt, out_ptr)
+
+    def bank(self, iq: np.ndarray, fmt: int = CS8) -> np.ndarray:
+        """Host path: iq is [n_streams][samplesPerReading * 2] raw samples; returns complex64 [n_streams][C][n_out]."""
+        C = self.bank_config()["channels"]
+        return self._iq_call(load().sdrg_engine_bank_host, "bank_host", iq, fmt,
+                             lambda: np.empty((self.n_streams, C, self.bank_max_out()), np.complex64))
 
     # ---- demodulator stage -----------------------------------------------------------------------
     def set_demod(self, **fields) -> None:
