@@ -1847,6 +1847,161 @@ int32_t sdrg_engine_listen_afc_host(sdrg_engine *eng, int32_t steps, const void 
                                     int32_t *n_out, sdrg_squelch_record *squelch_records, sdrg_agc_record *agc_records,
                                     sdrg_afc_record *afc_records);
 
+/* ------------------------------------------------------------------------------------------------
+ * BUILD EXTENSION, not a reference interface: the symbol stage: the symbol clock of FM audio recovered block by block
+ * and the audio sliced to 2 or 4 levels per stream, one byte (or one float) per symbol.  Per stream, the n real floats
+ * of a call (the demodulator's SDRG_DEMOD_OUT_F32 rows, or any rows in device memory) are cut into blocks of S values
+ * at the global indices that are multiples of S, as the AFC's are.  A clock that is a function of the global index alone
+ * cuts the stream into cells of 2^32 / inc samples; each completed block's squared differences, correlated with that
+ * clock, move a smoothed estimate of where the transmitter's cells meet, and while its coherence says the stream is
+ * locked the estimate sets the fraction of the cell at which the following blocks are sampled (feed-forward: no
+ * decision reaches back into the block that produced it, and a symbol is written by the call that holds the sample
+ * ending its cell).  Over the whole life of a stream (the calls' values concatenated, whatever their lengths) the
+ * result is that of one call.  All arithmetic is float, every product, sum, quotient and root rounded on its own,
+ * unless "double" or "integer" is stated; denormals are kept.  A non-finite value makes that stream's outputs and
+ * records unspecified from then on.
+ *   input      [n_streams][in_stride] float, 4-byte aligned, 0 <= n <= in_stride <= max_in.  g is the number of values
+ *              every stream has consumed; x[i] is the value at global index i, and x[i] = +0 for i < 0.
+ *   config     sample_rate and symbol_rate finite, > 0, sample_rate / symbol_rate in [2, 64]; levels 2 or 4; block S a
+ *              power of two in [SDRG_SYM_MIN_BLOCK, SDRG_SYM_MAX_BLOCK]; tau_blocks and tau_level_blocks finite, >= 0;
+ *              floor_db finite; lock_threshold in [0, 1]; phase_trim in [-0.5, 0.5]; level_mode SDRG_SYM_LEVEL_TRACK or
+ *              SDRG_SYM_LEVEL_FIXED; level_scale finite, > 0; fixed_centre finite; fixed_threshold finite, > 0 (the
+ *              last three are checked in either level_mode); format SDRG_SYM_HARD or SDRG_SYM_SOFT; max_in in
+ *              [1, 2^20].  Each is refused on its own.  A rejected set_symbols changes nothing; an accepted one, and
+ *              sdrg_engine_symbols_reset, restart every stream: g = 0, A = B = U = M = Q = +0, coh = +0, unseeded,
+ *              unlocked, slips = 0, tau = (uint32)(2^31 + trim), and centre = +0, thr = 1 (SDRG_SYM_LEVEL_TRACK) or the
+ *              two configured floats (SDRG_SYM_LEVEL_FIXED).
+ *   design     sdrg_symbols_design, in double, each result rounded once: inc = rint(2^32 symbol_rate / sample_rate) as
+ *              uint32, refused outside [2^26, 2^31]; rinc = (float)(1.0 / inc); beta = 1 - exp(-1 / tau_blocks) and
+ *              beta_level the same of tau_level_blocks, each exactly 1.0f at 0; floor_thr = 10^(floor_db / 10), refused
+ *              unless it is a finite positive float; lock_thr = (float)lock_threshold; K = (float)(2^31 / pi); trim =
+ *              (int64) rint(phase_trim 2^32); rs = (float)(1.0 / S); scale, centre and threshold, the floats of level_scale,
+ *              fixed_centre and fixed_threshold; and the table tab[k] = ((float)cos, (float)sin)(2 pi (k + 0.5) / 1024), k in [0, 1024).
+ *   clock      c_i = (uint32)(inc i): integer, wrapping, a function of the global index only.  Sample i >= 1 *emits*
+ *              when c_i < inc: the clock wrapped between i - 1 and i, so the cells' edges never depend on the data.
+ *              The emitting samples in [0, g) number K(g) = floor(inc (g - 1) / 2^32) for g >= 1, K(0) = 0; a call
+ *              writes n_sym = K(g + n) - K(g) symbols (sdrg_symbols_count, in 128-bit integers), and rows of cap =
+ *              floor(inc max_in / 2^32) + 1 symbols (sdrg_engine_symbols_max_out) hold any call's.
+ *   products   at in-block index j >= 1: dx = x[i] - x[i - 1], u = dx dx, (tc, ts) = tab[c_i >> 22], a = u tc,
+ *              b = u ts; at j = 0, u = a = b = +0: a block's statistics depend on its own values only, and a block
+ *              seam costs one product in S.  q = x x at every j.
+ *   block      T(.) is the adjacent-pair tree over a block's S values in order (v'[i] = v[2 i] + v[2 i + 1] until one
+ *              value is left), rs = 1 / S: Ab = T(a) rs, Bb = T(b) rs, Ub = T(u) rs, Mb = T(x) rs, Qb = T(q) rs.
+ *   step       for each completed block, in order: if Qb < floor_thr the block is held (nothing moves, the levels
+ *              included; held counts one): a closed squelch's zeros.  Otherwise, if not yet seeded, (A, B, U, M, Q) =
+ *              (Ab, Bb, Ub, Mb, Qb) and seeded = 1, else A = A + beta (Ab - A) and the same for B and U, and M = M +
+ *              beta_level (Mb - M) and the same for Q (also at beta = 1); then coh = sqrtf(A A + B B) / U, +0 when U
+ *              is 0, and locked = coh >= lock_thr.  If locked: ang = (int64) rintf(sdrg_atan2f(B, A) K), tau' =
+ *              (uint32)(ang - (inc >> 1) + 2^31 + trim) in 64-bit integers, wrapped; with d = (int32)(tau' - tau), one
+ *              slip is counted when d >= 0 && tau' < tau or d < 0 && tau' > tau (the sampling point went round the
+ *              cell's edge: one symbol is sampled twice or not at all); tau = tau'.  If not, tau stays.  Then the
+ *              levels: SDRG_SYM_LEVEL_TRACK: centre = M, w = Q - M M, thr = level_scale sqrtf(fmaxf(w, +0));
+ *              SDRG_SYM_LEVEL_FIXED: the two configured floats, always.  Block k is sampled with (tau, centre, thr,
+ *              locked) after block k - 1.  (u is largest where the cells meet, and sits half a sample before i:
+ *              - inc / 2; the sampling point is half a cell after the edge: + 2^31; u does not see a DC offset.)
+ *   symbol     for an emitting sample i of global block k: num = (uint64) c_i + (2^32 - tau), qd = num / inc, r = num
+ *              - qd inc, in integers (qd <= 65); nu = (float) r rinc; x0 = x[i - qd], x1 = x[i - qd - 1]; y = x0 - nu
+ *              (x0 - x1); v = y - centre: the cell that ended at i, sampled linearly at the fraction tau / 2^32 of its
+ *              length from the 66 values before i and none after.  SDRG_SYM_HARD, levels 2: s = v >= 0; levels 4: s =
+ *              v < -thr ? 0 : v < 0 ? 1 : v < thr ? 2 : 3; the byte is s | (locked ? 0 : SDRG_SYM_UNLOCKED).
+ *              SDRG_SYM_SOFT: the float thr > 0 ? v / thr : +0.  Its place in the call's row is K(i) - K(g).
+ *   output     symbols [n_streams][cap], uint8 (SDRG_SYM_HARD) or float (SDRG_SYM_SOFT, 4-byte aligned): every byte is
+ *              written by every call, zero from n_sym on.  *n_sym is set on the host before the call returns.  n = 0 is
+ *              a valid call: it writes symbols and the records and leaves the state where it is.
+ *   records    sdrg_symbols_record [n_streams] (32 bytes each) or NULL, written by every call: tau_frac = (float) tau
+ *              2^-32, tau, coherence the last computed coh (+0 before the first), centre, threshold, slips since the
+ *              last restart, held_blocks of the blocks this call completed, flags = locked | seeded << 1.
+ *   state      per stream the 66 values before the block in progress and that block's values so far, and the step's
+ *              words, in device memory (allocated at the first call), in two halves a call reads and writes in turn;
+ *              per engine g, advanced by n once the call's launches have been issued: a failed call commits nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define SDRG_SYM_LEVEL_TRACK 1
+#define SDRG_SYM_LEVEL_FIXED 2
+#define SDRG_SYM_HARD 1
+#define SDRG_SYM_SOFT 2
+#define SDRG_SYM_LOCKED 1 /* sdrg_symbols_record.flags */
+#define SDRG_SYM_SEEDED 2
+#define SDRG_SYM_UNLOCKED 0x80 /* a SDRG_SYM_HARD byte sampled while unlocked */
+#define SDRG_SYM_MIN_BLOCK 64
+#define SDRG_SYM_MAX_BLOCK 1024
+#define SDRG_SYM_MAX_IN 1048576
+#define SDRG_SYM_HISTORY 66
+#define SDRG_SYM_TABLE 1024
+typedef struct sdrg_symbols_config {
+    double sample_rate;      /* Hz: the rate of the input's values */
+    double symbol_rate;      /* symbols per second */
+    double tau_blocks;       /* the time constant of A, B and U */
+    double tau_level_blocks; /* of M and Q */
+    double floor_db;         /* blocks whose mean square is under 10^(floor_db / 10) move nothing */
+    double lock_threshold;
+    double phase_trim;       /* cells: added to the sampling point */
+    double level_scale;      /* SDRG_SYM_LEVEL_TRACK: thr = level_scale * the standard deviation */
+    double fixed_centre;     /* SDRG_SYM_LEVEL_FIXED */
+    double fixed_threshold;
+    int32_t levels;
+    int32_t block;
+    int32_t level_mode;
+    int32_t format;
+    int32_t max_in;
+} sdrg_symbols_config;
+
+typedef struct sdrg_symbols_design_values {
+    int64_t trim;
+    uint32_t inc;
+    float rinc, beta, beta_level, floor_thr, lock_thr, K, rs, scale, centre, threshold;
+} sdrg_symbols_design_values;
+
+typedef struct sdrg_symbols_record {
+    float tau_frac;
+    uint32_t tau;
+    float coherence;
+    float centre;
+    float threshold;
+    int32_t slips;
+    int32_t held_blocks;
+    int32_t flags;
+} sdrg_symbols_record;
+
+/* Host-only, no device.  After the checks of set_symbols: the design values above and, unless table is NULL, the
+ * SDRG_SYM_TABLE pairs (cos, sin). */
+int32_t sdrg_symbols_design(const sdrg_symbols_config *cfg, sdrg_symbols_design_values *design, float *table);
+/* Host-only: *tile = max(512, block), the consecutive values one workgroup of the moments kernel takes, by position
+ * counted from the start of the block in progress; *pass_tile, the consecutive symbols of a row one workgroup of the
+ * pass kernel writes.  Either pointer may be NULL. */
+int32_t sdrg_symbols_geometry(int32_t block, int32_t *tile, int32_t *pass_tile);
+/* Host-only: K(g + n) - K(g), the symbols a call of n values writes at stream position g, in 128-bit integers; -1 for
+ * an inc outside [2^26, 2^31]. */
+int64_t sdrg_symbols_count(uint32_t inc, uint64_t g, uint64_t n);
+
+/* Set (cfg != NULL) or switch off (cfg == NULL) the stage; the table is uploaded before the configuration is committed.
+ * A symbols call while it is off returns SDRG_E_INVALID and writes nothing. */
+int32_t sdrg_engine_set_symbols(sdrg_engine *eng, const sdrg_symbols_config *cfg);
+/* The configuration in force (SDRG_E_INVALID when off), its design values and g; any pointer may be NULL. */
+int32_t sdrg_engine_get_symbols(const sdrg_engine *eng, sdrg_symbols_config *cfg, sdrg_symbols_design_values *design,
+                                uint64_t *samples_consumed);
+int32_t sdrg_engine_symbols_reset(sdrg_engine *eng);
+/* *cap = floor(inc max_in / 2^32) + 1: the symbols per row of `symbols`. */
+int32_t sdrg_engine_symbols_max_out(const sdrg_engine *eng, int32_t *cap);
+/* in: n_streams rows of in_stride floats, of which the first n of every row are this call's; symbols [n_streams][cap]
+ * uint8 or float by format; records [n_streams] or NULL; all in device memory.  Stream rules and waiting as
+ * sdrg_engine_squelch_device. */
+int32_t sdrg_engine_symbols_device(sdrg_engine *eng, const void *in, int32_t in_stride, int32_t n, void *symbols,
+                                   sdrg_symbols_record *records, int32_t *n_sym);
+/* Host buffers of the same shapes, synchronous; all n_streams * in_stride values of in are copied. */
+int32_t sdrg_engine_symbols_host(sdrg_engine *eng, const void *in, int32_t in_stride, int32_t n, void *symbols,
+                                 sdrg_symbols_record *records, int32_t *n_sym);
+/* sdrg_engine_listen_host with the symbol stage reading the demodulator's float audio where it lies on the device,
+ * ahead of the resampler (in_stride = the demodulator's cap, n = its call's n_out): symbols [n_streams][cap] and, unless
+ * symbol_records is NULL, the records [n_streams] come back in addition, and *n_sym.  out may be NULL: the audio then
+ * stays on the device (n_out is still set).  SDRG_E_INVALID, with no stage moved, under listen_host's conditions in its
+ * order, then: the symbol stage off; the demodulator not writing SDRG_DEMOD_OUT_F32; the stage's max_in under the
+ * demodulator's row length.  Every buffer is reserved before the first launch: a call that fails for want of memory
+ * commits nothing in any stage either.  The other chain calls never run the symbol stage, whether or not it is set. */
+int32_t sdrg_engine_listen_symbols_host(sdrg_engine *eng, int32_t steps, const void *iq, int32_t fmt, void *out,
+                                        int32_t *n_out, sdrg_squelch_record *squelch_records,
+                                        sdrg_agc_record *agc_records, void *symbols,
+                                        sdrg_symbols_record *symbol_records, int32_t *n_sym);
+
 /* JNI read(): register the callback table (copied). NULL clears it. */
 int32_t sdrg_engine_set_callbacks(sdrg_engine *eng, const sdrg_callbacks *cbs);
 

@@ -442,6 +442,65 @@ sdrg_afc_design_values afc_design(const sdrg_afc_config &c) {
     return d;
 }
 
+// The symbol stage's configuration rules (sdrg.h): nullptr, or what is wrong
+const char *symbols_check(const sdrg_symbols_config &c) {
+    if (!std::isfinite(c.sample_rate) || !(c.sample_rate > 0.0)) return "sample_rate must be > 0 and finite";
+    if (!std::isfinite(c.symbol_rate) || !(c.symbol_rate > 0.0)) return "symbol_rate must be > 0 and finite";
+    const double sps = c.sample_rate / c.symbol_rate;
+    if (!(sps >= 2.0) || !(sps <= 64.0)) return "sample_rate / symbol_rate must be in [2, 64]";
+    if (c.levels != 2 && c.levels != 4) return "levels must be 2 or 4";
+    if (c.block < SDRG_SYM_MIN_BLOCK || c.block > SDRG_SYM_MAX_BLOCK || (c.block & (c.block - 1)) != 0)
+        return "block must be a power of two in [64, 1024]";
+    if (!(c.tau_blocks >= 0.0) || !std::isfinite(c.tau_blocks)) return "tau_blocks must be >= 0 and finite";
+    if (!(c.tau_level_blocks >= 0.0) || !std::isfinite(c.tau_level_blocks))
+        return "tau_level_blocks must be >= 0 and finite";
+    if (!std::isfinite(c.floor_db)) return "floor_db must be finite";
+    if (!(c.lock_threshold >= 0.0) || !(c.lock_threshold <= 1.0)) return "lock_threshold must be in [0, 1]";
+    if (!(c.phase_trim >= -0.5) || !(c.phase_trim <= 0.5)) return "phase_trim must be in [-0.5, 0.5]";
+    if (c.level_mode != SDRG_SYM_LEVEL_TRACK && c.level_mode != SDRG_SYM_LEVEL_FIXED)
+        return "level_mode must be SDRG_SYM_LEVEL_TRACK or SDRG_SYM_LEVEL_FIXED";
+    if (!(c.level_scale > 0.0) || !std::isfinite(c.level_scale)) return "level_scale must be > 0 and finite";
+    if (!std::isfinite(c.fixed_centre)) return "fixed_centre must be finite";
+    if (!(c.fixed_threshold > 0.0) || !std::isfinite(c.fixed_threshold)) return "fixed_threshold must be > 0 and finite";
+    if (c.format != SDRG_SYM_HARD && c.format != SDRG_SYM_SOFT) return "format must be SDRG_SYM_HARD or SDRG_SYM_SOFT";
+    if (c.max_in < 1 || c.max_in > SDRG_SYM_MAX_IN) return "max_in outside [1, 2^20]";
+    const double inc = std::rint(4294967296.0 * c.symbol_rate / c.sample_rate);
+    if (!(inc >= 67108864.0) || !(inc <= 2147483648.0)) return "2^32 symbol_rate / sample_rate outside [2^26, 2^31]";
+    const float floor_thr = (float)std::pow(10.0, c.floor_db / 10.0);
+    if (!std::isfinite(floor_thr) || !(floor_thr > 0.0f)) return "10^(floor_db / 10) is not a finite, positive float";
+    return nullptr;
+}
+
+// The symbol stage's constants and table (sdrg.h), in double, each rounded once; cfg has passed symbols_check
+sdrg_symbols_design_values symbols_design(const sdrg_symbols_config &c, float *table) {
+    sdrg_symbols_design_values d;
+    d.trim = (int64_t)std::rint(c.phase_trim * 4294967296.0);
+    d.inc = (uint32_t)std::rint(4294967296.0 * c.symbol_rate / c.sample_rate);
+    d.rinc = (float)(1.0 / (double)d.inc);
+    d.beta = c.tau_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.tau_blocks)) : 1.0f;
+    d.beta_level = c.tau_level_blocks > 0.0 ? (float)(1.0 - std::exp(-1.0 / c.tau_level_blocks)) : 1.0f;
+    d.floor_thr = (float)std::pow(10.0, c.floor_db / 10.0);
+    d.lock_thr = (float)c.lock_threshold;
+    d.K = (float)(2147483648.0 / M_PI);
+    d.rs = (float)(1.0 / (double)c.block);
+    d.scale = (float)c.level_scale;
+    d.centre = (float)c.fixed_centre;
+    d.threshold = (float)c.fixed_threshold;
+    if (table)
+        for (int k = 0; k < SDRG_SYM_TABLE; k++) {
+            const double w = 2.0 * M_PI * ((double)k + 0.5) / (double)SDRG_SYM_TABLE;
+            table[2 * k] = (float)std::cos(w);
+            table[2 * k + 1] = (float)std::sin(w);
+        }
+    return d;
+}
+
+// K(g + n) - K(g), K(g) = floor(inc (g - 1) / 2^32) for g >= 1 and K(0) = 0: inc (g - 1) passes 2^64
+uint64_t symbols_count(uint32_t inc, uint64_t g, uint64_t n) {
+    const auto K = [inc](unsigned __int128 x) -> unsigned __int128 { return x ? ((x - 1) * inc) >> 32 : 0; };
+    return (uint64_t)(K((unsigned __int128)g + n) - K(g));
+}
+
 // The noise blanker stage's configuration rules (sdrg.h): nullptr, or what is wrong
 const char *blanker_check(const sdrg_blanker_config &c) {
     if (!(c.tau_blocks >= 0.0) || !std::isfinite(c.tau_blocks)) return "tau_blocks must be >= 0 and finite";

@@ -49,6 +49,11 @@ void iqcorr_design(const sdrg_iqcorr_config &cfg, float *beta_dc, float *beta_ba
 // AFC stage: the configuration rules (nullptr = valid) and the seven design values
 const char *afc_check(const sdrg_afc_config &cfg);
 sdrg_afc_design_values afc_design(const sdrg_afc_config &cfg);
+// symbol stage: the configuration rules (nullptr = valid), the design values, the table [SDRG_SYM_TABLE][2] (null: not
+// wanted), and K(g + n) - K(g), the symbols a call of n values writes at stream position g
+const char *symbols_check(const sdrg_symbols_config &cfg);
+sdrg_symbols_design_values symbols_design(const sdrg_symbols_config &cfg, float *table);
+uint64_t symbols_count(uint32_t inc, uint64_t g, uint64_t n);
 const char *blanker_check(const sdrg_blanker_config &cfg);
 void blanker_design(const sdrg_blanker_config &cfg, float *beta, float *ratio, float *floor_thr);
 // tone detector stage: the configuration rules (nullptr = valid) and the design, table [K][S][2], wf [S] and the five

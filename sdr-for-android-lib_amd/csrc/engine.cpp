@@ -333,6 +333,24 @@ struct TonesStage {
     size_t half(int B) const { return (size_t)B * (size_t)tones_state_words(cfg.n_tones, cfg.components); }
 };
 
+// symbol stage (sdrg_engine_set_symbols / symbols_device / symbols_host / listen_symbols_host; symbols.hip)
+struct SymbolsStage {
+    sdrg_symbols_config cfg{};
+    bool set = false;
+    BlockCursor cur;
+    sdrg_symbols_design_values des{};  // symbols_design of cfg
+    DeviceBuf<float> d_tab;            // the table [SDRG_SYM_TABLE][2]: written by set_symbols
+    // halves of [n_streams][sym_state_words(S)]: the step's words, the history, the block's values so far
+    DevicePingPong<float> state;
+    // [the most blocks a call completes]: [5][n_streams] moments, then one more of [4][n_streams] words
+    DeviceBuf<float> blk;
+    bool soft() const { return cfg.format == SDRG_SYM_SOFT; }
+    int cap() const { return (int)(((uint64_t)des.inc * (uint64_t)cfg.max_in) >> 32) + 1; }
+    size_t width() const { return soft() ? sizeof(float) : 1; }  // bytes per symbol
+    size_t half(int B) const { return (size_t)B * (size_t)sym_state_words(cfg.block); }
+    size_t blocks() const { return (size_t)BlockCursor::cap(cfg.max_in, cfg.block); }
+};
+
 // sideband stage (sdrg_engine_set_sideband / sideband_device / sideband_host / listen_sideband_host; sideband.hip)
 struct SidebandStage {
     sdrg_sideband_config cfg{};
@@ -636,6 +654,7 @@ struct sdrg_engine {
     AfcStage afc;
     BlankerStage blank;
     TonesStage tones;
+    SymbolsStage sym;
     // The staging of the streaming stages' host calls (ddc_host, demod_host, channelizer_host, resample_host,
     // squelch_host, agc_host, iqcorr_host and the chains), as bytes: the caller's input, and the rows it gets back (with the squelch's
     // and the AGC's records behind them).  One pair serves them all, as spec_in does its
@@ -3889,6 +3908,153 @@ int32_t sdrg_engine_tones_host(sdrg_engine *e, const void *in, int32_t in_stride
     return tones_stage(e, "in", in, powers, n_blocks, true, in_stride, n, records);
 }
 
+// ---- symbol stage (symbols.hip) ------------------------------------------------------------------------------------
+
+int32_t sdrg_symbols_design(const sdrg_symbols_config *cfg, sdrg_symbols_design_values *design, float *table) {
+    if (!cfg || !design) return fail(SDRG_E_INVALID, "null symbols config or design");
+    if (const char *bad = symbols_check(*cfg)) return fail(SDRG_E_INVALID, "symbols: %s", bad);
+    *design = symbols_design(*cfg, table);
+    return SDRG_OK;
+}
+
+int32_t sdrg_symbols_geometry(int32_t block, int32_t *tile, int32_t *pass_tile) {
+    if (block < SDRG_SYM_MIN_BLOCK || block > BLOCK_MAX || (block & (block - 1)) != 0)
+        return fail(SDRG_E_INVALID, "symbols: block must be a power of two in [64, 1024]");
+    if (tile) *tile = block_tile(block);
+    if (pass_tile) *pass_tile = SYM_PASS_TILE;
+    return SDRG_OK;
+}
+
+int64_t sdrg_symbols_count(uint32_t inc, uint64_t g, uint64_t n) {
+    if (inc < (1u << 26) || inc > (1u << 31)) return -1;
+    return (int64_t)symbols_count(inc, g, n);
+}
+
+int32_t sdrg_engine_set_symbols(sdrg_engine *e, const sdrg_symbols_config *cfg) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    SymbolsStage &s = e->sym;
+    if (cfg) {
+        if (const char *bad = symbols_check(*cfg)) return fail(SDRG_E_INVALID, "symbols: %s", bad);
+        std::vector<float> tab((size_t)SDRG_SYM_TABLE * 2);
+        const sdrg_symbols_design_values des = symbols_design(*cfg, tab.data());
+        DeviceScope dscope(e->device);
+        HIP_TRY(dscope.error());
+        const int32_t rc = upload_floats(&s.d_tab, tab, "symbols table");
+        if (rc) return rc;
+        s.cfg = *cfg;
+        s.des = des;
+    }
+    s.set = cfg != nullptr;
+    s.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_get_symbols(const sdrg_engine *e, sdrg_symbols_config *cfg, sdrg_symbols_design_values *design,
+                                uint64_t *samples_consumed) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    const SymbolsStage &s = e->sym;
+    if (!s.set) return fail(SDRG_E_INVALID, "no symbols configuration set");
+    if (cfg) *cfg = s.cfg;
+    if (design) *design = s.des;
+    if (samples_consumed) *samples_consumed = s.cur.g;
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_symbols_reset(sdrg_engine *e) {
+    if (!e) return fail(SDRG_E_INVALID, "null engine");
+    e->sym.cur.restart();
+    return SDRG_OK;
+}
+
+int32_t sdrg_engine_symbols_max_out(const sdrg_engine *e, int32_t *cap) {
+    if (!e || !cap) return fail(SDRG_E_INVALID, "null engine or cap");
+    if (int32_t rc = require_set(e->sym.set, "symbols")) return rc;
+    *cap = e->sym.cap();
+    return SDRG_OK;
+}
+
+// n_out is the symbols the call writes (*n_sym); out is symbols; aux, the records.  n_blocks: the blocks it completes.
+struct SymbolsCall : StageCall {
+    int n_blocks = 0;
+};
+
+static int32_t sym_resolve(const sdrg_engine *e, int32_t in_stride, int32_t n, sdrg_symbols_record *records,
+                           SymbolsCall *c) {
+    const SymbolsStage &s = e->sym;
+    if (int32_t rc = require_set(s.set, "symbols")) return rc;
+    if (n < 0 || n > s.cfg.max_in) return fail(SDRG_E_INVALID, "symbols: n %d outside [0, max_in = %d]", n, s.cfg.max_in);
+    if (in_stride < std::max(n, 1) || in_stride > s.cfg.max_in)
+        return fail(SDRG_E_INVALID, "symbols: in_stride %d outside [max(n, 1) = %d, max_in = %d]", in_stride,
+                    std::max(n, 1), s.cfg.max_in);
+    c->n = n;
+    c->in_stride = in_stride;
+    c->cap = s.cap();
+    c->n_out = (int)symbols_count(s.des.inc, s.cur.g, (uint64_t)n);
+    c->n_blocks = s.cur.blocks(n, s.cfg.block);
+    c->in_bytes = (size_t)e->n_streams * (size_t)in_stride * sizeof(float);
+    c->out_bytes = (size_t)e->n_streams * (size_t)c->cap * s.width();
+    c->aux = records;
+    c->aux_bytes = (size_t)e->n_streams * sizeof(*records);
+    return SDRG_OK;
+}
+
+static int32_t sym_reserve(sdrg_engine *e, const SymbolsCall &) {
+    SymbolsStage &s = e->sym;
+    const int32_t rc = ensure_halves(&s.state, s.half(e->n_streams));
+    return rc ? rc : ensure_device(&s.blk, (size_t)e->n_streams * (s.blocks() * 5 + (s.blocks() + 1) * 4));
+}
+
+// One call on the main stream: in (rows of in_stride floats) and symbols, and c.aux, the records or null, in device memory
+static int32_t sym_launch(sdrg_engine *e, const SymbolsCall &c, const void *in, void *symbols) {
+    SymbolsStage &s = e->sym;
+    const size_t half = s.half(e->n_streams);
+    const sdrg_symbols_design_values &d = s.des;
+    const uint64_t g = s.cur.g;
+    SymParams p{};
+    p.n = c.n;
+    p.in_stride = c.in_stride;
+    p.block = s.cfg.block;
+    p.off = s.cur.offset(s.cfg.block);
+    p.n_blocks = c.n_blocks;
+    p.fresh = s.cur.fresh ? 1 : 0;
+    p.levels = s.cfg.levels;
+    p.track = s.cfg.level_mode == SDRG_SYM_LEVEL_TRACK ? 1 : 0;
+    p.soft = s.soft() ? 1 : 0;
+    p.n_sym = c.n_out;
+    p.cap = c.cap;
+    p.inc = d.inc;
+    p.c0 = (uint32_t)((uint64_t)d.inc * (g & 0xffffffffull));  // inc g mod 2^32
+    p.cpos0 = p.c0 - d.inc * (uint32_t)p.off;
+    p.tau0 = (uint32_t)(uint64_t)(2147483648ll + d.trim);
+    p.emit0 = (uint64_t)p.c0 + ((g >= 1 && p.c0 < d.inc) ? 0x100000000ull : 0ull);
+    p.trim = d.trim;
+    p.rinc = d.rinc, p.beta = d.beta, p.beta_level = d.beta_level, p.floor_thr = d.floor_thr, p.lock_thr = d.lock_thr;
+    p.K = d.K, p.rs = d.rs, p.level_scale = d.scale, p.fixed_centre = d.centre, p.fixed_thr = d.threshold;
+    p.tab = s.d_tab.p;
+    p.state_old = s.state.half(s.cur.old_half(), half);  // not read by a fresh call: p.fresh says so
+    p.state_new = s.state.next(s.cur, half);
+    p.mom = s.blk.p;
+    p.blk = reinterpret_cast<uint32_t *>(s.blk.p + (size_t)e->n_streams * s.blocks() * 5);
+    p.records = static_cast<sdrg_symbols_record *>(c.aux);
+    HIP_TRY(launch_symbols(static_cast<const float *>(in), e->n_streams, p, symbols, e->s_main));
+    s.cur.advance(c.n);  // a call without values wrote symbols and the records only: the state stays where it is
+    e->outputs_unmarked = true;
+    return SDRG_OK;
+}
+
+static constexpr auto sym_stage =
+    &stage_call<SymbolsCall, sym_resolve, sym_reserve, sym_launch, int32_t, int32_t, sdrg_symbols_record *>;
+
+int32_t sdrg_engine_symbols_device(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *symbols,
+                                   sdrg_symbols_record *records, int32_t *n_sym) {
+    return sym_stage(e, "in", in, symbols, n_sym, false, in_stride, n, records);
+}
+
+int32_t sdrg_engine_symbols_host(sdrg_engine *e, const void *in, int32_t in_stride, int32_t n, void *symbols,
+                                 sdrg_symbols_record *records, int32_t *n_sym) {
+    return sym_stage(e, "in", in, symbols, n_sym, true, in_stride, n, records);
+}
+
 // ---- the chains: DDC (-> AFC) (-> squelch) (-> AGC) -> demodulator or sideband (-> resampler), host memory in and out
 
 // The stage that turns the channel into audio.  What a chain asks of it, whichever it is: whether it is set, its
@@ -3935,12 +4101,22 @@ struct AfcStep {
     sdrg_afc_record *records;
 };
 
+// With `sym` (listen_symbols_host) the symbol stage reads the demodulator's float rows where the tone stage would, and
+// its symbols and records are staged behind the squelch's and the AGC's records; `out` may then be null: the audio is
+// not copied back.
+struct SymbolTap {
+    void *symbols;
+    sdrg_symbols_record *records;
+    int32_t *n_sym;
+};
+
 static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const void *iq, int32_t fmt, void *out,
                           int32_t *n_out, sdrg_squelch_record *sq_records = nullptr,
                           sdrg_agc_record *agc_records = nullptr, const ToneTap *tap = nullptr,
-                          const AfcStep *afc = nullptr) {
+                          const AfcStep *afc = nullptr, const SymbolTap *sym = nullptr) {
     if (!e) return fail(SDRG_E_INVALID, "null engine");
-    if (!iq || !out || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    if (!iq || (!out && !sym) || !n_out) return fail(SDRG_E_INVALID, "null iq, out or n_out");
+    if (sym && (!sym->symbols || !sym->n_sym)) return fail(SDRG_E_INVALID, "null symbols or n_sym");
     if (tap && (!tap->powers || !tap->n_blocks)) return fail(SDRG_E_INVALID, "null powers or n_blocks");
     if (steps & ~(SDRG_LISTEN_SQUELCH | SDRG_LISTEN_AGC | SDRG_LISTEN_RESAMPLE))
         return fail(SDRG_E_INVALID, "listen: unknown bits in steps 0x%x", (unsigned)steps);
@@ -3954,9 +4130,11 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     if (!rc && afc) rc = require_set(e->afc.set, "afc");
     if (!rc && afc && !e->afc.track())
         rc = fail(SDRG_E_INVALID, "the chain corrects the channel: afc mode must be SDRG_AFC_TRACK");
+    if (!rc && sym) rc = require_set(e->sym.set, "symbols");
     DdcCall d;
     // the squelch's, the AGC's, the detector's, the resampler's, the tone stage's and the AFC's
     StageCall q, g, a, r, t, f;
+    SymbolsCall y;  // the symbol stage's
     if (!rc) rc = ddc_resolve(e, fmt, &d);
     if (rc) return rc;
     // the checks between the stages come before the later stages' own: after them those cannot refuse their n
@@ -3988,8 +4166,17 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
             return fail(SDRG_E_INVALID, "tones max_in %d smaller than the %s's row length %d", e->tones.cfg.max_in, v.name,
                         v.cap);
     }
+    if (sym) {
+        if (!v.f32 || v.components != 1)
+            return fail(SDRG_E_INVALID, "the symbol stage reads real float audio: %s out_format must be %s", v.name,
+                        v.f32_name);
+        if (e->sym.cfg.max_in < v.cap)
+            return fail(SDRG_E_INVALID, "symbols max_in %d smaller than the %s's row length %d", e->sym.cfg.max_in, v.name,
+                        v.cap);
+    }
     rc = v.resolve(e, d.n_out, &a);
     a.in_stride = d.cap;  // the channel's rows are the DDC's
+    if (!rc && sym) rc = sym_resolve(e, a.cap, a.n_out, sym->records, &y);
     if (!rc && tap) rc = tones_resolve(e, a.cap, a.n_out, tap->records, &t);
     if (!rc && resample) rc = rs_resolve(e, a.cap, a.n_out, &r);
     if (!rc && squelch) rc = sq_resolve(e, d.cap, d.n_out, sq_records, &q);
@@ -4003,9 +4190,13 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     if (tap) aux.add(&powers, t.out_bytes);
     if (tap) aux.add(&t.aux, t.aux_bytes);
     if (afc) aux.add(&f.aux, f.aux_bytes);
+    void *symbols = sym ? sym->symbols : nullptr;  // the caller's, then where the launch writes them
+    if (sym) aux.add(&symbols, y.out_bytes);
+    if (sym) aux.add(&y.aux, y.aux_bytes);
     DeviceScope dscope(e->device);
     HIP_TRY(dscope.error());
     rc = ddc_reserve(e, d);
+    if (!rc && sym) rc = sym_reserve(e, y);
     if (!rc && tap) rc = tones_reserve(e, t);
     if (!rc && afc) rc = afc_reserve(e, f);
     if (!rc && squelch) rc = sq_reserve(e, q);
@@ -4023,11 +4214,13 @@ static int32_t chain_host(sdrg_engine *e, Detector det, int32_t steps, const voi
     void *audio = resample ? (void *)e->chain_audio.p : (void *)e->stream_out.p;
     if (!rc) rc = v.launch(e, a, e->chain_chan.p, audio);
     if (!rc && tap) rc = tones_launch(e, t, audio, powers);
+    if (!rc && sym) rc = sym_launch(e, y, audio, symbols);
     if (!rc && resample) rc = rs_launch(e, r, e->chain_audio.p, e->stream_out.p);
-    if (!rc) rc = aux.finish(e, out, last.out_bytes);
+    if (!rc) rc = aux.finish(e, out, out ? last.out_bytes : 0);  // a null out (listen_symbols_host): no rows back
     if (rc) return rc;
     *n_out = last.n_out;
     if (tap) *tap->n_blocks = t.n_out;
+    if (sym) *sym->n_sym = y.n_out;
     return SDRG_OK;
 }
 
@@ -4048,6 +4241,14 @@ int32_t sdrg_engine_listen_tones_host(sdrg_engine *e, int32_t steps, const void 
                                       sdrg_tones_record *tone_records, int32_t *n_blocks) {
     const ToneTap tap{powers, tone_records, n_blocks};
     return chain_host(e, Detector::Demod, steps, iq, fmt, out, n_out, squelch_records, agc_records, &tap);
+}
+
+int32_t sdrg_engine_listen_symbols_host(sdrg_engine *e, int32_t steps, const void *iq, int32_t fmt, void *out,
+                                        int32_t *n_out, sdrg_squelch_record *squelch_records,
+                                        sdrg_agc_record *agc_records, void *symbols, sdrg_symbols_record *symbol_records,
+                                        int32_t *n_sym) {
+    const SymbolTap sym{symbols, symbol_records, n_sym};
+    return chain_host(e, Detector::Demod, steps, iq, fmt, out, n_out, squelch_records, agc_records, nullptr, nullptr, &sym);
 }
 
 int32_t sdrg_engine_ddc_demod_host(sdrg_engine *e, const void *iq, int32_t fmt, void *out, int32_t *n_out) {

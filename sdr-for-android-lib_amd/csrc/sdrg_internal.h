@@ -370,6 +370,40 @@ static_assert(SDRG_AFC_MIN_BLOCK == BLOCK_MIN && SDRG_AFC_MAX_BLOCK == BLOCK_MAX
               "the block stages' positions and butterfly");
 hipError_t launch_afc(const float *chan, int n_streams, AfcParams p, float *out, hipStream_t stream);
 
+// Symbol stage (symbols.hip): per stream the n floats at in + stream * in_stride are the positions [off, off + n) of a
+// run of blocks of `block` values, as the block stages' are.  state_old / state_new [n_streams][block + SYM_STATE_HEAD +
+// SYM_HISTORY] floats: {A, B, U, M, Q, coh, tau (uint bits), flags (locked | seeded << 1, int bits), slips (int bits),
+// centre, thr, 0 ...}, the SYM_HISTORY values before the block in progress (+0 for what lies before the stream), then
+// that block's values so far; fresh: state_old is not read (a restarted stream, and off is 0).  mom [blocks][5]
+// [n_streams] floats and blk [blocks + 1][4][n_streams] words are scratch: the completed blocks' Ab, Bb, Ub, Mb and Qb,
+// and (tau, centre, thr, locked) for the call's block j (the block in progress when the call began is block 0).  c0 is
+// c at the call's first value, (uint32)(inc g); cpos0 that at position 0; emit0 = c0, plus 2^32 if the call's first
+// value emits: the call's value t is the last of floor((emit0 + inc t) / 2^32) symbols.  Writes symbols [n_streams][cap]
+// whole (bytes, or floats at soft; zeros from n_sym on), and, if n > 0, state_new; records [n_streams] unless nullptr.
+// n_streams, log2_block and tile are the launcher's.
+struct SymParams {
+    int n, in_stride, block, off, n_blocks, fresh;
+    int levels, track, soft, n_sym, cap;
+    uint32_t inc, c0, cpos0, tau0;
+    uint64_t emit0;
+    int64_t trim;
+    float rinc, beta, beta_level, floor_thr, lock_thr, K, rs, level_scale, fixed_centre, fixed_thr;
+    const float *tab;  // [SDRG_SYM_TABLE][2] on the device
+    const float *state_old;
+    float *state_new;
+    float *mom;
+    uint32_t *blk;
+    sdrg_symbols_record *records;
+    int n_streams, log2_block, tile;
+};
+constexpr int SYM_STATE_HEAD = 14, SYM_HISTORY = SDRG_SYM_HISTORY;
+constexpr int SYM_PASS_TILE = 256;  // symbols per workgroup of the pass kernel, one per lane
+static_assert(SDRG_SYM_MIN_BLOCK >= 64 && SDRG_SYM_MAX_BLOCK == BLOCK_MAX && SDRG_SYM_MAX_IN == BLOCK_MAX_IN &&
+                  (SYM_STATE_HEAD + SYM_HISTORY) % 4 == 0,
+              "the block stages' positions and butterfly: a block is at least a wave's 32 pairs; 16-byte state rows");
+constexpr int sym_state_words(int block) { return SYM_STATE_HEAD + SYM_HISTORY + block; }
+hipError_t launch_symbols(const float *in, int n_streams, SymParams p, void *symbols, hipStream_t stream);
+
 // Noise blanker stage (blanker.hip): per stream the n raw samples at iq + stream * in_stride (in fmt) are the positions
 // [off, off + n) of a run of blocks of `block` samples, as the block stages' are.  state_old / state_new [n_streams]
 // [blanker_state_words(block)] floats: {L, seeded (int bits), the threshold in force for the block in progress, 0}, the

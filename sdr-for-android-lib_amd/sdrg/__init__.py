@@ -165,6 +165,9 @@ EXPORTS = [
     "sdrg_engine_listen_tones_host",
     "sdrg_afc_design", "sdrg_afc_geometry", "sdrg_afc_offset_hz", "sdrg_engine_set_afc", "sdrg_engine_get_afc",
     "sdrg_engine_afc_reset", "sdrg_engine_afc_device", "sdrg_engine_afc_host", "sdrg_engine_listen_afc_host",
+    "sdrg_symbols_design", "sdrg_symbols_geometry", "sdrg_symbols_count", "sdrg_engine_set_symbols",
+    "sdrg_engine_get_symbols", "sdrg_engine_symbols_reset", "sdrg_engine_symbols_max_out", "sdrg_engine_symbols_device",
+    "sdrg_engine_symbols_host", "sdrg_engine_listen_symbols_host",
 ]
 DIST_ID_BYTES = 128  # SDRG_DIST_ID_BYTES (ncclUniqueId)
 
@@ -310,6 +313,32 @@ AfcRecord = np.dtype([("offset_hz", "<f4"), ("step", "<f4"), ("inc", "<i4"), ("c
                       ("level_db", "<f4"), ("held_blocks", "<i4"), ("flags", "<i4")])
 AFC_TRACK, AFC_MEASURE = 1, 2
 AFC_LOCKED, AFC_SEEDED = 1, 2  # sdrg_afc_record.flags
+
+
+class SymbolsConfig(ctypes.Structure):
+    """sdrg_symbols_config: the symbol stage's rates, time constants, floor, lock threshold, trim, levels, block length,
+    format and row length (include/sdrg.h)."""
+    _fields_ = [(k, ctypes.c_double) for k in ("sample_rate", "symbol_rate", "tau_blocks", "tau_level_blocks", "floor_db",
+                                               "lock_threshold", "phase_trim", "level_scale", "fixed_centre",
+                                               "fixed_threshold")] + \
+               [(k, ctypes.c_int32) for k in ("levels", "block", "level_mode", "format", "max_in")]
+
+
+class SymbolsDesign(ctypes.Structure):
+    """sdrg_symbols_design_values: the symbol stage's design but for the table."""
+    _fields_ = [("trim", ctypes.c_int64), ("inc", ctypes.c_uint32)] + \
+               [(k, ctypes.c_float) for k in ("rinc", "beta", "beta_level", "floor_thr", "lock_thr", "K", "rs",
+                                              "scale", "centre", "threshold")]
+
+
+# sdrg_symbols_record
+SymbolsRecord = np.dtype([("tau_frac", "<f4"), ("tau", "<u4"), ("coherence", "<f4"), ("centre", "<f4"),
+                          ("threshold", "<f4"), ("slips", "<i4"), ("held_blocks", "<i4"), ("flags", "<i4")])
+SYM_LEVEL_TRACK, SYM_LEVEL_FIXED = 1, 2
+SYM_HARD, SYM_SOFT = 1, 2
+SYM_LOCKED, SYM_SEEDED = 1, 2  # sdrg_symbols_record.flags
+SYM_UNLOCKED = 0x80            # a SYM_HARD byte sampled while unlocked
+SYM_HISTORY, SYM_TABLE = 66, 1024
 
 
 class BlankerConfig(ctypes.Structure):
@@ -683,6 +712,18 @@ def load() -> ctypes.CDLL:
         "sdrg_engine_afc_device": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_afc_host": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
         "sdrg_engine_listen_afc_host": (_I32, [P, _I32, P, _I32, P, ctypes.POINTER(_I32), P, P, P]),
+        "sdrg_symbols_design": (_I32, [ctypes.POINTER(SymbolsConfig), ctypes.POINTER(SymbolsDesign), P]),
+        "sdrg_symbols_geometry": (_I32, [_I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+        "sdrg_symbols_count": (_I64, [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]),
+        "sdrg_engine_set_symbols": (_I32, [P, ctypes.POINTER(SymbolsConfig)]),
+        "sdrg_engine_get_symbols": (_I32, [P, ctypes.POINTER(SymbolsConfig), ctypes.POINTER(SymbolsDesign),
+                                            ctypes.POINTER(ctypes.c_uint64)]),
+        "sdrg_engine_symbols_reset": (_I32, [P]),
+        "sdrg_engine_symbols_max_out": (_I32, [P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_symbols_device": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_symbols_host": (_I32, [P, P, _I32, _I32, P, P, ctypes.POINTER(_I32)]),
+        "sdrg_engine_listen_symbols_host": (_I32, [P, _I32, P, _I32, P, ctypes.POINTER(_I32), P, P, P, P,
+                                                    ctypes.POINTER(_I32)]),
         "sdrg_engine_set_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig)]),
         "sdrg_engine_get_squelch": (_I32, [P, ctypes.POINTER(SquelchConfig), ctypes.POINTER(_F), ctypes.POINTER(_F),
                                            ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_uint64)]),
@@ -1025,6 +1066,36 @@ def afc_design(**fields) -> dict:
     c, d = _filled(AfcConfig, "afc", fields), AfcDesign()
     _check(load().sdrg_afc_design(ctypes.byref(c), ctypes.byref(d)), "afc_design")
     return _afc_design_dict(d)
+
+
+def _symbols_design_dict(d: SymbolsDesign) -> dict:
+    return {k: (int(getattr(d, k)) if k in ("trim", "inc") else np.float32(getattr(d, k))) for k, _ in SymbolsDesign._fields_}
+
+
+def symbols_design(**fields) -> dict:
+    """The symbol stage's design for a configuration (host-side, no device): trim and inc as int, rinc, beta,
+    beta_level, floor_thr, lock_thr, K, rs, scale, centre and threshold as np.float32, and `table`,
+    float32 [SYM_TABLE][2] (cos, sin).  The fields are sdrg_symbols_config's (fields left out are 0)."""
+    c, d = _filled(SymbolsConfig, "symbols", fields), SymbolsDesign()
+    table = np.empty((SYM_TABLE, 2), np.float32)
+    _check(load().sdrg_symbols_design(ctypes.byref(c), ctypes.byref(d), _ptr(table)), "symbols_design")
+    return dict(_symbols_design_dict(d), table=table)
+
+
+def symbols_geometry(block: int) -> tuple:
+    """(tile, pass_tile): the consecutive values a workgroup of the symbol stage's moments kernel takes (by position in
+    the run of blocks), and the consecutive symbols of a row a workgroup of its pass kernel writes."""
+    t, q = _I32(), _I32()
+    _check(load().sdrg_symbols_geometry(block, ctypes.byref(t), ctypes.byref(q)), "symbols_geometry")
+    return t.value, q.value
+
+
+def symbols_count(inc: int, g: int, n: int) -> int:
+    """sdrg_symbols_count: the symbols a call of n values writes at stream position g."""
+    r = int(load().sdrg_symbols_count(int(inc), int(g), int(n)))
+    if r < 0:
+        raise SdrgError("symbols_count: inc outside [2^26, 2^31]")
+    return r
 
 
 def afc_geometry(block: int) -> int:
@@ -1837,6 +1908,69 @@ class Engine:
         _check(load().sdrg_engine_listen_afc_host(self._h, steps, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out),
                                                   _ptr(sq_rec), _ptr(agc_rec), _ptr(afc_rec)), "listen_afc_host")
         return out[..., :n_out.value], sq_rec, agc_rec, afc_rec
+
+    # ---- symbol stage -----------------------------------------------------------------------------
+    def set_symbols(self, **fields) -> None:
+        """sdrg_engine_set_symbols: the fields of sdrg_symbols_config (fields left out are 0); set_symbols(off=True)
+        switches the stage off."""
+        self._set_stage(SymbolsConfig, "symbols", fields)
+
+    def symbols_config(self) -> dict:
+        """The configuration in force, plus its design (symbols_design's values but for the table), cap (the symbols
+        per row) and samples_consumed."""
+        c, d, g = SymbolsConfig(), SymbolsDesign(), ctypes.c_uint64()
+        _check(load().sdrg_engine_get_symbols(self._h, ctypes.byref(c), ctypes.byref(d), ctypes.byref(g)), "get_symbols")
+        return dict(_as_dict(c), **_symbols_design_dict(d), cap=self.symbols_max_out(), samples_consumed=g.value)
+
+    def symbols_reset(self) -> None:
+        _check(load().sdrg_engine_symbols_reset(self._h), "symbols_reset")
+
+    def symbols_max_out(self) -> int:
+        """cap = floor(inc max_in / 2^32) + 1: the symbols per row of `symbols`."""
+        return self._i32_call(load().sdrg_engine_symbols_max_out, "symbols_max_out")
+
+    def symbols_device(self, in_ptr: int, in_stride: int, n: int, symbols_ptr: int, records_ptr: int | None = None) -> int:
+        """Device path: in [n_streams][in_stride] float32 (the first n of every row are the call's), symbols
+        [n_streams][cap] uint8 (SYM_HARD) or float32 (SYM_SOFT) out and, unless records_ptr is None, [n_streams]
+        SymbolsRecord; asynchronous on the main stream.  Returns n_sym, the symbols the call wrote per row."""
+        return self._i32_call(load().sdrg_engine_symbols_device, "symbols_device", in_ptr, in_stride, n, symbols_ptr,
+                              records_ptr)
+
+    def _symbols_out(self) -> np.ndarray:
+        c = SymbolsConfig()
+        _check(load().sdrg_engine_get_symbols(self._h, ctypes.byref(c), None, None), "get_symbols")
+        return np.empty((self.n_streams, self.symbols_max_out()), np.float32 if c.format == SYM_SOFT else np.uint8)
+
+    def symbols_host(self, values: np.ndarray, want_records: bool = True):
+        """Host path: values is float32 [n_streams][n], n <= max_in.  Returns (symbols [n_streams][n_sym] uint8 or
+        float32, the records [n_streams] SymbolsRecord or None, n_sym)."""
+        values = np.ascontiguousarray(values, np.float32).reshape(self.n_streams, -1)
+        n = values.shape[1]
+        rows = values if n else np.zeros((self.n_streams, 1), np.float32)  # a call without values still wants rows
+        sym = self._symbols_out()
+        rec = np.empty(self.n_streams, SymbolsRecord) if want_records else None
+        n_sym = self._i32_call(load().sdrg_engine_symbols_host, "symbols_host", _ptr(rows), rows.shape[1], n, _ptr(sym),
+                               _ptr(rec))
+        return sym[:, :n_sym], rec, n_sym
+
+    def listen_symbols(self, iq: np.ndarray, fmt: int = CS8, steps: int = 0, want_audio: bool = True,
+                       want_records: bool = True):
+        """sdrg_engine_listen_symbols_host: listen() with the symbol stage reading the demodulator's float audio on the
+        device, ahead of the resampler.  Returns (the audio [n_streams][n_out], or None with want_audio False: it then
+        stays on the device; the squelch's records or None, the AGC's records or None, symbols [n_streams][n_sym], the
+        symbol records or None, n_sym)."""
+        iq, n_out, n_sym = self._iq(iq, fmt), _I32(), _I32()
+        out = None
+        if want_audio:
+            out = self._resample_out() if steps & LISTEN_RESAMPLE else self._demod_out()
+        sq_rec = np.empty(self.n_streams, SquelchRecord) if steps & LISTEN_SQUELCH else None
+        agc_rec = np.empty(self.n_streams, AGC_RECORD_DTYPE) if steps & LISTEN_AGC else None
+        sym = self._symbols_out()
+        rec = np.empty(self.n_streams, SymbolsRecord) if want_records else None
+        _check(load().sdrg_engine_listen_symbols_host(self._h, steps, _ptr(iq), fmt, _ptr(out), ctypes.byref(n_out),
+                                                      _ptr(sq_rec), _ptr(agc_rec), _ptr(sym), _ptr(rec),
+                                                      ctypes.byref(n_sym)), "listen_symbols_host")
+        return (None if out is None else out[..., :n_out.value]), sq_rec, agc_rec, sym[:, :n_sym.value], rec, n_sym.value
 
     # ---- noise blanker stage ----------------------------------------------------------------------
     def set_blanker(self, **fields) -> None:
